@@ -1,11 +1,16 @@
 #!/usr/bin/env python3
 """FSC147 finetune-step throughput of the CounTR HIP engine (BASELINE.json metric).
 
-python bench.py --gpus N --steps K --warmup W      (N > 1: launched by torch.distributed.run, one rank per GPU)
+python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]      (N > 1: launched by torch.distributed.run, one rank per GPU)
 One step = forward (frozen ViT-B/16 encoder + decoder) + masked-MSE + decoder-side backward + gradient all-reduce +
 AdamW on a synthetic batch of 8 images 384x384 with 3 exemplars per GPU (configs[1]); weak scaling.
-Prints ONE JSON line with the whole-job images/sec, the roofline of the attention core kernel (live HIP-event
-timing) and the CPU baseline (the oracle's finetune step on the host cores, bounded sample, rank 0 at N=1 only).
+Prints ONE JSON line with the whole-job images/sec of K timed steps behind W warm-up steps.  --full times the block of K steps
+five times (`value`: the median block) and adds everything else the benchmark measures or checks: the oracle check of the timed
+step (`parity`), the shot-mix loop, the roofline of the attention
+core kernel (live HIP-event timing) and of the kernel families, the other workloads (child processes) and the CPU baseline
+(the oracle's finetune step on the host cores, bounded sample, rank 0 at N=1 only).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32; inputs are seeded, so two builds can be
+compared output for output).
 """
 import argparse
 import json
@@ -482,7 +487,7 @@ def bench_infer(args, world, rank, dev):
 
 
 def other_workloads(args, dev, steps=10, warmup=3):
-    """BASELINE configs[3] and [4] at their single-GPU shapes, timed by the SAME `python bench.py` invocation so that the driver's one run
+    """BASELINE configs[3] and [4] at their single-GPU shapes, timed by the SAME `python bench.py --full` invocation so that one run
     clocks all three single-GPU workloads: MAE pretraining step at 16 images per GPU and zero-shot inference on 8
     frames = 32 windows (C5); `steps` timed steps each behind `warmup` untimed ones.  Each runs in a fresh child process of this script
     (--workload ...) once the headline measurement has released the GPU: inside the parent's process the pretraining step measured
@@ -528,6 +533,35 @@ def other_workloads(args, dev, steps=10, warmup=3):
     return out
 
 
+DUMP_SAMPLE = 1 << 22      # elements: an output larger than this is written as a fixed, seeded sample of it (16 MiB in float32)
+
+
+def _sample(t, seed):
+    """A device tensor as float32 on the host: whole if it has at most DUMP_SAMPLE elements, else (flattened) the elements at
+    DUMP_SAMPLE sorted indices drawn by RandomState(seed) -- the same indices for the same size, run after run."""
+    import numpy as np
+    t = t.detach().float()
+    if t.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.RandomState(seed).randint(0, t.numel(), size=DUMP_SAMPLE))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    return t.cpu().numpy()
+
+
+def dump_outputs(path, model, step, sums, B):
+    """What the last timed step handed its caller: loss, predicted and ground-truth counts (step()'s return), the density map of
+    its forward and the trainable parameters AdamW left (seeded sample: 13.3 M elements at ViT-B)."""
+    import numpy as np
+    from countr_amd.engine import is_trainable
+    step.flush()
+    s = sums.detach().float().cpu().numpy()
+    out = {"loss": s[:1], "pred_counts": s[1:1 + B], "gt_counts": s[1 + B:1 + 2 * B],
+           "density": _sample(step.eng.plan(B, 3, True).buf["out"], 1),        # (the plan's output buffer: [B, 384, 384])
+           "trainable_params": _sample(torch.cat([p.detach().reshape(-1) for n, p in model.named_parameters() if is_trainable(n)]), 2)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 class _Watchdog:
     """Multi-GPU runs replay RCCL all-reduces as nodes of the step's hipGraph -- a path no multi-GPU box has run here yet.  An exception
     there is handled by the trainer (every rank falls back to host-issued collectives); a HANG cannot be.  So the communicating bench
@@ -566,7 +600,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--reps", type=int, default=5, help="the timed block of --steps steps is repeated this often; `value` is the MEDIAN block")
+    ap.add_argument("--reps", type=int, default=None, help="the timed block of --steps steps is repeated this often; `value` is the MEDIAN block "
+                                                            "(default: 1, so that --steps steps are timed; 5 with --full)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the oracle check of the timed step, the shot-mix loop, the "
+                                                         "roofline passes, the other workloads and the CPU baseline (each --no-* below "
+                                                         "drops one of them again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="finetune only: write the last timed step's loss, counts, density map and "
+                                                          "(a seeded sample of) the trainable parameters as DIR/<name>.npy, float32")
     ap.add_argument("--batch", type=int, default=8, help="images per GPU (BASELINE configs[1]: 8)")
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--no-graph", action="store_true")
@@ -590,6 +630,10 @@ def main():
                          "infer = zero-shot sliding-window inference, batch 32 windows (config 5)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl == RCCL; gloo only for single-GPU dry runs)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "finetune":
+        ap.error("--dump-outputs: the finetune workload only")
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launched like the N = 1 run (plain `python bench.py --gpus N`): re-exec under torch.distributed.run, one rank per GPU
@@ -712,7 +756,7 @@ def main():
         time.sleep(3600)
     kick("parity check")
     # (after the warm-up: the checked step REPLAYS the captured graph the timed blocks replay)
-    parity = None if (args.plain or args.no_parity) else parity_check(model, step, world, rank, B, NB, dev, kick=kick)
+    parity = parity_check(model, step, world, rank, B, NB, dev, kick=kick) if (args.full and not args.plain and not args.no_parity) else None
     step.sync.profile = world > 1 or step.sync.comm
     # box-to-box and run-to-run spread (5.3-5.55 ms over the boxes of round 2) is larger than most single optimisations: the block of
     # --steps steps is timed --reps times (each bracketed by barrier + synchronize, max over ranks) and the MEDIAN block is the value
@@ -724,11 +768,15 @@ def main():
     host_ms = 1e3 * host_dt[0] / args.steps
     dts = sorted(b[0] for b in blocks)
     dt, sums = dts[len(dts) // 2], blocks[-1][1]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, step, sums, B)
     exposed = step.sync.exposed_us() if step.sync.profile else None
     comm_mode, host_issued = None, None
     if step.sync.comm:
         comm_mode = "captured" if getattr(step.sync, "capturable", False) else "host-issued"
-        if comm_mode == "captured":
+        if comm_mode == "captured" and not args.full:
+            exposed = None                  # (nothing bracketed in the captured blocks: --full measures it on the extra run below)
+        elif comm_mode == "captured":
             # the headline blocks replayed ONE graph per step with the RCCL all-reduces as nodes of it: nothing to bracket.  The exposed
             # communication is measured on a short extra run in the per-phase-graph mode (host-issued collectives between the phases),
             # whose step time is reported beside it
@@ -756,15 +804,16 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
-    from countr_amd.parallel import shared_shot_num
-    kick("shot mix: capture of the other shot counts")
-    mix = [shared_shot_num(i, seed=0) for i in range(args.steps)]
-    with step.on_stream():
-        for S in sorted(set(mix) | {0, 1, 2}):
-            # build / capture the plans of the other shot counts outside the timed region (pipeline_encoder: the three forms of a step --
-            # own encoder forward + look-ahead, look-ahead only, no look-ahead -- are three graphs per shot count)
-            one(0, S); one(1, S); one(2, S, more=False)
-    dt_mix, _ = timed(mix)
+    if args.full:
+        from countr_amd.parallel import shared_shot_num
+        kick("shot mix: capture of the other shot counts")
+        mix = [shared_shot_num(i, seed=0) for i in range(args.steps)]
+        with step.on_stream():
+            for S in sorted(set(mix) | {0, 1, 2}):
+                # build / capture the plans of the other shot counts outside the timed region (pipeline_encoder: the three forms of a step --
+                # own encoder forward + look-ahead, look-ahead only, no look-ahead -- are three graphs per shot count)
+                one(0, S); one(1, S); one(2, S, more=False)
+        dt_mix, _ = timed(mix)
     loss = sums[0].item()
     ranks_seen = None
     if world > 1:
@@ -801,18 +850,20 @@ def main():
             "timed_region": ("per step (ONE hipGraph replay at N = 1): device-to-device staging of a batch + fresh loss mask + fwd + loss + decoder bwd + "
                              "grad all-reduce + AdamW" + ("; encoder_pipelining: the graph of step k holds batch k + 1's frozen-encoder forward (own lane) "
                              "beside batch k's decoder side -- a timed block of K steps holds exactly K encoder forwards" if step._pipe_ok() else "")),
-            "shot_mix": {"images_per_sec": world * B * args.steps / dt_mix, "ms_per_step": 1e3 * dt_mix / args.steps,
-                         "shot_nums": "uniform 0..3 per step (%s)" % "".join(str(x) for x in mix[:32])},
+            "full": args.full,
         }
-        line["roofline"] = attention_roofline(model, B)
+        if args.full:
+            line["shot_mix"] = {"images_per_sec": world * B * args.steps / dt_mix, "ms_per_step": 1e3 * dt_mix / args.steps,
+                                "shot_nums": "uniform 0..3 per step (%s)" % "".join(str(x) for x in mix[:32])}
+            line["roofline"] = attention_roofline(model, B)
         line["roofline_step"] = {"bound": "mfma", "achieved": GF_STEP_PER_IMG * ips / world / 1e12, "peak": MFMA_BF16_PEAK / 1e12, "unit": "TFLOP/s",
                                  "frac": GF_STEP_PER_IMG * ips / world / MFMA_BF16_PEAK,
                                  "note": "whole step per GPU: 321.16 GF algorithmic per image (SURVEY 8d) x images/s; the sustained full-chip matrix peak "
                                          "is 2.0 PF (1.92 GHz under load), and the GEMM family is bound by the LDS-DMA path (~42 B/clk per CU), DESIGN.md"}
         if world == 1:
-            if not args.no_families:
+            if args.full and not args.no_families:
                 line["roofline_families"] = family_breakdown(model, step, B)
-            if not args.no_b32:
+            if args.full and not args.no_b32:
                 # BASELINE configs[4]: the same kernel at 32 windows (zero-shot inference plan), amortising the per-launch fixed cost
                 model.eval()
                 with torch.no_grad():
@@ -830,10 +881,10 @@ def main():
                                  "note": "buckets in backward-completion order (head | decoder blocks | exemplar CNN | shot_token); every bucket but "
                                          "the last is all-reduced on a side stream under the next backward phase; exposed_comm_us = median time the "
                                          "step stream waited in GradSync.finish() (measured in the host-issued mode: event pairs cannot be captured)"}
-        if world == 1 and not args.no_other and not args.no_graph:
+        if args.full and world == 1 and not args.no_other and not args.no_graph:
             del step
             line["other_workloads"] = other_workloads(args, dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         if wd is not None:
             wd.cancel()

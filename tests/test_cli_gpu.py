@@ -201,8 +201,8 @@ def test_pretrain_cli_on_files_and_synthetic_fallback(fake_fsc, tmp_path):
 
 
 def test_bench_contract_line():
-    """bench.py prints exactly one JSON line with the driver's contract keys, the roofline and (at N = 1) the CPU baseline."""
-    out = run(["bench.py", "--steps", "3", "--warmup", "2"])
+    """bench.py --full prints exactly one JSON line with the driver's contract keys, the roofline and (at N = 1) the CPU baseline."""
+    out = run(["bench.py", "--steps", "3", "--warmup", "2", "--full"])
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     j = json.loads(lines[0])
@@ -222,3 +222,26 @@ def test_bench_contract_line():
     out = run(["bench.py", "--workload", "pretrain", "--steps", "2", "--warmup", "2"])
     p = json.loads([l for l in out.splitlines() if l.startswith("{")][0])
     assert "pretrain" in p["metric"] and p["value"] > 0 and p["n_gpus"] == 1
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """Without --full, bench.py times exactly --steps steps (one block) and measures nothing beside the headline; --dump-outputs writes
+    the last timed step's outputs as float32 .npy files within 64 MB."""
+    d = tmp_path / "out"
+    out = run(["bench.py", "--steps", "4", "--warmup", "2", "--dump-outputs", str(d)])
+    lines = [l for l in out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["steps"] == 4 and j["timed_blocks"] == 1 and j["full"] is False and j["parity_checked"] is False
+    assert j["unit"] == "images/sec" and j["higher_is_better"] is True and j["dtype"] == "bf16"
+    assert abs(j["value"] - 8 * 1e3 / j["ms_per_step"]) < 1e-6 * j["value"]
+    for k in ("shot_mix", "roofline", "roofline_families", "roofline_b32", "other_workloads", "cpu_baseline"):
+        assert k not in j, k
+    got = {f.stem: np.load(f) for f in d.iterdir()}
+    assert set(got) == {"loss", "pred_counts", "gt_counts", "density", "trainable_params"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 * 2 ** 20
+    assert got["loss"][0] == np.float32(j["final_loss"]) and got["density"].shape == (8, 384, 384)
+    assert got["pred_counts"].shape == got["gt_counts"].shape == (8,) and got["trainable_params"].size == 1 << 22
+    # the counts the step returned are those of the density map it wrote
+    assert np.allclose(got["density"].astype(np.float64).sum(axis=(1, 2)) / 60, got["pred_counts"], rtol=1e-3, atol=1e-2)

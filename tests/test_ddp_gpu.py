@@ -194,8 +194,8 @@ def test_bench_self_launch_two_ranks():
     """`python bench.py --gpus 2` started like the N = 1 run (no torch.distributed.run) re-launches itself with one rank per
     requested GPU and reports n_gpus = 2 (gloo on the single GPU of this box)."""
     import json
-    r = run_retry(lambda: [sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"],
-                  dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
+    r = run_retry(lambda: [sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
+                           "--full"], dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert j["n_gpus"] == 2 and j["config"]["global_batch"] == 16 and j["value"] > 0
     # the timed step object is checked against the oracle outside the timed regions -- at N > 1 the all-reduced flat gradient against
@@ -226,11 +226,11 @@ def test_rccl_path_with_one_rank(what, tmp_path):
 
 
 def test_bench_rccl_one_rank():
-    """bench.py through torch.distributed.run with backend nccl on one rank and forced collectives: the launch line the driver uses
+    """bench.py --full through torch.distributed.run with backend nccl on one rank and forced collectives: the launch line the driver uses
     for N > 1, exercised as far as one GPU allows."""
     import json
     cmd = lambda: [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                   "--master-port", str(free_port()), "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"]
+                   "--master-port", str(free_port()), "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--full"]
     r = run_retry(cmd, dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", COUNTR_FORCE_COMM="1", COUNTR_BENCH_INIT_PG="1"))
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert j["n_gpus"] == 1 and j["value"] > 0 and j["parity_checked"] is True
@@ -265,7 +265,7 @@ def test_bench_parity_guard_holds_behind_any_warmup(warmup):
     measures counts against the density map's mass and accepts >= 40 tensors.  --warmup 5 --steps 20 is the driver's command."""
     import json
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20" if warmup == 5 else "3", "--warmup", str(warmup), "--reps", "1",
-                        "--no-other", "--no-cpu-baseline", "--no-families", "--no-b32"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-other", "--no-cpu-baseline", "--no-families", "--no-b32"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-2000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert j["parity_checked"] is True and j["parity"]["count_rel_err"] < 5e-2 and j["parity"]["gradient_tensors"] >= 40

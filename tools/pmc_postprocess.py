@@ -1,4 +1,4 @@
-"""Turns the counter groups of tools/pmc_step.sh (gpurun_out/<tag>_pmc_groups.json) into the round's evidence files:
+"""Turns the counter groups of tools/pmc_step.sh ($COUNTR_OUT/<tag>_pmc_groups.json, default prof_out/) into the round's evidence files:
 profiles/<tag>_family_traffic.json (read by bench.py into roofline_families.{linear,conv}.traffic), <tag>_linear_pmc.txt, <tag>_conv_pmc.txt,
 <tag>_attention_pmc.txt, <tag>_attention_traffic.json.  usage: python tools/pmc_postprocess.py [tag] [algorithmic bytes json from the bench line]
 
@@ -12,7 +12,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r4"
-src = os.path.join(ROOT, "gpurun_out", tag + "_pmc_groups.json")
+src = os.path.join(ROOT, os.environ.get("COUNTR_OUT", "prof_out"), tag + "_pmc_groups.json")
 tmp = "/tmp/%s_re" % tag
 subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "pmc_report.py"), "--json", src, tmp], stdout=subprocess.DEVNULL)
 d = json.load(open(tmp + "_pmc_groups.json"))

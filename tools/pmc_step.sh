@@ -1,11 +1,12 @@
 #!/bin/bash
 # PMC passes over the whole finetune step (eager launches: python bench.py --steps 2 --warmup 2 --no-graph), one rocprofv3 run per counter
 # group (--kernel-trace only; FETCH_SIZE and WRITE_SIZE do not fit one TCC pass), summarised per (kernel, grid) and per family by
-# tools/pmc_report.py.  bash tools/pmc_step.sh <tag> [env assignments...]  ->  gpurun_out/<tag>_pmc_groups.json, <tag>_pmc_report.txt
+# tools/pmc_report.py.  bash tools/pmc_step.sh <tag> [env assignments...]  ->  <tag>_pmc_groups.json, <tag>_pmc_report.txt under $COUNTR_OUT (default prof_out/)
 tag=${1:-pmc}; shift
 export TMPDIR=/tmp
-cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
+cd "$(dirname "$0")/.."
+out=${COUNTR_OUT:-prof_out}
+mkdir -p $out
 dbs=""
 run() {
   rm -rf /tmp/pmcs_$1
@@ -18,5 +19,5 @@ run sq1 "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY
 run lds "SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_VMEM SQ_WAVES"
 run fetch "FETCH_SIZE"
 run write "WRITE_SIZE"
-python tools/pmc_report.py gpurun_out/${tag} $dbs > gpurun_out/${tag}_pmc_report.txt 2>&1
-head -80 gpurun_out/${tag}_pmc_report.txt
+python tools/pmc_report.py $out/${tag} $dbs > $out/${tag}_pmc_report.txt 2>&1
+head -80 $out/${tag}_pmc_report.txt
