@@ -28,10 +28,6 @@
 #include <type_traits>
 #include <utility>
 
-#ifndef CWG_ABL
-#define CWG_ABL 0   // timing experiments (tools/exp_cwg.sh, results are WRONG): 1 = no MFMA, 2 = no fragment reads, 3 = no DMA after the first tiles
-#endif
-
 namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
@@ -122,9 +118,6 @@ __device__ __forceinline__ void cwg_body(const CwgArgs& g, const int v) {
   }
   auto issue = [&](int t, int slot_) {   // called with t = 0, 1, 2, ... in order (the coordinates advance by one tile per call)
     char* dst = smem + slot_ * STAGE_BYTES + cw * 1024;
-#if CWG_ABL == 3
-    if (t >= 2) return;
-#endif
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(srdA, (lds_vptr_t)(dst + i * 4096), 16, voffA, t * tileA + i * passA, 0, 0);
@@ -177,29 +170,11 @@ __device__ __forceinline__ void cwg_body(const CwgArgs& g, const int v) {
   const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, make_uint4(COUNTR_H16_ONE_PAIR, COUNTR_H16_ONE_PAIR, COUNTR_H16_ONE_PAIR, COUNTR_H16_ONE_PAIR));
 
   Frag fr[4][4];   // [set = k-step][a0, a1, b0, b1]
-#if CWG_ABL == 2
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) { fr[a][b].lo = s16x4_t{(short)lane, 1, 2, 3}; fr[a][b].hi = s16x4_t{3, 2, 1, (short)lane}; }
-#endif
   uint32_t a0, a1, b0, b1;
   auto addr = [&](uint32_t sbase) { a0 = sbase + offA[0]; a1 = sbase + offA[1]; b0 = sbase + offB[0]; b1 = sbase + offB[1]; };
-#if CWG_ABL == 2
-#define CWG_RD(SET, Q, KK, A) { fr[SET][Q].lo[0] += (short)(A); }
-#else
 #define CWG_RD(SET, Q, KK, A) { fr[SET][Q].lo = ds_tr<(KK) * 4096>(A); fr[SET][Q].hi = ds_tr<(KK) * 4096 + 1024>(A); }
-#endif
-#if CWG_ABL == 1
-#define CWG_MM(SET, TM, TN) acc[TM][TN][(SET) * 4 + (TM) * 2 + (TN)] += (float)fr[SET][TM].lo[0] * (float)fr[SET][2 + TN].hi[1]
-#else
 #define CWG_MM(SET, TM, TN) acc[TM][TN] = COUNTR_MFMA_32X32X16(frag_bits(fr[SET][TM]), frag_bits(fr[SET][2 + TN]), acc[TM][TN], 0, 0, 0)
-#endif
-#ifdef CWG_NOSB
-#define CWG_SB
-#else
 #define CWG_SB __builtin_amdgcn_sched_barrier(0)
-#endif
 #define CWG_BIAS(SET) if (mine) { accb = COUNTR_MFMA_32X32X16(frag_bits(tmr ? fr[SET][1] : fr[SET][0]), ones, accb, 0, 0, 0); CWG_SB; }
   // MFMAs of set U with the reads of set R = k-step KK of the stage at a0 / a1 / b0 / b1 between them
 #define CWG_STEP_RD(U, R, KK) CWG_MM(U, 0, 0); CWG_SB; CWG_RD(R, 0, KK, a0); CWG_SB; CWG_MM(U, 0, 1); CWG_SB; CWG_RD(R, 2, KK, b0); CWG_SB; \
@@ -536,8 +511,7 @@ int cwg_form(const countr_gemm_args* a, bool lin) {
   int form = ((wide % 256) == 0 && t256 > 0 && (long)(a->K / 64) * t256 >= 8 * 256) ? 2 : 1;
   // three taps of a kernel row per workgroup (conv only) where the map's rows are whole k-tiles and the k-range is long enough that
   // 12 Cout Cin / 128^2 tiles x a chip-filling split leave >= 16 k-tiles each: the 192 x 192 layer
-  bool can3 = !lin && ((a->W % 64) == 0 || (a->W % 96) == 0);
-  { const char* e = getenv("COUNTR_LEAN_WGRAD3"); if (e && atoi(e) == 0) can3 = false; }      // (A/B switch: the round-4 selection)
+  const bool can3 = !lin && ((a->W % 64) == 0 || (a->W % 96) == 0);
   if (can3 && (long)(a->K / 64) * (a->M / 128) * 3 * (a->Cin / 128) >= 16 * 256) form = 3;
   { const char* e = getenv("COUNTR_LEAN_WGRAD_FORM"); if (e) form = atoi(e); }
   if (form == 3 && !can3) form = 2;

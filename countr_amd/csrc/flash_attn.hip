@@ -18,10 +18,7 @@ constexpr int FA_BKV = 64;   // keys per tile
 // Bytes per LDS row of a staged [rows][DH] bf16 tile.  Row pitch = 32 mod 64 bytes makes BOTH fragment reads conflict-free over
 // the 64 LDS banks: ds_read_b128 (16 rows x one 16-byte chunk per 16-lane group) and ds_read_b64_tr_b16 (8 rows x 4 chunks of
 // 8 bytes per 32-lane group).  The former DH*2 + 16 pitch was 2-way conflicted on both (tools/lds_banks.py enumerates them).
-#ifndef COUNTR_FA_PAD
-#define COUNTR_FA_PAD 32
-#endif
-constexpr int fa_pitch(int dh) { return dh * 2 + COUNTR_FA_PAD; }
+constexpr int fa_pitch(int dh) { return dh * 2 + 32; }
 
 }  // namespace
 

@@ -29,12 +29,6 @@
 // v_cvt_pk_bf16_f32 4.7 cycles per wave instruction.  A tile costs a wave 16 MFMAs and ~570 VALU cycles (half of them the 32
 // v_exp_f32), so the loop is VALU-bound by construction at dh = 64.
 #include "common.hpp"
-#ifndef COUNTR_FA_NOPIN
-#define COUNTR_FA_NOPIN 0   // experiments: 1 = no end-of-slot sched_barrier in the pipelined step, 2 = one every fourth slot, 3 = none at all
-#endif
-#ifndef COUNTR_FA_PRIO
-#define COUNTR_FA_PRIO 0
-#endif
 // Round 6: no running row max in the steady state.  P = exp2(S - m_ref) with m_ref = the row max of the FIRST key tile: a later score
 // that exceeds it by d just makes that P 2^d -- exact in fp32 / bfloat16 (a power-of-two factor that cancels in O / l) as long as
 // nothing overflows, and l >= max P tells afterwards whether anything could have.  So the loop carries no v_max3 chain, no cross-lane
@@ -42,10 +36,7 @@
 // lane checks l < 2^64 and O finite, the workgroup ORs the verdicts through one LDS word, and a workgroup with a miss (a row whose
 // later scores exceed the first tile's max by more than 64 in the log2 domain, or non-finite data) runs its strip AGAIN on the exact
 // deferred-rescale loop below -- same result as before, twice the time, for inputs no trained attention produces.  bfloat16 build only:
-// an fp16 P overflows at 2^16, so the fp16 library keeps the running max.  -DCOUNTR_FA_NOMAX=0: the round-2..5 kernel.
-#ifndef COUNTR_FA_NOMAX
-#define COUNTR_FA_NOMAX (!COUNTR_HALF_FP16)
-#endif
+// an fp16 P overflows at 2^16, so the fp16 library keeps the running max (NOMAX below).
 #include <stdlib.h>
 #include <utility>
 
@@ -71,12 +62,12 @@ template <int DH, bool DMA> struct FaCfg {
   static constexpr int OP = DH * 2 + 16;                                // pitch of the output staging rows
   static constexpr int OST = DMA ? 0 : NSLOT * STAGE;                   // DMA: the output staging aliases the (drained) ring
   static constexpr int LDS = DMA ? NSLOT * STAGE : NSLOT * STAGE + 4 * 32 * OP;
-  static constexpr int LDS_ALL = LDS + 16;                              // + the workgroup's "fast path overflowed" word (COUNTR_FA_NOMAX)
+  static constexpr int LDS_ALL = LDS + 16;                              // + the workgroup's "fast path overflowed" word (NOMAX)
   static_assert(!DMA || (DH == 64 && 4 * 32 * OP <= NSLOT * STAGE), "DMA path is laid out for 128-byte rows");
 };
 
 // units of exp work (2 scores each) finished by the end of MFMA slot j; slots = 2*KS QK^T MFMAs then 4*DB PV MFMAs
-// NM (no running max, see COUNTR_FA_NOMAX): the slots MAX0 .. NS-1 carry no row-max work, so the exp units are spread over all slots
+// NM (no running max, see NOMAX): the slots MAX0 .. NS-1 carry no row-max work, so the exp units are spread over all slots
 // (deadlines: the PV MFMA of slot NQK + e reads units 4 (e / DB) .. +3, which must be complete by the end of the slot before it).
 template <int DH, bool NM> struct FaSched;
 template <> struct FaSched<64, false> {
@@ -123,34 +114,22 @@ template <int OFF> __device__ __forceinline__ bf16x8_t fa_read_tr(uint32_t a) { 
 template <int PENDING> __device__ __forceinline__ void fa_lds_wait(bf16x8_t& f) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f) : "n"(PENDING)); }
 template <int PENDING> __device__ __forceinline__ void fa_vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PENDING) : "memory"); }
 
-// ABL (timing experiments only, compiled in by -DCOUNTR_FA_ABL_BUILD=<k>; 1-6 give wrong results): 1 = K/V staged in the prologue only (no loads,
-// LDS stores or barriers in the steps), 2 = 1 + no v_exp, 3 = 1 + no MFMA, 4 = staging and barriers only, 5 = empty kernel,
-// 6 = one tile only (prologue + epilogue), 7 = correct output + s_memtime stamps of wave 0 written to lse (tools/stamp_attn.py),
-// 8 = no fragment reads in the steps (MFMAs on stale registers)
 // PRE: q already carries scale * log2(e) (the frozen encoder's q projection is pre-scaled at weight-packing time, engine.py): the
 // scores come out of the MFMA in the exp2 domain, and because the QK^T accumulators start at -m_ref instead of 0 the softmax
 // needs no subtract / scale FMA at all (one VALU instruction per score less: 32 of ~135 per tile and wave).
-template <int DH, bool RAGGED, int ABL = 0, bool PRE = false>
+template <int DH, bool RAGGED, bool PRE = false>
 __global__ __launch_bounds__(256, 2) void fa_fwd_pipe_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                              float* __restrict__ lse, int N, int H, float c /* scale*log2e */) {
   constexpr bool DMA = DH == 64;
   using C = FaCfg<DH, DMA>;
-  constexpr bool NOMAX = COUNTR_FA_NOMAX && !COUNTR_HALF_FP16 && (ABL == 0 || ABL == 7);
+  constexpr bool NOMAX = !COUNTR_HALF_FP16;
   constexpr int KS = DH / 16;        // QK^T k-steps (16 channels each)
   constexpr int DB = DH / 32;        // 32-channel blocks of O^T
   constexpr int CPR = DH / 8;        // 16-byte chunks per K/V row
   constexpr int RPP = 256 / CPR;     // rows staged per pass of the 256 threads (register path)
   constexpr int PASSES = 64 / RPP;
   constexpr int NQK = 2 * KS;        // MFMA slots of QK^T
-#ifndef COUNTR_FA_LA
-#define COUNTR_FA_LA 5
-#endif
-#ifndef COUNTR_FA_SPLIT
-#define COUNTR_FA_SPLIT 0
-#endif
-  constexpr bool SPLIT = DMA && COUNTR_FA_SPLIT;
-  constexpr int LA = DMA ? COUNTR_FA_LA : 2;   // fragment look-ahead in MFMA slots (register-staged dh = 32 path: compiler-scheduled reads)
-  constexpr bool STAGING = !((ABL >= 1 && ABL <= 3) || ABL == 9 || ABL == 10);   // 9 = 1 + no VALU at all in the steps, 10 = 1 + no row max / rescale
+  constexpr int LA = DMA ? 5 : 2;   // fragment look-ahead in MFMA slots (register-staged dh = 32 path: compiler-scheduled reads)
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63, ql = lane & 31, hh = lane >> 5;
@@ -176,18 +155,8 @@ __global__ __launch_bounds__(256, 2) void fa_fwd_pipe_kernel(const bf16_t* __res
   const bf16_t* kp = qp + H * DH;
   const bf16_t* vp = kp + H * DH;
   const int q0 = qb * 128 + wave * 32;
-  const bool active = (ABL == 4) ? false : q0 < N;   // wave-uniform
-  const int T = (ABL == 6) ? 1 : (N + 63) >> 6;
-  if (ABL == 5 && N > 0) return;
-  uint64_t tk0 = 0, tkc = 0, tks = 0, tkb = 0, tkp = 0;
-  if (ABL == 7) tk0 = __builtin_readcyclecounter();
-#if COUNTR_FA_PRIO   // experiment (round-3 verdict, 3e): static priority by wave slot -- the two waves of a SIMD alternate instead of contending
-  {
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(4, 0, 4)" : "=s"(hw));    // HW_ID.wave_id: the slot of this wave on its SIMD
-    if (hw & 1) __builtin_amdgcn_s_setprio(COUNTR_FA_PRIO);
-  }
-#endif
+  const bool active = q0 < N;   // wave-uniform
+  const int T = (N + 63) >> 6;
 
   // ---- Q^T fragments (MFMA B operand): lane (ql, hh) holds channels 16 ks + 8 hh .. +7 of query q0 + ql
   bf16x8_t qf[KS];
@@ -334,25 +303,10 @@ __global__ __launch_bounds__(256, 2) void fa_fwd_pipe_kernel(const bf16_t* __res
     const int blk = u >> 3, w = u & 7;
     float p0 = PRE ? S[blk][2 * w] : __builtin_fmaf(S[blk][2 * w], c, -mref);
     float p1 = PRE ? S[blk][2 * w + 1] : __builtin_fmaf(S[blk][2 * w + 1], c, -mref);
-    if (ABL != 2) { p0 = __builtin_amdgcn_exp2f(p0); p1 = __builtin_amdgcn_exp2f(p1); }
+    p0 = __builtin_amdgcn_exp2f(p0); p1 = __builtin_amdgcn_exp2f(p1);
     l0 += p0;
     l1 += p1;
     P[blk][w] = pack2bf(p0, p1);
-  };
-  // split form (COUNTR_FA_SPLIT): the two v_exp_f32 of unit u are issued in one MFMA slot, the instructions that consume them (row
-  // sums, bf16 pack) in the next, so that an in-order wave never waits for a transcendental result
-  float pe[16][2];
-  auto exp_only = [&](const f32x16_t (&S)[2], int u) {
-    const int blk = u >> 3, w = u & 7;
-    float p0 = PRE ? S[blk][2 * w] : __builtin_fmaf(S[blk][2 * w], c, -mref);
-    float p1 = PRE ? S[blk][2 * w + 1] : __builtin_fmaf(S[blk][2 * w + 1], c, -mref);
-    pe[u][0] = __builtin_amdgcn_exp2f(p0); pe[u][1] = __builtin_amdgcn_exp2f(p1);
-  };
-  auto exp_finish = [&](int u) {
-    const int blk = u >> 3, w = u & 7;
-    l0 += pe[u][0];
-    l1 += pe[u][1];
-    P[blk][w] = pack2bf(pe[u][0], pe[u][1]);
   };
   auto pfrag = [&](int blk, int s) {
     const u32x4_t v = {P[blk][4 * s], P[blk][4 * s + 1], P[blk][4 * s + 2], P[blk][4 * s + 3]};
@@ -435,16 +389,12 @@ __global__ __launch_bounds__(256, 2) void fa_fwd_pipe_kernel(const bf16_t* __res
     constexpr bool NM = decltype(NMt)::value;
     using SC = FaSched<DH, NM>;
     const int slot = DMA ? (t & 3) : (t & 1);
-    if (STAGING) {
-      if (DMA) {
-        if (t + 2 < T) dma_stage(t + 2);   // slot (t+2)&3 was last read in step t-2: two barriers ago
-      } else {
-        if (t + 2 < T) gload(kp, t + 2, kreg);
-        gload(vp, t + 1, vreg);
-      }
+    if (DMA) {
+      if (t + 2 < T) dma_stage(t + 2);   // slot (t+2)&3 was last read in step t-2: two barriers ago
+    } else {
+      if (t + 2 < T) gload(kp, t + 2, kreg);
+      gload(vp, t + 1, vreg);
     }
-    uint64_t ta = 0, tb = 0, tc = 0;
-    if (ABL == 7) ta = __builtin_readcyclecounter();
     if (active) {
       const char* K = Kslot(slot);
       const char* V = Vslot(slot);
@@ -464,7 +414,6 @@ __global__ __launch_bounds__(256, 2) void fa_fwd_pipe_kernel(const bf16_t* __res
       constexpr auto lds_after = [](int j) { int n = 0; for (int k = 1; k <= LA; ++k) if (j + k < SC::NS) n += (j + k < NQK) ? 1 : 2; return n; };
       auto issue = [&](auto J) {   // fragment read(s) of MFMA slot j
         constexpr int j = J;
-        if constexpr (ABL == 8) { fr[j] = qf[j & (KS - 1)]; return; }     // timing experiment: no fragment reads
         if constexpr (j < NQK) {
           if constexpr (DMA) fr[j] = fa_read_b128<(j & 1) * 4096>(ka[j >> 1]);
           else fr[j] = kfrag(K, j & 1, j >> 1);
@@ -476,10 +425,8 @@ __global__ __launch_bounds__(256, 2) void fa_fwd_pipe_kernel(const bf16_t* __res
       };
       fa_static_for<LA>([&](auto J) { issue(J); });
       float mx = 0.f;
-      if (ABL != 9) {
 #pragma unroll
-        for (int u = 0; u < SC::PRE; ++u) { if (SPLIT) exp_only(Sc, u); else exp_unit(Sc, u); }
-      }
+      for (int u = 0; u < SC::PRE; ++u) exp_unit(Sc, u);
       __builtin_amdgcn_sched_barrier(0);
       fa_static_for<SC::NS>([&](auto J) {
         constexpr int j = J;
@@ -488,15 +435,11 @@ __global__ __launch_bounds__(256, 2) void fa_fwd_pipe_kernel(const bf16_t* __res
           constexpr int pend = lds_after(j);
           static_assert(pend <= 15, "lgkmcnt is a 4-bit counter");
           fa_lds_wait<pend>(fr[j]);
-#if COUNTR_FA_NOPIN != 3
           __builtin_amdgcn_sched_barrier(0);
-#endif
         }
         if constexpr (j < NQK) {
           constexpr int blk = j & 1, ks = j >> 1;
-          if constexpr (ABL == 3) {
-            Sn[blk][ks] = __builtin_bit_cast(float, (int)fr[j][0] | ((int)qf[ks][0] << 16));
-          } else if constexpr (ks == 0) {
+          if constexpr (ks == 0) {
             f32x16_t z;
 #pragma unroll
             for (int i = 0; i < 16; ++i) z[i] = 0.f;
@@ -506,27 +449,12 @@ __global__ __launch_bounds__(256, 2) void fa_fwd_pipe_kernel(const bf16_t* __res
           }
         } else {
           constexpr int e = j - NQK, blk = e / (2 * DB), s = (e / DB) & 1, d = e % DB;
-          if constexpr (ABL == 3) o[d][e] += __builtin_bit_cast(float, (int)fr[j][0] | ((int)pfrag(blk, s)[0] << 16));
-          else o[d] = COUNTR_MFMA_32X32X16(fr[j], pfrag(blk, s), o[d], 0, 0, 0);
+          o[d] = COUNTR_MFMA_32X32X16(fr[j], pfrag(blk, s), o[d], 0, 0, 0);
         }
         constexpr int u0 = (j == 0) ? SC::PRE : SC::unit_end[j == 0 ? 0 : j - 1], u1 = SC::unit_end[j];
-        if constexpr (ABL != 9) {
-          if constexpr (SPLIT) {   // exponentials of this slot's units first, then the consumers of the previous slot's
-            constexpr int f0 = (j == 0) ? 0 : ((j == 1) ? SC::PRE : SC::unit_end[j - 2]);
 #pragma unroll
-            for (int u = u0; u < u1; ++u) exp_only(Sc, u);
-#pragma unroll
-            for (int u = f0; u < u0; ++u) exp_finish(u);
-            if constexpr (j + 1 == SC::NS) {
-#pragma unroll
-              for (int u = u0; u < 16; ++u) exp_finish(u);
-            }
-          } else {
-#pragma unroll
-            for (int u = u0; u < u1; ++u) exp_unit(Sc, u);
-          }
-        }
-        if constexpr (j >= SC::MAX0 && ABL != 9 && ABL != 10) {   // row max of S(t+1), a share per slot
+        for (int u = u0; u < u1; ++u) exp_unit(Sc, u);
+        if constexpr (j >= SC::MAX0) {   // row max of S(t+1), a share per slot
           constexpr int PER = 16 / (SC::NS - SC::MAX0), r0 = (j - SC::MAX0) * PER;
           if (RAGGED && j == SC::MAX0 && t + 2 == T) mask_tail(Sn, t + 1);
           if constexpr (!NM) {
@@ -534,30 +462,18 @@ __global__ __launch_bounds__(256, 2) void fa_fwd_pipe_kernel(const bf16_t* __res
             for (int r = r0; r < r0 + PER; ++r) mx = (r == 0) ? fmaxf(Sn[0][0], Sn[1][0]) : max3(mx, Sn[0][r], Sn[1][r]);
           }
         }
-#if COUNTR_FA_NOPIN == 0
         __builtin_amdgcn_sched_barrier(0);
-#elif COUNTR_FA_NOPIN == 2
-        if constexpr ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);     // a pin every fourth slot only
-#endif
       });
-      if constexpr (!NM) {
-        if (ABL != 9 && ABL != 10) rescale_for(xor32_max(mx), Sn);
-      }
+      if constexpr (!NM) rescale_for(xor32_max(mx), Sn);
     }
-    if (ABL == 7) tb = __builtin_readcyclecounter();
-    if (STAGING) {
-      if (DMA) {
-        vm_wait_pending(stage_count(t + 2));   // stage t+1 has landed (this wave's part); stage t+2 stays in flight
-        if (ABL == 7) tc = __builtin_readcyclecounter();
-        __builtin_amdgcn_s_barrier();
-      } else {
-        if (t + 2 < T) lstore(Kslot(slot ^ 1), C::KP, kreg);
-        lstore(Vslot(slot ^ 1), C::VP, vreg);
-        if (ABL == 7) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tc = __builtin_readcyclecounter(); }
-        __syncthreads();
-      }
+    if (DMA) {
+      vm_wait_pending(stage_count(t + 2));   // stage t+1 has landed (this wave's part); stage t+2 stays in flight
+      __builtin_amdgcn_s_barrier();
+    } else {
+      if (t + 2 < T) lstore(Kslot(slot ^ 1), C::KP, kreg);
+      lstore(Vslot(slot ^ 1), C::VP, vreg);
+      __syncthreads();
     }
-    if (ABL == 7) { const uint64_t td = __builtin_readcyclecounter(); tkc += tb - ta; tks += tc - tb; tkb += td - tc; }
   };
   // ---- last tile: no next scores
   auto tail = [&](const int t, f32x16_t (&Sc)[2]) __attribute__((always_inline)) {
@@ -601,7 +517,6 @@ __global__ __launch_bounds__(256, 2) void fa_fwd_pipe_kernel(const bf16_t* __res
 
   auto attend = [&](auto NMt) __attribute__((always_inline)) {   // prologue + all key tiles
     prologue();
-    if (ABL == 7) tkp = __builtin_readcyclecounter();
     int t = 0;
     for (; t + 2 < T; t += 2) {
       step(NMt, t, SA, SB);
@@ -614,10 +529,8 @@ __global__ __launch_bounds__(256, 2) void fa_fwd_pipe_kernel(const bf16_t* __res
       tail(t, SA);
     }
   };
-  uint64_t tke = 0;
   if constexpr (NOMAX) {
     attend(std::true_type{});
-    if (ABL == 7) tke = __builtin_readcyclecounter();
     if (active) {   // did every P, l and O of this lane stay finite and far from the top of the fp32 range?
       float z = 0.f;
 #pragma unroll
@@ -633,7 +546,6 @@ __global__ __launch_bounds__(256, 2) void fa_fwd_pipe_kernel(const bf16_t* __res
     }
   } else {
     attend(std::false_type{});
-    if (ABL == 7) tke = __builtin_readcyclecounter();
     // ---- epilogue: normalise, stage the wave's [32][DH] bf16 block through its private LDS rows, store whole rows (16-byte chunks)
     if (DMA) __builtin_amdgcn_s_barrier();   // the staging rows alias the ring: every wave is done with the last V tile (no DMA pending)
   }
@@ -649,7 +561,7 @@ __global__ __launch_bounds__(256, 2) void fa_fwd_pipe_kernel(const bf16_t* __res
         *reinterpret_cast<uint2*>(ost + ql * C::OP + (d * 32 + 8 * rg + 4 * hh) * 2) = pk;
       }
     const int q = q0 + ql;
-    if (ABL != 7 && lse && hh == 0 && q < N) lse[((int64_t)b * H + h) * N + q] = (mref + log2f(lt)) * 0.6931471805599453f;
+    if (lse && hh == 0 && q < N) lse[((int64_t)b * H + h) * N + q] = (mref + log2f(lt)) * 0.6931471805599453f;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -659,33 +571,17 @@ __global__ __launch_bounds__(256, 2) void fa_fwd_pipe_kernel(const bf16_t* __res
       if (q0 + r < N) *reinterpret_cast<uint4*>(out + ((int64_t)b * N + q0 + r) * (H * DH) + h * DH + cc * 8) = v;
     }
   }
-  if (ABL == 7 && lse && wave == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint64_t tend = __builtin_readcyclecounter();
-    if (lane == 0) {
-      float* d = lse + blockIdx.x * 8;
-      d[0] = (float)(tend - tk0); d[1] = (float)(tkp - tk0); d[2] = (float)tkc; d[3] = (float)tks; d[4] = (float)tkb;
-      d[5] = (float)(tend - tke); d[6] = (float)(tk0 & 0xffffff); d[7] = (float)(tke - tkp);
-    }
-  }
 }
 
 template <int DH>
 int launch_fa_fwd_pipe(const void* qkv, void* out, float* lse, int B, int N, int H, float c, hipStream_t s) {
   using C = FaCfg<DH, DH == 64>;
   dim3 grid(B * H * ((N + 127) / 128)), block(256);
-#ifdef COUNTR_FA_ABL_BUILD     // timing experiments (bash tools/exp_file.sh flash_attn_fwd abl<k> -DCOUNTR_FA_ABL_BUILD=<k>): results are wrong
-  if (DH == 64 && N % 64 == 0) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fa_fwd_pipe_kernel<64, false, COUNTR_FA_ABL_BUILD>), hipFuncAttributeMaxDynamicSharedMemorySize, FaCfg<64, true>::LDS_ALL);
-    hipLaunchKernelGGL((fa_fwd_pipe_kernel<64, false, COUNTR_FA_ABL_BUILD>), grid, block, (FaCfg<64, true>::LDS_ALL), s, (const bf16_t*)qkv, (bf16_t*)out, lse, N, H, c);
-    COUNTR_LAUNCH_CHECK("countr_attn_fwd (ablation)");
-  }
-#endif
   // the dh = 64 ring is exactly 64 KiB; with the verdict word behind it the workgroup's LDS is a little over the default limit
   if (c <= 0.f) {   // pre-scaled q (see PRE): built for the encoder shape class only
     if (DH != 64 || N % 64) { countr_set_error("countr_attn_fwd: scale <= 0 (pre-scaled q) needs head_dim 64 and N % 64 == 0"); return -1; }
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fa_fwd_pipe_kernel<64, false, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_ALL);
-    hipLaunchKernelGGL((fa_fwd_pipe_kernel<64, false, 0, true>), grid, block, C::LDS_ALL, s, (const bf16_t*)qkv, (bf16_t*)out, lse, N, H, 1.f);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fa_fwd_pipe_kernel<64, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_ALL);
+    hipLaunchKernelGGL((fa_fwd_pipe_kernel<64, false, true>), grid, block, C::LDS_ALL, s, (const bf16_t*)qkv, (bf16_t*)out, lse, N, H, 1.f);
     COUNTR_LAUNCH_CHECK("countr_attn_fwd");
   }
   if (N % 64) {

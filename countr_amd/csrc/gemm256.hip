@@ -24,10 +24,6 @@
 #include <type_traits>
 #include <utility>
 
-#ifndef G256_ABL
-#define G256_ABL 0   // timing experiments (results are WRONG): 1 = no MFMA, 2 = no fragment reads, 3 = no DMA after the prologue
-#endif
-
 namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
@@ -75,11 +71,7 @@ __device__ __forceinline__ uint32_t lds_u32(const char* p) { return (uint32_t)(u
 
 template <int OFF> __device__ __forceinline__ bf16x8_t ds_read128(uint32_t a) {
   bf16x8_t v;
-#if G256_ABL == 2
-  v = __builtin_bit_cast(bf16x8_t, u32x4_t{a, (uint32_t)OFF, 1u, 2u});
-#else
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(a), "n"(OFF));
-#endif
   return v;
 }
 __device__ __forceinline__ void wait4(bf16x8_t (&f)[4]) {
@@ -108,9 +100,6 @@ __device__ __forceinline__ f32x2_t gelu_sig2(f32x2_t x) {
   return x * r;
 }
 
-#ifndef G256_PH
-#define G256_PH 2     // phases per k-tile: 4 = one output quadrant (8 MFMAs) per phase, 2 = two quadrants (16 MFMAs) per phase
-#endif
 #ifndef G256_REC
 #define G256_REC 2    // stamp builds: the pair of k-tiles (2 G256_REC, 2 G256_REC + 1) whose phases are recorded
 #endif
@@ -204,15 +193,12 @@ __global__ __launch_bounds__(512, 2) void g256_kernel(const BigArgs g) {
   // one unit of k-tile t into buffer BUF: KIND 0 = A, 1 = W; U = lo / hi
   auto issue = [&](auto KIND, auto UU, auto BB, int t) {
     constexpr int kind = decltype(KIND)::value, u = decltype(UU)::value, buf = decltype(BB)::value;
-#if G256_ABL == 3
-    if (t >= 2) return;
-#endif
     const uint32_t kill = t < ntiles ? 0u : 0x80000000u;
     char* dst = dma_dst + (kind ? B_BASE : 0) + (2 * u + buf) * UNIT;
     if constexpr (kind == 0) {
       if constexpr (CONV) {
         int tap, cb;
-        countr_conv_ktile(t, g.Cin, tap, cb);
+        countr_conv_ktile(t, tap, cb);
         const int ty = (tap * 11) >> 5, tx = tap - 3 * ty;
         const uint32_t so = (uint32_t)(cshift + ((int64_t)((ty - 1) * g.Wd + (tx - 1)) * g.Cin + cb) * 2);
 #pragma unroll
@@ -234,7 +220,7 @@ __global__ __launch_bounds__(512, 2) void g256_kernel(const BigArgs g) {
     } else {
       const uint32_t vo = voffB | kill;
       uint32_t kb = (uint32_t)t * 128u;            // byte offset of k-tile t inside a W row ([tap][Cin] for a convolution)
-      if constexpr (CONV) { int tap, cb; countr_conv_ktile(t, g.Cin, tap, cb); kb = (uint32_t)(tap * g.Cin + cb) * 2u; }
+      if constexpr (CONV) { int tap, cb; countr_conv_ktile(t, tap, cb); kb = (uint32_t)(tap * g.Cin + cb) * 2u; }
 #pragma unroll
       for (int j = 0; j < 2; ++j)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(srdB, (lds_vptr_t)(dst + j * 8192), 16, vo, kb + (4 * j + u) * passB, 0, 0);
@@ -245,16 +231,10 @@ __global__ __launch_bounds__(512, 2) void g256_kernel(const BigArgs g) {
   // ---- prologue: the stream of units is A-lo, W-lo, W-hi, A-hi per k-tile; six units are ahead of the first phase
   issue(I0{}, I0{}, I0{}, 0); issue(I1{}, I0{}, I0{}, 0); issue(I1{}, I1{}, I0{}, 0); issue(I0{}, I1{}, I0{}, 0);
   issue(I0{}, I0{}, I1{}, 1); issue(I1{}, I0{}, I1{}, 1);
-#if G256_PH == 2
-  issue(I1{}, I1{}, I1{}, 1);      // (two-phase form: the three units a k-tile's first phase reads travel together, seven units ahead)
-#endif
+  issue(I1{}, I1{}, I1{}, 1);      // (the three units a k-tile's first phase reads travel together, seven units ahead)
   if constexpr (LN) {
     // the six partial loads (older than the DMA pieces) have returned
-#if G256_PH == 2
     asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-#else
-    asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-#endif
     if (tid < 256) {
       float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -297,30 +277,14 @@ __global__ __launch_bounds__(512, 2) void g256_kernel(const BigArgs g) {
 
 #define G_SB __builtin_amdgcn_sched_barrier(0)
 #define G_BAR __builtin_amdgcn_s_barrier()
-#if G256_ABL == 1
-#define G_MM(TM, TN, WF, XF) { const u32x4_t a_ = __builtin_bit_cast(u32x4_t, WF), b_ = __builtin_bit_cast(u32x4_t, XF); \
-        acc[TM][TN][0] += __uint_as_float(a_[0] ^ b_[0]); acc[TM][TN][5] += __uint_as_float(a_[1] ^ b_[1]); \
-        acc[TM][TN][10] += __uint_as_float(a_[2] ^ b_[2]); acc[TM][TN][15] += __uint_as_float(a_[3] ^ b_[3]); }
-#else
 #define G_MM(TM, TN, WF, XF) acc[TM][TN] = COUNTR_MFMA_32X32X16(WF, XF, acc[TM][TN], 0, 0, 0)
-#endif
-  // one output quadrant: rows half AH (wave-tile rows 64 AH + [0, 64)), column tile TN, fragments WF[kk] x xa[tm2][kk]
-#ifndef G256_ORDER
-#define G256_ORDER 1
-#endif
-#if G256_ORDER == 0     // the two accumulators alternate (a dependent MFMA every other slot)
-#define G_QUAD(AH, TN, WF)                                                     \
-  G_MM(2 * AH, TN, WF[0], xa[0][0]); G_MM(2 * AH + 1, TN, WF[0], xa[1][0]);    \
-  G_MM(2 * AH, TN, WF[1], xa[0][1]); G_MM(2 * AH + 1, TN, WF[1], xa[1][1]);    \
-  G_MM(2 * AH, TN, WF[2], xa[0][2]); G_MM(2 * AH + 1, TN, WF[2], xa[1][2]);    \
-  G_MM(2 * AH, TN, WF[3], xa[0][3]); G_MM(2 * AH + 1, TN, WF[3], xa[1][3]);
-#else                   // one accumulator's four k-steps back to back (the accumulate-forwarding path), then the other's
+  // one output quadrant: rows half AH (wave-tile rows 64 AH + [0, 64)), column tile TN, fragments WF[kk] x xa[tm2][kk]; one
+  // accumulator's four k-steps back to back (the accumulate-forwarding path), then the other's
 #define G_QUAD(AH, TN, WF)                                                     \
   G_MM(2 * AH, TN, WF[0], xa[0][0]); G_MM(2 * AH, TN, WF[1], xa[0][1]);        \
   G_MM(2 * AH, TN, WF[2], xa[0][2]); G_MM(2 * AH, TN, WF[3], xa[0][3]);        \
   G_MM(2 * AH + 1, TN, WF[0], xa[1][0]); G_MM(2 * AH + 1, TN, WF[1], xa[1][1]); \
   G_MM(2 * AH + 1, TN, WF[2], xa[1][2]); G_MM(2 * AH + 1, TN, WF[3], xa[1][3]);
-#endif
 #define G_P1 __builtin_amdgcn_s_setprio(1)
 #define G_P0 __builtin_amdgcn_s_setprio(0)
 #define G_VM8 asm volatile("s_waitcnt vmcnt(8)" ::: "memory")
@@ -339,85 +303,13 @@ __global__ __launch_bounds__(512, 2) void g256_kernel(const BigArgs g) {
 #define GSTQ(P, I)
 #define GREC(P, TT)
 #endif
-  // one k-tile (buffer BUF) = four phases; in its M part a phase reads fragments, issues ONE unit and waits until at most four units
-  // (eight pieces of this wave) are in flight: the unit read in phase p + 1 was issued five phases earlier and has been waited for by
-  // EVERY wave before the barrier in front of that read (both M halves: the later half passes one more barrier first)
-  auto ktile = [&](auto BB, int t) {
-    constexpr int buf = decltype(BB)::value;
-    using NB = std::integral_constant<int, buf ^ 1>;
-    constexpr int P0 = 4 * buf;
-    // phase 1: A-lo + W-lo of this k-tile; issue W-hi of k-tile t + 1
-    {
-      GSTQ(P0, 0);
-      sfor<2>([&](auto TM2) { sfor<4>([&](auto KK) { constexpr int tm2 = decltype(TM2)::value, kk = decltype(KK)::value;
-        xa[tm2][kk] = ds_read128<(0 + buf) * UNIT + tm2 * 4096>(xad[kk]); }); });
-      sfor<4>([&](auto KK) { constexpr int kk = decltype(KK)::value; wlo[kk] = ds_read128<(0 + buf) * UNIT>(wad[kk]); });
-      issue(I1{}, I1{}, NB{}, t + 1);
-      G_VM8;
-      GSTQ(P0, 1);
-      G_BAR;
-      GSTQ(P0, 2);
-      wait12(xa, wlo); G_SB;
-      GREC((P0 + 7) & 7, t - 1);
-      G_P1; G_QUAD(0, 0, wlo); G_P0; G_SB;
-      GSTQ(P0, 3);
-      G_BAR;
-    }
-    // phase 2: W-hi; issue A-hi of k-tile t + 1
-    {
-      GSTQ(P0 + 1, 0);
-      sfor<4>([&](auto KK) { constexpr int kk = decltype(KK)::value; whi[kk] = ds_read128<(2 + buf) * UNIT>(wad[kk]); });
-      issue(I0{}, I1{}, NB{}, t + 1);
-      G_VM8;
-      GSTQ(P0 + 1, 1);
-      G_BAR;
-      GSTQ(P0 + 1, 2);
-      wait4(whi); G_SB;
-      GREC(P0, t);
-      G_P1; G_QUAD(0, 1, whi); G_P0; G_SB;
-      GSTQ(P0 + 1, 3);
-      G_BAR;
-    }
-    // phase 3: A-hi; issue A-lo of k-tile t + 2 (this buffer: its A-lo / W-lo regions were last read in phase 1)
-    {
-      GSTQ(P0 + 2, 0);
-      sfor<2>([&](auto TM2) { sfor<4>([&](auto KK) { constexpr int tm2 = decltype(TM2)::value, kk = decltype(KK)::value;
-        xa[tm2][kk] = ds_read128<(2 + buf) * UNIT + tm2 * 4096>(xad[kk]); }); });
-      issue(I0{}, I0{}, BB, t + 2);
-      G_VM8;
-      GSTQ(P0 + 2, 1);
-      G_BAR;
-      GSTQ(P0 + 2, 2);
-      wait8(xa); G_SB;
-      GREC(P0 + 1, t);
-      G_P1; G_QUAD(1, 1, whi); G_P0; G_SB;
-      GSTQ(P0 + 2, 3);
-      G_BAR;
-    }
-    // phase 4: no reads; issue W-lo of k-tile t + 2
-    {
-      GSTQ(P0 + 3, 0);
-      issue(I1{}, I0{}, BB, t + 2);
-      G_VM8;
-      GSTQ(P0 + 3, 1);
-      G_BAR;
-      GSTQ(P0 + 3, 2);
-      G_SB;
-      GREC(P0 + 2, t);
-      G_P1; G_QUAD(1, 0, wlo); G_P0; G_SB;
-      GSTQ(P0 + 3, 3);
-      G_BAR;
-    }
-  };
-
-#if G256_PH == 2
-  // Two phases per k-tile (16 MFMAs = 512 matrix cycles each: half the barriers, and the partner half's M part -- which costs the
-  // multiplying wave ~40 cycles per segment whatever its length -- is paid half as often).  X: A-lo, W-lo, W-hi (16 reads) -> quadrants
+  // One k-tile (buffer BUF) = two phases of 16 MFMAs (512 matrix cycles) each: half the barriers of one quadrant per phase, and the
+  // partner half's M part -- which costs the multiplying wave ~40 cycles per segment whatever its length -- is paid half as often.  X: A-lo, W-lo, W-hi (16 reads) -> quadrants
   // (lo, lo), (lo, hi); issues A-hi of k-tile t + 1.  Y: A-hi (8 reads) -> (hi, hi), (hi, lo); issues A-lo, W-lo, W-hi of k-tile t + 2
   // into the regions X has just read: every wave retires its fragment reads (lgkmcnt(0)) BEFORE the mid barrier, so a region may be
   // restaged one phase after its last read.  A unit is waited for (vmcnt(8): at most four units in flight) in the phase before its read,
   // two phases after its issue.
-  auto ktile2 = [&](auto BB, int t) {
+  auto ktile = [&](auto BB, int t) {
     constexpr int buf = decltype(BB)::value;
     using NB = std::integral_constant<int, buf ^ 1>;
     constexpr int P0 = 2 * buf;
@@ -456,19 +348,13 @@ __global__ __launch_bounds__(512, 2) void g256_kernel(const BigArgs g) {
       G_BAR;
     }
   };
-#endif
 
   G_VM8;          // A-lo(0), W-lo(0) of this wave have landed
   G_BAR;          // ... of every wave
   if (wr == 1) G_BAR;     // the second M half runs one barrier behind the first
   for (int t = 0; t < ntiles; t += 2) {
-#if G256_PH == 2
-    ktile2(I0{}, t);
-    ktile2(I1{}, t + 1);
-#else
     ktile(I0{}, t);
     ktile(I1{}, t + 1);
-#endif
   }
   if (wr == 0) G_BAR;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the masked pieces behind the last k-tile

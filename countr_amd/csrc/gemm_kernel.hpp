@@ -231,12 +231,8 @@ template <int ROWS, int NW> struct DmaLoader<COUNTR_OP_ROW, ROWS, NW> {
   __device__ void issue(int k0, int kend, char* lds, int wave) {
 #pragma unroll
     for (int i = 0; i < PASSES; ++i) {
-#if defined(COUNTR_ABL) && COUNTR_ABL == 4   // timing experiment: no per-tile address arithmetic (always the first k-tile)
-      const void* src = (const void*)rp[i];
-#else
       const int k = k0 + kc[i];
       const void* src = ((k + 8) <= kend && rp[i]) ? (const void*)(rp[i] + (int64_t)k * 2) : (const void*)g_zero_page;
-#endif
       dma16(src, lds + (i * NW + wave) * 1024);
     }
   }
@@ -486,13 +482,6 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
   // stage s: A tile at smem + 2*s*OP_BYTES, B tile right behind it
 
   const int tid = threadIdx.x, lane = tid & 63;
-#ifdef COUNTR_GEMM_STAMP   // kernel-level timeline per workgroup (absolute s_memtime): entry, loop start, loop end, exit
-  const uint64_t tl_entry = __builtin_readcyclecounter();
-  uint64_t tl_loop0 = 0, tl_loop1 = 0, tl_x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define TLX(k) tl_x[k] = __builtin_readcyclecounter()
-#else
-#define TLX(k)
-#endif
   const bool loader_wave = SPEC && (tid >> 6) >= WM * WN;
   const int wave = loader_wave ? (tid >> 6) - WM * WN : (tid >> 6);   // index inside its role
   const int tilesN = (g.N + BNt - 1) / BNt;
@@ -505,22 +494,11 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
   // the operand panels of a k-range are fetched by one L2, not by all eight.
   int lt, zz;
   {
-#ifndef COUNTR_ZMAP
-#define COUNTR_ZMAP 1
-#endif
     const int nx = gridDim.x;
-#if COUNTR_ZMAP
     const int lin = blockIdx.x + nx * blockIdx.z, nt_ = nx * gridDim.z;
-#else
-    const int lin = blockIdx.x, nt_ = nx;
-#endif
     const int q = nt_ >> 3, r = nt_ & 7, x = lin & 7, j = lin >> 3;
     const int v = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
-#if COUNTR_ZMAP
     zz = v / nx; lt = v - zz * nx;
-#else
-    zz = blockIdx.z; lt = v;
-#endif
   }
   const int tile_m = lt / tilesN, tile_n = lt - tile_m * tilesN;
   const int m0 = tile_m * BMt, n0 = tile_n * BNt;
@@ -578,7 +556,6 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
     return MPERM ? (((2 * h + ((r >> 2) & 1)) >> 2) * 64 + (r >> 3) * 16 + ((2 * h + ((r >> 2) & 1)) & 3) * 4 + (r & 3)) : (h * 32 + r);
   };
   resid4_t rpre[RPRE_OK ? 2 : 1][RPRE_OK ? 8 : 1];
-  TLX(0);
   if constexpr (RPRE_OK) {
     if (resid_pre) {
 #pragma unroll
@@ -607,8 +584,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
     // profiles/r2_gemm_conv192_pmc.txt.)
     // ... round 4: with the faster kernels of linear.hip / gemm256.hip it does pay in the step (4.62 -> 4.58 ms), and this kernel follows
     // their order on unsplit convolutions so that a sample's result does not depend on which kernel its batch size selects
-    // (common.hpp: COUNTR_CONV_CHUNK_MAJOR)
-    const bool chunk_major = COUNTR_CONV_CHUNK_MAJOR && MA == COUNTR_OP_IM2ROW && kstart == 0 && kend == g.K && g.K == 9 * g.Cin && ntiles <= 79;
+    const bool chunk_major = MA == COUNTR_OP_IM2ROW && kstart == 0 && kend == g.K && g.K == 9 * g.Cin && ntiles <= 79;
     auto ktile = [&](int t) {
       int tt = t + kskew; if (tt >= ntiles) tt -= ntiles;
       if (chunk_major) { const int c = (tt * 57) >> 9; return (tt - 9 * c) * g.Cin + c * BK; }
@@ -617,19 +593,14 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
     constexpr int NLW = SPEC ? NLD : NW;   // waves that stage tiles
     DmaLoader<MA, BMt, NLW> la;
     DmaLoader<MB, BNt, NLW> lb;
-    TLX(1);
     la.init(dA, m0, kstart, wv, lane);
     lb.init(dB, n0, kstart, wv, lane);
-    TLX(2);
     // uniform-base addressing when every k-tile of this launch is full and the operands span < 4 GiB (see DmaLoader); the
     // whole main loop is instantiated twice so that the fast variant carries no per-lane pointer selects
     const bool fullk = ((kend - kstart) % BK) == 0;
     const bool okA = !decltype(la)::HAS_FAST || (((int64_t)g.M * dA.ld * 2 < (int64_t)0xffff0000ll) && (MA != COUNTR_OP_COL || (int64_t)g.K * dA.ld * 2 < (int64_t)0xffff0000ll));
     const bool okB = !decltype(lb)::HAS_FAST || (((int64_t)g.N * dB.ld * 2 < (int64_t)0xffff0000ll) && (MB != COUNTR_OP_COL || (int64_t)g.K * dB.ld * 2 < (int64_t)0xffff0000ll));
     const bool fast_addr = fullk && okA && okB && (decltype(la)::HAS_FAST || decltype(lb)::HAS_FAST);
-#ifndef COUNTR_ABL
-#define COUNTR_ABL 0   // ablation builds (tools/ablate_gemm.sh): 1 = no MFMA, 2 = no fragment reads, 3 = DMA only for tile 0
-#endif
     // optional fused bias gradient: sum_k A(m, k), accumulated by the waves of the first N-tile column only
     const bool do_rowsum = g.rowsum_partial != nullptr && tile_n == 0 && (wave % WN) == 0;
     f32x4_t accb[TMW];
@@ -649,9 +620,6 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
     auto set_tile = [&](const char* sa_, const char* sb_) { sa = lds_addr(sa_); sb = lds_addr(sb_); };
       auto request = [&](auto S) {
         constexpr int s = decltype(S)::value, kk = s / NH, h = s % NH;
-#if COUNTR_ABL == 2
-        for (int q = 0; q < 4; ++q) { xf[s & 1][q] = __builtin_bit_cast(bf16x8_t, make_uint4(lane, q, kk, 1)); if (h == 0) wf[kk][q] = xf[s & 1][q]; }
-#else
         if constexpr (MPERM) {
           const int r0 = mrow(0);
           const uint32_t xa = sa + r0 * 128 + (((kk * 4 + (lane >> 4)) ^ swz_row(r0)) << 4);
@@ -671,7 +639,6 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
               wf[kk][tn] = frag_bf16<MB>(sb, nrow_base + tn * 4, nrow4_base + tn * 4, kk, lane);
           }
         }
-#endif
       };
       auto step = [&](auto S, auto NEXT_, auto WAIT_) {
         constexpr int s = decltype(S)::value, kk = s / NH, h = s % NH, NEXT = decltype(NEXT_)::value;
@@ -680,24 +647,13 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
         static_assert(NEXT != 2 || (((s & 1) == 1) && kk == 1), "the next tile's first request writes xf[0] / wf[0]");
         if constexpr (NEXT == 1) request(std::integral_constant<int, s + 1>{});
         if constexpr (NEXT == 2) request(std::integral_constant<int, 0>{});
-#if COUNTR_ABL != 2
         constexpr int nxt = NEXT == 1 ? XR + (((s + 1) % NH) == 0 ? WR : 0) : (NEXT == 2 ? XR + WR : 0);   // reads allowed to stay in flight
         if constexpr (WAIT) lds_wait<(nxt > 15 ? 15 : nxt)>(xf[s & 1], wf[kk]);                           // lgkmcnt is a 4-bit counter
-#endif
-#if COUNTR_ABL == 1
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const uint4 a = __builtin_bit_cast(uint4, xf[s & 1][q]), b = __builtin_bit_cast(uint4, wf[kk][q]);
-          acc[h * 4 + q][0][0] += __uint_as_float(a.x ^ b.x); acc[h * 4 + q][1][1] += __uint_as_float(a.y ^ b.y);
-          acc[h * 4 + q][2][2] += __uint_as_float(a.z ^ b.z); acc[h * 4 + q][3][3] += __uint_as_float(a.w ^ b.w);
-        }
-#else
 #pragma unroll
         for (int tm = 0; tm < 4; ++tm)
 #pragma unroll
           for (int tn = 0; tn < 4; ++tn)
             acc[h * 4 + tm][tn] = COUNTR_MFMA_16X16X32(wf[kk][tn], xf[s & 1][tm], acc[h * 4 + tm][tn], 0, 0, 0);
-#endif
         if (do_rowsum) {  // wave-uniform: row sums of the M-side operand = bias gradient of a wgrad GEMM
           const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, make_uint4(COUNTR_H16_ONE_PAIR, COUNTR_H16_ONE_PAIR, COUNTR_H16_ONE_PAIR, COUNTR_H16_ONE_PAIR));
 #pragma unroll
@@ -751,13 +707,6 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
       // arrives only after it issued tile t-1's MFMAs (their fragments were read), a loader only after tile t has landed.
       constexpr int PER = DmaLoader<MA, BMt, NLW>::PASSES + DmaLoader<MB, BNt, NLW>::PASSES;
       static_assert((STAGES - 2) * PER <= 63, "vmcnt immediate");
-#ifdef COUNTR_GEMM_STAMP   // loaders: [1] load wait, [2] barrier, [3] DMA issue; compute waves: [2] barrier, [4] fragments + MFMA
-      uint64_t sk1 = 0, sk2 = 0, sk3 = 0, sk4 = 0;
-      const uint64_t sk0 = __builtin_readcyclecounter();
-#define SSTAMP(x) const uint64_t x = __builtin_readcyclecounter()
-#else
-#define SSTAMP(x)
-#endif
       if (loader_wave) {
 #pragma unroll
         for (int s = 0; s < STAGES - 1; ++s)
@@ -767,21 +716,15 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
           }
         int islot = STAGES - 1;
         for (int t = 0; t < ntiles; ++t) {
-          SSTAMP(ua);
           if (t + STAGES - 2 < ntiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((STAGES - 2) * PER) : "memory");
           else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          SSTAMP(ub);
           __builtin_amdgcn_s_barrier();
-          SSTAMP(uc);
           if (t + STAGES - 1 < ntiles) {
             char* nxt = smem + islot * (SA + SB);
             issueA(ktile(t + STAGES - 1), nxt);
             issueB(ktile(t + STAGES - 1), nxt + SA);
           }
           islot = (islot + 1 == STAGES) ? 0 : islot + 1;
-#ifdef COUNTR_GEMM_STAMP
-          { SSTAMP(ud); sk1 += ub - ua; sk2 += uc - ub; sk3 += ud - uc; }
-#endif
         }
       } else {
         // rotated: [steps 0..NS-2 of tile t] -> last step's fragments landed -> barrier t+1 -> request tile t+1's first fragments
@@ -794,31 +737,18 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
           request(I0{});
         }
         for (int t = 0; t + 1 < ntiles; ++t) {
-          SSTAMP(ua);
           steps_but_last();
           wait_frags(std::integral_constant<int, NS - 1>{});
           slot = (slot + 1 == STAGES) ? 0 : slot + 1;
-          SSTAMP(ub);
           __builtin_amdgcn_s_barrier();
           set_tile(smem + slot * (SA + SB), smem + slot * (SA + SB) + SA);
-          SSTAMP(uc);
           step(std::integral_constant<int, NS - 1>{}, I2{}, NO{});
-#ifdef COUNTR_GEMM_STAMP
-          { SSTAMP(ud); sk2 += uc - ub; sk4 += (ub - ua) + (ud - uc); }
-#endif
         }
         if (ntiles > 0) {   // last tile: nothing follows
           steps_but_last();
           step(std::integral_constant<int, NS - 1>{}, I0{}, YES{});
         }
       }
-#ifdef COUNTR_GEMM_STAMP
-      if (g.nbatch == 1 && g.sC1 && lane == 0) {
-        float* d = reinterpret_cast<float*>(g.sC1) + ((int64_t)blockIdx.x * (NW + NLD) + (tid >> 6)) * 8;
-        d[0] = (float)(__builtin_readcyclecounter() - sk0); d[1] = (float)sk1; d[2] = (float)sk2; d[3] = (float)sk3; d[4] = (float)sk4;
-        d[5] = (float)ntiles; d[6] = loader_wave ? 1.f : 2.f;
-      }
-#endif
     } else if constexpr (STAGES >= 3) {
       // Deep pipeline for SMALL grids (<= 1 workgroup per CU, nothing else to hide the DMA round trip): STAGES-1 tiles are in
       // flight while one is multiplied.  Counted vmcnt: DMA loads retire in order, so "at most (STAGES-2) tiles' worth of
@@ -858,53 +788,27 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
       __builtin_amdgcn_s_barrier();
       // (Letting the second wave group of an 8-wave workgroup issue its share of tile t+1 in the MIDDLE of tile t was measured on the
       // experimental 256x256 tile and changes nothing: profiles/r2_gemm_256x256_experiment.txt.)
-#ifdef COUNTR_GEMM_STAMP   // s_memtime anatomy (tools/stamp_gemm.py): per-wave cycles in DMA issue / MFMA steps / load wait / barrier
-      uint64_t tki = 0, tkm = 0, tkw = 0, tkb = 0;
-      const uint64_t tk0 = __builtin_readcyclecounter();
-#define STAMP(x) const uint64_t x = __builtin_readcyclecounter()
-#else
-#define STAMP(x)
-#endif
       for (int t = 0; t < ntiles; ++t) {
         const int cur = t & 1;
         char* nxt = smem + (cur ^ 1) * (SA + SB);
-        const bool more = t + 1 < ntiles && (COUNTR_ABL != 3);
+        const bool more = t + 1 < ntiles;
         auto issue_next = [&] {
           if (more) {
             issueA(ktile(t + 1), nxt);
             issueB(ktile(t + 1), nxt + SA);
           }
         };
-        STAMP(ta);
         set_tile(smem + cur * (SA + SB), smem + cur * (SA + SB) + SA);
         request(I0{});                        // first fragments first: their LDS round trip runs under the DMA issue below
         issue_next();
-        STAMP(tb);
         steps_but_last();
         step(std::integral_constant<int, NS - 1>{}, I0{}, YES{});
-        STAMP(tc);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        STAMP(td);
         __builtin_amdgcn_s_barrier();
-#ifdef COUNTR_GEMM_STAMP
-        { STAMP(te); tki += tb - ta; tkm += tc - tb; tkw += td - tc; tkb += te - td; }
-#endif
       }
-#ifdef COUNTR_GEMM_STAMP
-      if (g.nbatch == 1 && g.sC1 && lane == 0) {   // (stamp builds only: the unused batch stride carries the debug buffer address)
-        float* d = reinterpret_cast<float*>(g.sC1) + ((int64_t)blockIdx.x * NW + wv) * 8;
-        d[0] = (float)(__builtin_readcyclecounter() - tk0); d[1] = (float)tki; d[2] = (float)tkm; d[3] = (float)tkw; d[4] = (float)tkb; d[5] = (float)ntiles;
-      }
-#endif
     }
     };
-#ifdef COUNTR_GEMM_STAMP
-    tl_loop0 = __builtin_readcyclecounter();
-#endif
     if (fast_addr) main_loop(std::true_type{}); else main_loop(std::false_type{});
-#ifdef COUNTR_GEMM_STAMP
-    tl_loop1 = __builtin_readcyclecounter();
-#endif
     // deep rings have no barrier behind the last tile: one here (all waves, loaders included) frees the ring for the staged epilogue
     if constexpr (STAGES >= 3) __builtin_amdgcn_s_barrier();
     if (loader_wave) return;   // no barrier after this point
@@ -1001,10 +905,9 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
       bv[tn][0] = bv[tn][1] = bv[tn][2] = bv[tn][3] = 0.f;
       if (has_bias && nb + tn * 4 < g.N) ld4<float>(g.bias + nb + tn * 4, bv[tn]);
     }
-    TLX(3);
     if constexpr (!GENERIC && sizeof(T) == 2 && (TMW % 2 == 0)) {
       // Staged epilogue: a lane's natural stores are 8-byte (bf16) / 16-byte (fp32) pieces of 16 different rows per instruction
-      // (4 lanes share a row): measured 8-24 % of a forward GEMM (COUNTR_ABL=5).  Instead the wave writes 32 rows x 64 columns of
+      // (4 lanes share a row): measured 8-24 % of a forward GEMM (with the stores removed).  Instead the wave writes 32 rows x 64 columns of
       // finished values (bias / GELU applied) into its private slice of the now idle LDS ring and stores whole row segments:
       // 16-byte chunks, 8 (bf16) or 16 (fp32) consecutive lanes per 128 / 256-byte segment; the fp32 residual is read the same way.
       using OT = std::conditional_t<OBFC, bf16_t, float>;
@@ -1042,7 +945,6 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
           }
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
           __builtin_amdgcn_wave_barrier();
-          if (h == 0) TLX(4);
 #pragma unroll
           for (int j = 0; j < (32 * CPRW) / 64; ++j) {
             const int idx = lane + 64 * j, r = idx / CPRW, cc = idx % CPRW;
@@ -1073,9 +975,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
           }
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
           __builtin_amdgcn_wave_barrier();
-          if (h == 0) TLX(5);
         }
-        TLX(6);
         return;
       }
     }
@@ -1112,13 +1012,8 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] += r[e];
         }
-#if COUNTR_ABL == 5   // timing experiment: no output stores (only an unreachable one keeps the values alive)
-        if (v[0] == 123.456f)
-#endif
-        {
-          if (obf) st4<bf16_t>(reinterpret_cast<bf16_t*>(g.C) + crow + n, v);
-          else st4<float>(reinterpret_cast<float*>(g.C) + crow + n, v);
-        }
+        if (obf) st4<bf16_t>(reinterpret_cast<bf16_t*>(g.C) + crow + n, v);
+        else st4<float>(reinterpret_cast<float*>(g.C) + crow + n, v);
       }
     }
   };
@@ -1136,17 +1031,6 @@ __global__ __launch_bounds__(64 * (WM * WN + NLD)) void gemm_kernel(const countr
     else if (g.act == COUNTR_ACT_NONE && !hb && hr) epilogue(false_type{}, true_type{}, A0{}, false_type{}, false_type{});
     else epilogue(false_type{}, false_type{}, A0{}, false_type{}, true_type{});
   }
-#ifdef COUNTR_GEMM_STAMP
-  if (g.nbatch == 1 && g.sC1 && tid == 0) {   // [workgroup][4] x uint64 behind the per-wave records (float offset 400000)
-    uint64_t* t = reinterpret_cast<uint64_t*>(reinterpret_cast<float*>(g.sC1) + 400000) + (int64_t)blockIdx.x * 4;
-    const uint64_t tl_pre = __builtin_readcyclecounter();   // before waiting for the store acknowledgements
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    t[0] = tl_entry; t[1] = tl_loop0; t[2] = tl_loop1; t[3] = __builtin_readcyclecounter();
-    uint64_t* x = reinterpret_cast<uint64_t*>(reinterpret_cast<float*>(g.sC1) + 500000) + (int64_t)blockIdx.x * 8;
-    for (int k = 0; k < 7; ++k) x[k] = tl_x[k];
-    x[7] = tl_pre;
-  }
-#endif
 }
 
 template <typename T, int MA, int MB, int STAGES, int WM, int WN, int TMW = 4, int NLD = 0>

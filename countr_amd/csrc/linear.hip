@@ -24,10 +24,6 @@
 #include <type_traits>
 #include <utility>
 
-#ifndef LIN_ABL
-#define LIN_ABL 0   // timing experiments (tools/exp_lin.sh, results are WRONG): 1 = no MFMA, 2 = no fragment reads, 3 = no DMA after the first tiles
-#endif
-
 namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
@@ -183,16 +179,13 @@ __global__ __launch_bounds__(256 * WMB * WNB + 64 * NLD, NLD ? ((STAGES == 2 && 
   const __amdgpu_buffer_rsrc_t srdB = __builtin_amdgcn_make_buffer_rsrc((void*)(g.W + (int64_t)n0 * g.ldw * 2), 0, 0x7ffffff0, 0x00020000);
   const uint32_t passA = (uint32_t)(CONV ? g.Cin : g.lda) * (16u * NLW), passB = (uint32_t)g.ldw * (16u * NLW);   // 8 NLW rows further, bytes
   auto issue = [&](int t, int slot) {
-#if LIN_ABL == 3
-    if (t >= 2) return;
-#endif
     char* dst = smem + slot * STAGE_BYTES + cw * 1024;
     uint32_t kb = (uint32_t)t * 128u;              // byte offset of k-tile t inside a W row
     if constexpr (CONV) {
       // k-tile t = 64 channels of one tap (64 | Cin): scalar offset = tap shift + channel block, per-lane pixel offset, and one bit
       // test per piece for the zero padding (offset 2^31 is out of the descriptor's range: the DMA writes zeros)
       int tap, cb;
-      countr_conv_ktile(t, g.Cin, tap, cb);
+      countr_conv_ktile(t, tap, cb);
       kb = (uint32_t)(tap * g.Cin + cb) * 2u;
       const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
       const uint32_t so = (uint32_t)(cshift + ((int64_t)(dy * g.Wd + dx) * g.Cin + cb) * 2);
@@ -326,18 +319,8 @@ __global__ __launch_bounds__(256 * WMB * WNB + 64 * NLD, NLD ? ((STAGES == 2 && 
   auto addr = [&](auto KK) { constexpr int kk = decltype(KK)::value; xa = sbase + xoff[kk]; wa = sbase + woff[kk]; };
   using K0 = std::integral_constant<int, 0>; using K1 = std::integral_constant<int, 1>;
   using K2 = std::integral_constant<int, 2>; using K3 = std::integral_constant<int, 3>;
-#if LIN_ABL == 2
-#define LIN_RD(SET, Q, OFF, A) fr[SET][Q] = __builtin_bit_cast(bf16x8_t, u32x4_t{A, (uint32_t)(OFF), (uint32_t)(Q), 1u})
-#else
 #define LIN_RD(SET, Q, OFF, A) fr[SET][Q] = ds_read128<OFF>(A)
-#endif
-#if LIN_ABL == 1
-#define LIN_MM(SET, TM, TN) { const u32x4_t a_ = __builtin_bit_cast(u32x4_t, fr[SET][2 + TN]), b_ = __builtin_bit_cast(u32x4_t, fr[SET][TM]); \
-        acc[TM][TN][0] += __uint_as_float(a_[0] ^ b_[0]); acc[TM][TN][5] += __uint_as_float(a_[1] ^ b_[1]); \
-        acc[TM][TN][10] += __uint_as_float(a_[2] ^ b_[2]); acc[TM][TN][15] += __uint_as_float(a_[3] ^ b_[3]); }
-#else
 #define LIN_MM(SET, TM, TN) acc[TM][TN] = COUNTR_MFMA_32X32X16(fr[SET][2 + TN], fr[SET][TM], acc[TM][TN], 0, 0, 0)
-#endif
 #define LIN_SB __builtin_amdgcn_sched_barrier(0)
   // MFMAs of set U with the four reads of set R (addresses xa / wa) between them
 #define LIN_STEP_RD(U, R) LIN_MM(U, 0, 0); LIN_SB; LIN_RD(R, 0, 0, xa); LIN_SB; LIN_MM(U, 0, 1); LIN_SB; LIN_RD(R, 2, 0, wa); LIN_SB; \
@@ -345,17 +328,8 @@ __global__ __launch_bounds__(256 * WMB * WNB + 64 * NLD, NLD ? ((STAGES == 2 && 
 #define LIN_STEP(U) LIN_MM(U, 0, 0); LIN_MM(U, 0, 1); LIN_MM(U, 1, 0); LIN_MM(U, 1, 1); LIN_SB
 #define LIN_RD4(SET) LIN_RD(SET, 0, 0, xa); LIN_RD(SET, 1, 4096, xa); LIN_RD(SET, 2, 0, wa); LIN_RD(SET, 3, 4096, wa)
   // 96-row wave tile: the third x fragment and its two MFMAs
-#if LIN_ABL == 2
-#define LIN_RDX2(SET) fr2[SET] = __builtin_bit_cast(bf16x8_t, u32x4_t{xa, 8192u, 9u, 1u})
-#else
 #define LIN_RDX2(SET) fr2[SET] = ds_read128<8192>(xa)
-#endif
-#if LIN_ABL == 1
-#define LIN_MM2(SET, TN) { const u32x4_t a_ = __builtin_bit_cast(u32x4_t, fr[SET][2 + TN]), b_ = __builtin_bit_cast(u32x4_t, fr2[SET]); \
-        acc[TM - 1][TN][0] += __uint_as_float(a_[0] ^ b_[0]); acc[TM - 1][TN][7] += __uint_as_float(a_[2] ^ b_[3]); }
-#else
 #define LIN_MM2(SET, TN) acc[TM - 1][TN] = COUNTR_MFMA_32X32X16(fr[SET][2 + TN], fr2[SET], acc[TM - 1][TN], 0, 0, 0)
-#endif
 #define LIN_STEP6(U) LIN_MM(U, 0, 0); LIN_MM(U, 0, 1); LIN_MM(U, 1, 0); LIN_MM(U, 1, 1); LIN_MM2(U, 0); LIN_MM2(U, 1); LIN_SB
 #ifdef LIN_STAMP   // s_memtime anatomy (tools/stamp_lin.py): loaders [1] load wait [2] barrier [3] DMA issue; compute waves [2] barrier
 #define LSTAMP(x) const uint64_t x = __builtin_readcyclecounter()

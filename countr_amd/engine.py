@@ -258,23 +258,11 @@ class Engine:
         self._ws = {}
         self._need = {}
         self._sizing = False
-        self.reduce_vec4 = True      # 16-byte loads in the deferred-sum kernel
         self._defer = {}             # id(ops) -> (ops, [pending reduction entries]): flushed into countr_reduce_table launches
         self._tables = []
-        self.warm_weights = os.environ.get("COUNTR_WARM", "1") != "0"     # spare workgroups of a GEMM read the next GEMM's (cold) weight panel
-        self.defer_reduce = True     # split-K slabs / bias row sums / LayerNorm block partials are summed by table-driven launches
         self._acc = 0                # accumulate flag baked into the parameter-gradient launches being built (gradient accumulation)
         self.generation = 0
         self._sides = None
-        # (fork / join of the independent backward branches -- wgrad | dgrad | bias grad -- measured a wash, 9.62 vs 9.56 ms, and removed:
-        # the fork / lane / join markers inside the launch lists are ignored by run(); only the exemplar branch's "x" markers fork)
-        self.parallel_lanes = False
-        # forward: the exemplar CNN (~20 launches of fewer than 200 workgroups, ~0.25 ms serial) runs on a side lane beside the encoder.
-        # Round 1 measured this as a loss (6.45 vs 6.20 ms, four graph launches per step); with the whole step in ONE graph it
-        # gains 50-70 us per step at B = 8 (5.63 -> 5.57 ms, three A/B pairs on one box).
-        self.overlap_exemplar = True
-        self.group_wgrads = os.environ.get("COUNTR_GROUP_WGRADS", "1") != "0"   # a block's Linear weight gradients in one launch (A/B switch)
-        self.act_splitk = True       # split-K + finisher for few-tile, long-K forward GEMMs
 
     def _make_layout(self, named_shapes):
         return ParamLayout(named_shapes)
@@ -444,20 +432,12 @@ class Engine:
     def _op(self, ops, fn, *args):
         ops.append((fn, args, None))
 
-    # ---- parallel branches: ops between FORK and JOIN are distributed over up to 3 stream "lanes" (lane 0 = the caller's
-    # stream).  Under graph capture the event fork/join becomes parallel branches of the hipGraph, so independent small
-    # kernels (bias-grad, wgrad, dgrad of one layer) share the GPU instead of running back to back.
-    FORK, JOIN = ("fork",), ("join",)
-
-    def _fork(self, ops):
-        ops.append((None, self.FORK, None))
-
-    def _lane(self, ops, k):
-        ops.append((None, ("lane", k), None))
-
-    def _join(self, ops):
-        ops.append((None, self.JOIN, None))
-
+    # ---- parallel branches: ops between a "fork" and a "join" marker are distributed over up to 3 stream "lanes" (lane 0 = the
+    # caller's stream).  Under graph capture the event fork / join becomes parallel branches of the hipGraph.  The exemplar branch
+    # uses them: its CNN (~20 launches of fewer than 200 workgroups, ~0.25 ms serial) runs on a side lane beside the encoder in the
+    # forward (round 1 measured this as a loss, 6.45 vs 6.20 ms, with four graph launches per step; with the whole step in ONE graph it
+    # gains 50-70 us per step at B = 8, 5.63 -> 5.57 ms) and its token backward beside the decoder blocks' (run_backward_rest_and_tok).
+    # (Forking the independent branches of every layer's backward -- wgrad | dgrad | bias grad -- measured a wash, 9.62 vs 9.56 ms.)
     def _side_streams(self):
         if self._sides is None:
             self._sides = [torch.cuda.Stream(device=self.device) for _ in range(2)]
@@ -505,12 +485,6 @@ class Engine:
                 if kind == "pmain":
                     st = st_main
                     continue
-                if kind[0] == "x":           # forward overlap of the exemplar CNN with the encoder (overlap_exemplar)
-                    if not self.overlap_exemplar:
-                        continue
-                    kind = kind[1:]
-                elif not self.parallel_lanes:
-                    continue
                 sides = self._side_streams()
                 if kind == "fork":
                     self._fork_ev.record(main)
@@ -535,24 +509,21 @@ class Engine:
                 _lib.check(rc, getattr(fn, "__name__", "countr op"))
 
     def run_backward_rest_and_tok(self, lists):
-        """bwd_rest followed by bwd_tok -- or, in bf16 mode with lanes enabled, the exemplar-token backward (~20 launches of fewer than
+        """bwd_rest followed by bwd_tok -- or, in bf16 mode, the exemplar-token backward (~20 launches of fewer than
         200 workgroups, serial in their own dependency chain, headed by the K / V input-gradient GEMMs that build dy_tok) on a side lane
         beside what is left of the decoder-block backward once block 0's cross-attention backward has produced the last dK / dV.  The two branches share no scratch buffer in bf16 mode
         (fp32 mode's unfused bias gradients use one column-sum workspace: it stays serial).  Only for a step without a collective
         between the two lists (one rank)."""
         m = next((k for k, op in enumerate(lists.bwd_rest) if op[0] is None and op[1][0] == "tokready"), None)
-        # (serial as well when the deferred reductions are off -- _conv_wgrad in bwd_tok and _linear_wgrad behind the marker would then
-        # share the 'splitk' / 'rowsum' scratch -- and with COUNTR_PARALLEL_LANES=1, whose nested fork / join inside bwd_tok would take
-        # the rest of that list off the side lane)
-        if m is None or not self.overlap_exemplar or self.code != BF16 or not self.defer_reduce or self.parallel_lanes:
+        if m is None or self.code != BF16:
             self.run(lists.bwd_rest)
             self.run(lists.bwd_tok)
             return
         comb = getattr(lists, "_bwd_comb", None)
         if comb is None:
             mark = lambda *a: (None, a, None)
-            comb = lists._bwd_comb = (lists.bwd_rest[:m] + [mark("xfork"), mark("xlane", 1)] + lists.bwd_tok + [mark("xlane", 0)]
-                                      + lists.bwd_rest[m + 1:] + [mark("xjoin")])
+            comb = lists._bwd_comb = (lists.bwd_rest[:m] + [mark("fork"), mark("lane", 1)] + lists.bwd_tok + [mark("lane", 0)]
+                                      + lists.bwd_rest[m + 1:] + [mark("join")])
         self.run(comb)
 
     # ---- deferred reductions: the split-K slabs of a wgrad, the fused bias-gradient row sums and the LayerNorm dgamma / dbeta block
@@ -584,7 +555,7 @@ class Engine:
         for (pp, op, nslabs, stride, count, N, taps, acc, _owner) in entries:
             wide = int(nslabs > 16 and taps == 0)          # LayerNorm block partials: 16 columns x 16 slab groups per block
             cin = N // taps if taps else 4
-            vec = int(not wide and self.reduce_vec4 and count % 4 == 0 and stride % 4 == 0 and pp % 16 == 0 and op % 16 == 0 and cin % 4 == 0)
+            vec = int(not wide and count % 4 == 0 and stride % 4 == 0 and pp % 16 == 0 and op % 16 == 0 and cin % 4 == 0)
             rows.append([pp, op, nslabs | (acc << 32) | (wide << 33) | (vec << 34), stride, count, N, taps, blk])
             blk += -(-count // (16 if wide else (1024 if vec else 256)))
         tab = torch.tensor(rows, dtype=torch.int64).reshape(-1)
@@ -627,13 +598,13 @@ class Engine:
         again to the fork / join gaps and to the GEMM it ran beside (4.80 vs 4.68 ms).  Results never change.
         `ops` must be in EXECUTION order of one lane; a hint never crosses a fork / lane / join marker (the launch in front of one may
         run beside or after the consumer: wasted bandwidth)."""
-        if not self.warm_weights or self.code != BF16 or self._sizing:
+        if self.code != BF16 or self._sizing:
             return
         bufs = self._weight_buffers()
         nxt = None
         for fn, args, a in reversed(ops):
-            if fn is None and args and (args[0] in ("xfork", "xlane", "xjoin") or (self.parallel_lanes and args[0] in ("fork", "lane", "join"))):
-                nxt = None       # (the plain fork / lane / join markers are inert unless parallel_lanes: run() executes them in list order)
+            if fn is None and args and args[0] in ("fork", "lane", "join"):
+                nxt = None
                 continue
             if fn is not self.L.countr_gemm or a is None:
                 continue
@@ -700,7 +671,7 @@ class Engine:
         no accumulation window the kernel writes the gradient itself (no slab sum).  fp32 mode, or a group the library would run as
         separate launches anyway: the per-layer path."""
         n = len(items)
-        arr = (GemmArgs * n)() if 2 <= n <= 10 and self.code == BF16 and self.group_wgrads else None
+        arr = (GemmArgs * n)() if 2 <= n <= 10 and self.code == BF16 else None
         tiles = 0
         if arr is not None:
             for q, (dy, x, wname, M, N, K, _b) in zip(arr, items):
@@ -767,16 +738,12 @@ class Engine:
     def _linear_bwd(self, ops, dy, x, wname, M, N, K, dx=None, resid=None, dx_bf16=None, gelu_pre=None, group=None):
         """bias grad | weight grad | input grad of one nn.Linear: three independent branches.  group (a list): the weight / bias
         gradient is not launched here but handed to the caller's _linear_wgrad_group (dy and x must stay untouched until then)."""
-        self._fork(ops)
-        self._lane(ops, 2)
         if group is not None:
             group.append((dy, x, wname, M, N, K, wname[:-6] + "bias"))
         else:
             self._linear_wgrad(ops, dy, x, wname, M, N, K, bias_name=wname[:-6] + "bias")
         if dx is not None:
-            self._lane(ops, 0)
             self._linear_dgrad(ops, dy, wname, dx, M, N, K, resid=resid, out_bf16=dx_bf16, gelu_pre=gelu_pre)
-        self._join(ops)
 
     def _cast(self, ops, src_f32, dst_t, n):
         if self.code == F32:
@@ -843,39 +810,31 @@ class Engine:
         dS = self._shared("probs", B * heads * N * N, self.tdt)
         ob = int(self.code == BF16)
         nb = dict(nbatch=B * heads, nb1=heads)
-        self._fork(ops)
-        self._lane(ops, 1)
         # dV[j,d] = sum_i P[i,j] dO[i,d]
         self._gemm(ops, self.code, OP_COL, OP_COL, A=probs.data_ptr(), B=dout.data_ptr(), C=dqkv.data_ptr() + 2 * Dm * es,
                    lda=N, ldb=Dm, ldc=3 * Dm, M=N, N=dh, K=N, sA0=heads * N * N, sA1=N * N, sB0=N * Dm, sB1=dh,
                    sC0=N * 3 * Dm, sC1=dh, out_bf16=ob, **nb)
-        self._lane(ops, 0)
         # dP[i,j] = sum_d dO[i,d] V[j,d]
         self._gemm(ops, self.code, OP_ROW, OP_ROW, A=dout.data_ptr(), B=qkv.data_ptr() + 2 * Dm * es, C=dP.data_ptr(),
                    lda=Dm, ldb=3 * Dm, ldc=N, M=N, N=N, K=dh, sA0=N * Dm, sA1=dh, sB0=N * 3 * Dm, sB1=dh,
                    sC0=heads * N * N, sC1=N * N, out_bf16=0, **nb)
         self._op(ops, self.L.countr_softmax_bwd, probs.data_ptr(), dP.data_ptr(), dS.data_ptr(), B * heads * N, N, scale, self.code)
-        self._join(ops)
-        self._fork(ops)
-        self._lane(ops, 1)
         # dQ[i,d] = sum_j dS[i,j] K[j,d]
         self._gemm(ops, self.code, OP_ROW, OP_COL, A=dS.data_ptr(), B=qkv.data_ptr() + Dm * es, C=dqkv.data_ptr(),
                    lda=N, ldb=3 * Dm, ldc=3 * Dm, M=N, N=dh, K=N, sA0=heads * N * N, sA1=N * N, sB0=N * 3 * Dm, sB1=dh,
                    sC0=N * 3 * Dm, sC1=dh, out_bf16=ob, **nb)
-        self._lane(ops, 0)
         # dK[j,d] = sum_i dS[i,j] Q[i,d]
         self._gemm(ops, self.code, OP_COL, OP_COL, A=dS.data_ptr(), B=qkv.data_ptr(), C=dqkv.data_ptr() + Dm * es,
                    lda=N, ldb=3 * Dm, ldc=3 * Dm, M=N, N=dh, K=N, sA0=heads * N * N, sA1=N * N, sB0=N * 3 * Dm, sB1=dh,
                    sC0=N * 3 * Dm, sC1=dh, out_bf16=ob, **nb)
-        self._join(ops)
 
-    def _act_splitk(self, HW, K):
+    def _fwd_conv_splitk(self, HW, K):
         """Split-K factor for a forward-type convolution (bf16 mode).  On the small maps (<= 24x24 per image) the implicit GEMM has
         few 128x128 tiles and a long K -- decode_head0 forward: 72 tiles x 72 k-tiles = 44 us on a quarter of the CUs; exemplar conv4
         dgrad: 24 x 72 = 43 us -- so K is cut over the idle CUs and a finisher pass (countr_splitk_finish) adds the slabs.  The factor
         depends on the LAYER only (map size, K), never on the batch: the fp32 summation tree of a sample is the same in every batch
         (tests/test_properties_gpu.py: sample i alone == sample i in a batch, bit for bit).  1 = no split."""
-        if self.code != BF16 or not self.act_splitk or HW > 576:
+        if self.code != BF16 or HW > 576:
             return 1
         ktiles = K // 64
         return 8 if ktiles >= 64 else (4 if ktiles >= 32 else 1)
@@ -887,7 +846,7 @@ class Engine:
         that epilogue (countr_gemm_gn_rows: the lean 16-bit kernels on maps of more than 256 tiles), else None -- the caller then keeps
         the statistics pass over the map."""
         M, K = Bn * H * W, 9 * Cin
-        sk = self._act_splitk(H * W, K)
+        sk = self._fwd_conv_splitk(H * W, K)
         if sk == 1 and gn_rows is not None and self.code == BF16 and os.environ.get("COUNTR_GN_ROWS", "1") != "0":
             q = GemmArgs()
             kw = dict(A=x.data_ptr() or 16, B=w_ohwi.data_ptr() or 16, C=out.data_ptr() or 16, bias=bias_ptr, ldb=K, ldc=Cout, M=M, N=Cout, K=K,
@@ -916,35 +875,29 @@ class Engine:
         q.M, q.N, q.K, q.H, q.W, q.Cin, q.lda, q.ldc, q.alpha, q.nbatch, q.nb1 = Cout, 9 * Cin, Kp, H, W, Cin, Cout, 9 * Cin, 1.0, 1, 1
         tiles = int(self.L.countr_gemm_tiles(C.byref(q), self.code, OP_COL, OP_IM2COL))   # 128x128, or 128x256 on the lean kernel
         sk = self._splitk(tiles, -(-Kp // bk))
-        defer = self.defer_reduce
-        cw_key = wname     # one partial buffer per convolution (<= 130 MB each): with a buffer per ROLE every weight gradient forced the pending sums out
-        part = self._shared(("skp." + cw_key) if defer else "splitk", sk * Cout * 9 * Cin)
+        # one partial buffer per convolution (<= 130 MB each): with a buffer per ROLE every weight gradient forced the pending sums out
+        part = self._shared("skp." + wname, sk * Cout * 9 * Cin)
         fuse_bias = bias_name is not None and self.code == BF16
-        rs = self._shared(("rsp." + cw_key) if defer else "rowsum", 64 * 4096) if fuse_bias else None
-        if defer:
-            self._claim(part.data_ptr())
+        rs = self._shared("rsp." + wname, 64 * 4096) if fuse_bias else None
+        self._claim(part.data_ptr())
         kw = dict(A=dy.data_ptr(), B=x.data_ptr(), partial=part.data_ptr(), lda=Cout, ldc=9 * Cin, M=Cout, N=9 * Cin, K=Kp, H=H, W=W,
                   Cin=Cin, splitk=sk)
         rslabs = sk
         if fuse_bias:
-            # the lean weight-gradient kernel (conv_wgrad.hip) deals the bias-gradient work over more waves: more, thinner slabs.  Only
-            # the table-driven finisher sums an arbitrary slab count; countr_splitk_reduce keeps the [splitk][M] layout (rowsum_slabs 0)
+            # the lean weight-gradient kernel (conv_wgrad.hip) deals the bias-gradient work over more waves: more, thinner slabs (the
+            # table-driven finisher sums an arbitrary slab count)
             q = GemmArgs()
             for k_, v_ in kw.items():
                 setattr(q, k_, v_)
             q.alpha, q.nbatch, q.nb1 = 1.0, 1, 1
-            n = int(self.L.countr_gemm_rowsum_slabs(C.byref(q), self.code, OP_COL, OP_IM2COL)) if defer else sk
+            n = int(self.L.countr_gemm_rowsum_slabs(C.byref(q), self.code, OP_COL, OP_IM2COL))
             if n * Cout <= 64 * 4096:
                 rslabs = n
-            kw.update(rowsum_partial=rs.data_ptr(), rowsum_slabs=(rslabs if defer else 0))
+            kw.update(rowsum_partial=rs.data_ptr(), rowsum_slabs=rslabs)
         self._gemm(ops, self.code, OP_COL, OP_IM2COL, **kw)
-        if defer:
-            self._reduce_later(ops, part.data_ptr(), part.data_ptr(), self._gp(wname), sk, Cout * 9 * Cin, Cout * 9 * Cin, N=9 * Cin, taps=9)
-            if fuse_bias:
-                self._reduce_later(ops, part.data_ptr(), rs.data_ptr(), self._gp(bias_name), rslabs, Cout, Cout)
-        else:
-            self._op(ops, self.L.countr_splitk_reduce, part.data_ptr(), self._gp(wname), sk, Cout, 9 * Cin, 9, self._acc,
-                     rs.data_ptr() if fuse_bias else None, self._gp(bias_name) if fuse_bias else None)
+        self._reduce_later(ops, part.data_ptr(), part.data_ptr(), self._gp(wname), sk, Cout * 9 * Cin, Cout * 9 * Cin, N=9 * Cin, taps=9)
+        if fuse_bias:
+            self._reduce_later(ops, part.data_ptr(), rs.data_ptr(), self._gp(bias_name), rslabs, Cout, Cout)
         if bias_name is not None and not fuse_bias:
             self._bias_grad(ops, dy, bias_name, Kp, Cout)
 
@@ -1093,9 +1046,7 @@ class Engine:
         for i in range(self.ddepth):
             b = "decoder_blocks.%d" % i
             wk, wv = b + ".attn.wk.weight", b + ".attn.wv.weight"
-            joint = (lay.off[wv] == lay.off[wk] + Dd * Dd and lay.off[wv[:-6] + "bias"] == lay.off[wk[:-6] + "bias"] + Dd
-                     and os.environ.get("COUNTR_JOINT_KV", "1") != "0")
-            if joint:
+            if lay.off[wv] == lay.off[wk] + Dd * Dd and lay.off[wv[:-6] + "bias"] == lay.off[wk[:-6] + "bias"] + Dd:
                 kvb = A(b + ".kv", (B * Sy, 2 * Dd), T)
                 self._linear(ops, ytok, wk, kvb, B * Sy, 2 * Dd, Dd)
                 kv.append((_Cols(kvb, 0), _Cols(kvb, Dd), 2 * Dd))
@@ -1193,7 +1144,7 @@ class Engine:
             p.fwd_par = p.fwd
         else:     # [fork | lane 1: exemplar CNN | lane 0: encoder + decoder_embed | join | decoder blocks + head]
             mark = lambda *a: (None, a, None)
-            p.fwd_par = ([mark("xfork"), mark("xlane", 1)] + p.fwd[ex[0]:ex[1]] + [mark("xlane", 0)] + p.fwd[:ex[0]] + [mark("xjoin")]
+            p.fwd_par = ([mark("fork"), mark("lane", 1)] + p.fwd[ex[0]:ex[1]] + [mark("lane", 0)] + p.fwd[:ex[0]] + [mark("join")]
                          + p.fwd[ex[1]:])
         if ex is None:
             self._auto_warm(p.fwd)
@@ -1219,50 +1170,37 @@ class Engine:
             for i in (3, 2, 1, 0):
                 hn = "decode_head%d" % i
                 HW = hs[i] * hs[i]
-                # GroupNorm parameter gradients: with deferred reductions the per-block partials {dbeta, dgamma, dw1}[256] stay in this
-                # layer's own workspace and are summed by the table launch that finishes the layer's conv wgrad anyway (they used to
-                # be 2-3 colsum launches of 16 workgroups each: ~80 us per step of latency-bound finishers)
-                defer = self.defer_reduce
-                gws = self._shared("gnbw%d" % i, B * 64 * 3 * 256 + 64 + 16 * B + B * 3 * 256) if defer else gn_ws
-                if defer:
-                    self._claim(gws.data_ptr())
-                gpar = lambda n: None if defer else self._gp(n)
+                # GroupNorm parameter gradients: the per-block partials {dbeta, dgamma, dw1}[256] stay in this layer's own workspace and
+                # are summed by the table launch that finishes the layer's conv wgrad anyway (they used to be 2-3 colsum launches of 16
+                # workgroups each: ~80 us per step of latency-bound finishers)
+                gws = self._shared("gnbw%d" % i, B * 64 * 3 * 256 + 64 + 16 * B + B * 3 * 256)
+                self._claim(gws.data_ptr())
                 if i == 3:
                     self._op(ops, L.countr_groupnorm_relu_bwd, hc[i].data_ptr(), None, d1.data_ptr(), self._pp(hn + ".3.weight"),
                              hstats[i].data_ptr(), self._pp(hn + ".1.weight"), self._pp(hn + ".1.bias"), dpre.data_ptr(),
-                             gpar(hn + ".1.weight"), gpar(hn + ".1.bias"), gpar(hn + ".3.weight"), self._gp(hn + ".3.bias"),
-                             gws.data_ptr(), B, HW, 256, 8, code, self._acc)
+                             None, None, None, self._gp(hn + ".3.bias"), gws.data_ptr(), B, HW, 256, 8, code, self._acc)
                 else:
                     self._op(ops, L.countr_upsample2x_bwd, dup.data_ptr(), dact.data_ptr(), B, hs[i], hs[i], 256, code)
                     self._op(ops, L.countr_groupnorm_relu_bwd, hc[i].data_ptr(), dact.data_ptr(), None, None, hstats[i].data_ptr(),
-                             self._pp(hn + ".1.weight"), self._pp(hn + ".1.bias"), dpre.data_ptr(), gpar(hn + ".1.weight"),
-                             gpar(hn + ".1.bias"), None, None, gws.data_ptr(), B, HW, 256, 8, code, self._acc)
-                if defer:
-                    # the backward's finalize pass leaves per-IMAGE sums behind the split partials: B rows to add, not B * nsplit
-                    img = gws.data_ptr() + 4 * L.countr_groupnorm_bwd_image_sums_offset(B, HW)
-                    planes = [(0, hn + ".1.bias"), (1, hn + ".1.weight")] + ([(2, hn + ".3.weight")] if i == 3 else [])
-                    for plane, pname in planes:
-                        self._reduce_later(ops, gws.data_ptr(), img + plane * 256 * 4, self._gp(pname), B, 3 * 256, 256)
-                big = hs[i] >= 96   # each of these kernels fills the GPU on its own: forking only adds contention
-                if not big:
-                    self._fork(ops)
-                    self._lane(ops, 1)
+                             self._pp(hn + ".1.weight"), self._pp(hn + ".1.bias"), dpre.data_ptr(), None, None, None, None,
+                             gws.data_ptr(), B, HW, 256, 8, code, self._acc)
+                # the backward's finalize pass leaves per-IMAGE sums behind the split partials: B rows to add, not B * nsplit
+                img = gws.data_ptr() + 4 * L.countr_groupnorm_bwd_image_sums_offset(B, HW)
+                planes = [(0, hn + ".1.bias"), (1, hn + ".1.weight")] + ([(2, hn + ".3.weight")] if i == 3 else [])
+                for plane, pname in planes:
+                    self._reduce_later(ops, gws.data_ptr(), img + plane * 256 * 4, self._gp(pname), B, 3 * 256, 256)
                 self._conv_wgrad(ops, dpre, hin[i], hn + ".0.weight", B, hs[i], hs[i], cin[i], 256, bias_name=hn + ".0.bias")
                 # dgrad == forward conv of dpre with the dgrad-form weights (Cin_gemm = 256 output channels)
-                if not big:
-                    self._lane(ops, 0)
                 tgt = dup if i > 0 else ddn
                 self._gemm(ops, code, OP_IM2ROW, OP_ROW, A=dpre.data_ptr(), B=self.Wd[hn + ".0.weight"].data_ptr(), C=tgt.data_ptr(),
                            ldb=9 * 256, ldc=cin[i], M=B * HW, N=cin[i], K=9 * 256, H=hs[i], W=hs[i], Cin=256,
                            out_bf16=int(code == BF16))
-                if not big:
-                    self._join(ops)
             gx = A("gx", (rows, Dd), f32)
             gxT = A("gxT", (rows, Dd), T) if code == BF16 else None
             # grouped weight gradients (bf16): the six Linear weight gradients of a block (and decoder_embed's with the last block's) run
             # as ONE launch behind the block's last LayerNorm backward -- so the operand view of the residual gradient cycles through
             # four buffers (the three versions the deferred launch still reads stay intact while the next one is written)
-            grouped = code == BF16 and self.group_wgrads
+            grouped = code == BF16
             gxT_alt = [gxT] + [A("gxT%d" % k, (rows, Dd), T) for k in (2, 3, 4)] if grouped else [gxT] * 4
             gsel = [0]
 
@@ -1396,14 +1334,13 @@ class Engine:
         In the plain forward the chain hides beside the encoder (p.fwd_par); inline it was the head of the decoder's critical path."""
         dec = p.fwd[p.enc_ops:]
         ex, xi = getattr(p, "ex_range", None), getattr(p, "first_xattn", None)
-        if (ex is None or xi is None or not self.overlap_exemplar or self.code != BF16 or os.environ.get("COUNTR_PIPE_EXEMPLAR_LANE", "1") == "0"
-                or not (p.enc_ops <= ex[0] <= ex[1] <= xi)):
+        if ex is None or xi is None or self.code != BF16 or not (p.enc_ops <= ex[0] <= ex[1] <= xi):
             return dec
         cached = getattr(p, "_dec_lane", None)
         if cached is None:
             mark = lambda *a: (None, a, None)
-            cached = p._dec_lane = ([mark("xfork"), mark("xlane", 1)] + p.fwd[ex[0]:ex[1]] + [mark("xlane", 0)] + p.fwd[p.enc_ops:ex[0]]
-                                    + p.fwd[ex[1]:xi] + [mark("xjoin")] + p.fwd[xi:])
+            cached = p._dec_lane = ([mark("fork"), mark("lane", 1)] + p.fwd[ex[0]:ex[1]] + [mark("lane", 0)] + p.fwd[p.enc_ops:ex[0]]
+                                    + p.fwd[ex[1]:xi] + [mark("join")] + p.fwd[xi:])
         return cached
 
     def forward_loaded_pipelined(self, B, shot_num, have, ahead):
@@ -1486,7 +1423,7 @@ class Engine:
             return
         if getattr(self, "_shadow_tab", None) is None:
             lin = list(self.WtT)                      # Linear weights [N][K]: only the transposed form
-            from16 = self.half and os.environ.get("COUNTR_TRANSPOSE16", "1") != "0" and all(self.layout.shapes[c][0] % 64 == 0 and self.layout.shapes[c][1] % 64 == 0 for c in lin)
+            from16 = self.half and all(self.layout.shapes[c][0] % 64 == 0 and self.layout.shapes[c][1] % 64 == 0 for c in lin)
             self._lin_tab = None
             if lin and from16:
                 m = len(lin)

@@ -121,7 +121,7 @@ class MaeEngine(Engine):
         T, f32 = self.tdt, torch.float32
         A = lambda k, shape, dt: self._alloc(p, tag + k, shape, dt)
         return {"gx": A(".gx", (rows, Dm), f32), "gxT": A(".gxT", (rows, Dm), T) if self.code == BF16 else None,
-                "gxT2": A(".gxT2", (rows, Dm), T) if (self.code == BF16 and self.group_wgrads) else None,
+                "gxT2": A(".gxT2", (rows, Dm), T) if self.code == BF16 else None,
                 "dh": A(".dh", (rows, 4 * Dm), T), "dn_t": A(".dn_t", (rows, Dm), T), "dproj_in": A(".dproj_in", (rows, Dm), T),
                 "dqkv": A(".dqkv", (rows, 3 * Dm), T)}
 

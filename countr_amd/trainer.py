@@ -694,8 +694,6 @@ class FinetuneStep(_GraphStep):
         super().__init__(model, batch, lr, weight_decay, betas, eps, use_graph, process_group, accum_iter, mask_seed)
         self.per_rank = bool(per_rank_shot)
         self.pipe = bool(pipeline_encoder) and os.environ.get("COUNTR_PIPELINE_ENCODER", "1") != "0"
-        sp = os.environ.get("COUNTR_PIPE_SPLIT", "")          # experiments: "nf,nh" launches of the encoder lane at the step's head / in front of
-        self.pipe_split = tuple(int(x) for x in sp.split(",")) if sp else (10 ** 6, 0)      # the head's backward (rest: in front of the blocks' backward)
         self.defer = bool(defer_optimizer) and not self.pipe
         self.mse_ws = torch.zeros(self.eng.L.countr_masked_mse_workspace_floats(batch), device=self.eng.device)
         self.gt = torch.zeros((batch, self.eng.img, self.eng.img), device=self.eng.device)
@@ -716,25 +714,17 @@ class FinetuneStep(_GraphStep):
         _lib.check(eng.L.countr_masked_mse_amp(p.buf["out"].data_ptr(), self.gt.data_ptr(), self.mask.data_ptr(), p.buf["dout"].data_ptr(),
                                                sums.data_ptr(), self.mse_ws.data_ptr(), self.B, HW, 1.0,
                                                self.amp.data_ptr() if self.amp is not None else None, eng._stream()), "masked_mse")
-        if self._cur_pipe in ("steady", "coldnext"):
-            eng.run(self._pipe_part(p, 1))
         eng.run(self._lists(p, acc).bwd_head)
 
     def _prologue_mask(self):
         return self.mask
 
-    def _pipe_part(self, p, k):
-        """Part k of the encoder lane's launches: issued (0) at the head of the step, (1) in front of the head's backward, (2) in front of
-        the decoder blocks' backward -- one ordered lane, forked from the main lane at each of the three points.  `pipe_split` = how many
-        launches the first two parts get (the third takes the rest)."""
-        n = len(p.enc_pipe)
-        nf = min(self.pipe_split[0], n)
-        nh = min(self.pipe_split[1], n - nf)
-        lo, hi = ((0, nf), (nf, nf + nh), (nf + nh, n))[k]
-        if hi <= lo:
+    def _pipe_lane(self, p):
+        """The encoder lane's launches, issued at the head of the step on a lane of their own (forked from the main lane)."""
+        if not p.enc_pipe:
             return []
         mark = lambda *a: (None, a, None)
-        return [mark("pfork")] + p.enc_pipe[lo:hi] + [mark("pmain")]
+        return [mark("pfork")] + p.enc_pipe + [mark("pmain")]
 
     def _fwd_list(self, p, pc):
         """The forward launch list of plan p; with a pending optimizer update pc (defer_optimizer) the list that applies it first:
@@ -748,9 +738,8 @@ class FinetuneStep(_GraphStep):
             assert pc is None
             cache = p.__dict__.setdefault("_pipe_lists", {})
             if mode not in cache:
-                mark = lambda *a: (None, a, None)
                 dec = self.eng.decoder_ops_with_exemplar_lane(p)
-                lane = self._pipe_part(p, 0)
+                lane = self._pipe_lane(p)
                 cache[mode] = {"steady": lane + dec, "last": dec, "coldnext": p.fwd[:p.enc_ops] + lane + dec}[mode]
             return cache[mode]
         if pc is None:
@@ -765,7 +754,7 @@ class FinetuneStep(_GraphStep):
                 lane1, rest = [adam], p.fwd[p.enc_ops:]
             else:
                 lane1, rest = [adam] + p.fwd[ex[0]:ex[1]], p.fwd[p.enc_ops:ex[0]] + p.fwd[ex[1]:]
-            cache[pc] = [mark("xfork"), mark("xlane", 1)] + lane1 + [mark("xlane", 0)] + enc + [mark("xjoin")] + rest
+            cache[pc] = [mark("fork"), mark("lane", 1)] + lane1 + [mark("lane", 0)] + enc + [mark("join")] + rest
         return cache[pc]
 
     def _make_sync(self, process_group):
@@ -798,8 +787,6 @@ class FinetuneStep(_GraphStep):
     def _phase_b(self, key):
         S, acc = key
         p = self.eng.plan(self.B, S, True)
-        if self._cur_pipe in ("steady", "coldnext"):
-            self.eng.run(self._pipe_part(p, 2))
         self.eng.run(self._lists(p, acc).bwd_rest)
 
     def _phase_b2(self, key):
@@ -811,8 +798,6 @@ class FinetuneStep(_GraphStep):
         (_a, fa, ka), (_b, _fb, (S, acc)), (_b2, _fb2, (_S2, acc_tok)) = phases
         fa(ka)
         p = self.eng.plan(self.B, S, True)
-        if self._cur_pipe in ("steady", "coldnext"):
-            self.eng.run(self._pipe_part(p, 2))
         rest, tok = self._lists(p, acc), self._lists(p, acc_tok)
         if rest is tok:
             self.eng.run_backward_rest_and_tok(rest)

@@ -33,7 +33,7 @@ ALG = {
     ("lin_kernel<1, 4, 0, 3, true, 2, false, 2>", 144): ("3x3 convolution 48x48, 256 -> 256, forward / dgrad", B * 48 * 48 * 256 * 2 * 2 + 256 * 2304 * 2),
     ("cwg_kernel<2, false>", 252): ("3x3 convolution weight gradients (average of 192x192 / 96x96 / 48x48 / 24x24: both maps + fp32 dW once)",
                                     (B * (192 * 192 + 96 * 96 + 48 * 48) * 256 * 4 + B * 24 * 24 * (512 + 256) * 2 + 3 * 256 * 2304 * 4 + 256 * 4608 * 4) / 4),
-    ("fa_fwd_pipe_kernel<64, false, 0, true>", 480): ("encoder attention core (q, k, v in, o out)", 28311552),
+    ("fa_fwd_pipe_kernel<64, false, true>", 480): ("encoder attention core (q, k, v in, o out)", 28311552),
 }
 
 

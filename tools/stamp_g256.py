@@ -16,7 +16,7 @@ def show(name, dbg, nwg):
     ok = nt > 0
     print("%s: %d workgroups, loop %.0f cycles per k-tile (2048 matrix cycles), clock %.0f MHz" % (
         name, nwg, (d[ok, 32].double() / nt[ok]).mean().item(), (d[ok, 32].double() / (d[ok, 33].double() * 1e-2)).mean().item()), flush=True)
-    NPH = int(os.environ.get("G256_PH", "2"))       # phases per k-tile of the build
+    NPH = 2                                         # phases per k-tile
     s = d[:, :32].view(-1, 8, 4)[:, : 2 * NPH]
     w = torch.arange(d.shape[0]) % 8
     for half, sel in (("first M half ", (w < 4) & ok), ("second M half", (w >= 4) & ok)):
