@@ -12,6 +12,7 @@ Layouts: tokens [B*N, C]; feature maps NHWC; parameters live in one flat fp32 bu
 the trainable decoder-side region ordered by backward completion so that gradient buckets are contiguous).
 """
 import ctypes as C
+import itertools
 import math
 import os
 import re
@@ -161,6 +162,20 @@ class _Cols:
         return self.t.data_ptr() + self.off * self.t.element_size()
 
 
+# ---- schedules.  A launch list holds ops (fn, args, keep) and markers (fn is None) that Engine.run() turns into stream changes:
+# ops between FORK and JOIN are distributed over up to 3 stream "lanes" (lane 0 = the caller's stream); PFORK ... PMAIN puts the
+# pipelined encoder on a lane of its own that Engine.pipe_join() closes.
+FORK, JOIN = (None, ("fork",), None), (None, ("join",), None)
+LANE0, LANE1 = (None, ("lane", 0), None), (None, ("lane", 1), None)
+PFORK, PMAIN = (None, ("pfork",), None), (None, ("pmain",), None)
+LANE_BOUNDS = {m[1][0] for m in (FORK, LANE0, LANE1, JOIN)}      # the marker kinds a warm-up hint never crosses (_auto_warm)
+
+
+def side_by_side(side, main):
+    """[fork | lane 1: side | lane 0: main | join]"""
+    return [FORK, LANE1] + side + [LANE0] + main + [JOIN]
+
+
 class Plan:
     """Launch lists + buffers for one (B, S, train) configuration."""
 
@@ -170,8 +185,16 @@ class Plan:
         self.bwd_head = []   # backward until bucket 0 (head + decoder_norm) gradients are final
         self.bwd_rest = []   # ... until bucket 1 (decoder blocks + decoder_embed) is final
         self.bwd_tok = []    # exemplar tokens: exemplar CNN (bucket 2) or shot_token (bucket 3)
+        self.tok_ready = None   # index into bwd_rest from which bwd_tok may run beside it (Engine.run_backward_rest_and_tok)
         self.acc = None      # the same three lists with parameter gradients ACCUMULATED (micro-steps 2.. of gradient accumulation)
         self.buf = {}
+        self.enc_ops = None  # fwd[:enc_ops] is the encoder
+        self.enc_pipe = None    # the encoder's launches on the shared look-ahead buffers below (Engine._encoder_pipe_variant), or None
+        self.pipe_img = self.pipe_latent = self.pipe_latent_bytes = None
+        self.ex_range = None    # fwd[ex_range[0]:ex_range[1]]: exemplar CNN + the k | v projections (plans with exemplars)
+        self.first_xattn = None  # index into fwd of the first launch that reads the keys / values
+        self.fwd_gen = 0     # train-mode forwards run on this plan's buffers so far (models_mae_cross._DecoderFn)
+        self.sched = {}      # schedules derived from the lists above, built on first use (Engine.decoder_ops_with_exemplar_lane, ...)
 
 
 class Engine:
@@ -262,7 +285,11 @@ class Engine:
         self._tables = []
         self._acc = 0                # accumulate flag baked into the parameter-gradient launches being built (gradient accumulation)
         self.generation = 0
-        self._sides = None
+        # streams and events of run()'s lanes, created on first use (_side_streams, _pipe_stream)
+        self._sides = self._fork_ev = self._join_ev = None
+        self._pipe = self._pipe_ev = None
+        self._pipe_token = None      # pipe_claim()
+        self._shadow_tab = self._lin_tab = None      # pointer tables of _refresh_conv_shadows
 
     def _make_layout(self, named_shapes):
         return ParamLayout(named_shapes)
@@ -446,7 +473,7 @@ class Engine:
         return self._sides
 
     def _pipe_stream(self):
-        if getattr(self, "_pipe", None) is None:
+        if self._pipe is None:
             self._pipe = torch.cuda.Stream(device=self.device)
             self._pipe_ev = [torch.cuda.Event(), torch.cuda.Event()]
         return self._pipe
@@ -458,7 +485,7 @@ class Engine:
         return self._pipe_token
 
     def pipe_owner(self, token):
-        return token is not None and getattr(self, "_pipe_token", None) is token
+        return token is not None and self._pipe_token is token
 
     def pipe_join(self):
         """The caller's stream waits for the pipelined-encoder lane (the closing edge of run()'s "pfork")."""
@@ -474,8 +501,6 @@ class Engine:
         for fn, args, _keep in ops:
             if fn is None:
                 kind = args[0]
-                if kind == "tokready":
-                    continue
                 if kind == "pfork":          # pipelined encoder (trainer.FinetuneStep(pipeline_encoder=True)): the next batch's frozen-encoder
                     ps = self._pipe_stream()         # forward on its own lane beside this batch's decoder side; joined by pipe_join()
                     self._pipe_ev[0].record(main)
@@ -514,17 +539,14 @@ class Engine:
         beside what is left of the decoder-block backward once block 0's cross-attention backward has produced the last dK / dV.  The two branches share no scratch buffer in bf16 mode
         (fp32 mode's unfused bias gradients use one column-sum workspace: it stays serial).  Only for a step without a collective
         between the two lists (one rank)."""
-        m = next((k for k, op in enumerate(lists.bwd_rest) if op[0] is None and op[1][0] == "tokready"), None)
+        m = lists.tok_ready
         if m is None or self.code != BF16:
             self.run(lists.bwd_rest)
             self.run(lists.bwd_tok)
             return
-        comb = getattr(lists, "_bwd_comb", None)
-        if comb is None:
-            mark = lambda *a: (None, a, None)
-            comb = lists._bwd_comb = (lists.bwd_rest[:m] + [mark("fork"), mark("lane", 1)] + lists.bwd_tok + [mark("lane", 0)]
-                                      + lists.bwd_rest[m + 1:] + [mark("join")])
-        self.run(comb)
+        if "bwd_rest_tok" not in lists.sched:
+            lists.sched["bwd_rest_tok"] = lists.bwd_rest[:m] + side_by_side(lists.bwd_tok, lists.bwd_rest[m:])
+        self.run(lists.sched["bwd_rest_tok"])
 
     # ---- deferred reductions: the split-K slabs of a wgrad, the fused bias-gradient row sums and the LayerNorm dgamma / dbeta block
     # partials are not finished by one ~5-9 us launch each but collected per launch list and summed by ONE table-driven launch
@@ -603,7 +625,7 @@ class Engine:
         bufs = self._weight_buffers()
         nxt = None
         for fn, args, a in reversed(ops):
-            if fn is None and args and args[0] in ("fork", "lane", "join"):
+            if fn is None and args and args[0] in LANE_BOUNDS:
                 nxt = None
                 continue
             if fn is not self.L.countr_gemm or a is None:
@@ -902,20 +924,24 @@ class Engine:
             self._bias_grad(ops, dy, bias_name, Kp, Cout)
 
     # ------------------------------------------------------------------ plan construction
-    def plan(self, B, S, train):
-        key = (B, S, bool(train))
+    def _sized_with(self, S, train):
+        """The (S, train) combinations whose shared scratch is sized together with plan (B, S, train): EVERY shot count and both modes
+        of this batch size at once, so that building another plan later never moves scratch that launch lists (and captured graphs)
+        already point to."""
         if train and self.forward_only:
             raise _lib.CountrError("this configuration (patch %d on %d pixels, head_dim %d) runs forward-only: its density map is %d x %d, "
                                    "which the reference's training loss (FSC_finetune_cross.py:294, against a %d x %d ground truth) cannot "
                                    "consume either" % (self.patch, self.img, self.D // self.H, 16 * self.grid, 16 * self.grid, self.img, self.img))
+        return [(s_, tr) for s_ in sorted({0, 1, 2, 3, S}) for tr in ((False,) if self.forward_only else (False, True))]
+
+    def plan(self, B, S, train):
+        key = (B, S, bool(train))
         if key not in self.plans:
-            # size the shared scratch for EVERY shot count and both modes of this batch size at once, so that building
-            # another plan later never moves scratch that launch lists (and captured graphs) already point to
+            combos = self._sized_with(S, train)
             self._sizing = True
             try:
-                for s_ in sorted({0, 1, 2, 3, S}):
-                    for tr in ((False,) if self.forward_only else (False, True)):
-                        self._build(B, s_, tr)
+                for s_, tr in combos:
+                    self._build(B, s_, tr)
             finally:
                 self._sizing = False
             self._reserve()
@@ -923,16 +949,49 @@ class Engine:
         return self.plans[key]
 
     def _build(self, B, S, train):
-        L = self.L
+        """The stages below in order; each takes the launch list and the plan, allocates its buffers, appends its launches and returns
+        what later stages read."""
         p = Plan()
-        T, f32 = self.tdt, torch.float32
-        N, D, Dd, H, Hd = self.N, self.D, self.Dd, self.H, self.Hd
-        rows = B * N
-        code = self.code
-        ops = p.fwd
-        A = lambda k, shape, dt: self._alloc(p, k, shape, dt)
+        ops, rows = p.fwd, B * self.N
+        # ---------------- forward: models_mae_cross.py:136-148 (encoder, no grad), :150-199 (decoder)
+        enc = self._encoder_fwd(ops, p, B)
+        self._encoder_pipe_variant(p, B, enc)
+        x = self._alloc(p, "dx0", (rows, self.Dd), torch.float32)
+        self._linear(ops, enc["latent"], "decoder_embed.weight", x, rows, self.Dd, self.D, resid=self._pp("decoder_pos_embed"), res_mod=self.N)
+        tok = self._exemplar_tokens_fwd(ops, p, B, S, train)
+        kv = self._kv_fwd(ops, p, B, tok)
+        if S > 0:
+            p.ex_range = (tok["ex0"], len(ops))
+        blk = []
+        for i in range(self.ddepth):
+            blk.append(self._dec_block_fwd(ops, p, i, x, kv[i], B, tok["Sy"], train))
+            x = blk[-1]["x3"]
+        head = self._head_fwd(ops, p, B, x)
+        self._finish_forward(p)
+        if not train:
+            return p
 
-        # ---------------- encoder (no grad): models_mae_cross.py:136-148
+        # ---------------- backward (decoder side only), twice over the same buffers: overwrite / accumulate the parameter gradients
+        p.acc = Plan()
+        for acc, lists in ((0, p), (1, p.acc)):
+            self._acc = acc
+            s = self._bwd_scratch(p, B, tok)
+            g_t = self._head_bwd(lists.bwd_head, p, B, head, s)
+            tok_dgrads = []
+            for i in reversed(range(self.ddepth)):
+                g_t = self._dec_block_bwd(lists, i, blk[i], s, tok, B, g_t, tok_dgrads, embed_in=enc["latent"] if i == 0 else None)
+            self._exemplar_tokens_bwd(lists.bwd_tok, p, B, S, tok, s, tok_dgrads)
+            self._flush_reductions(p)
+            for ops_ in (lists.bwd_head, lists.bwd_rest, lists.bwd_tok):
+                self._auto_warm(ops_)
+        self._acc = 0
+        return p
+
+    def _encoder_fwd(self, ops, p, B):
+        """Patch embedding, the ViT blocks and the final norm -> {latent, x, patches} (x / patches: read by _encoder_pipe_variant)."""
+        L, T, f32, code = self.L, self.tdt, torch.float32, self.code
+        N, D, H, rows = self.N, self.D, self.H, B * self.N
+        A = lambda k, shape, dt: self._alloc(p, k, shape, dt)
         img = A("img", (B, 3, self.img, self.img), f32)
         # (a patch row that is not a whole number of 16-byte chunks in 16-bit storage -- patch 14: K = 588 -- keeps the patch matrix and
         # its product in fp32: mae_vit_huge_patch14's forward-only configuration)
@@ -976,31 +1035,40 @@ class Engine:
             self._linear(ops, hid, b + ".mlp.fc2.weight", x, rows, D, 4 * D, resid=x, **({} if i + 1 == self.depth else prod))
         self._layernorm(ops, x, "norm", latent, rows, D)
         p.enc_ops = len(ops)
-        # Pipelined-encoder variant (trainer.FinetuneStep(pipeline_encoder=True); inference.density_maps_stream): the SAME launches reading the next batch's images from a
-        # buffer shared by all plans and leaving its latent in another one, so that they can run on their own lane beside this batch's
-        # decoder side (which keeps reading this plan's `latent`, down to decoder_embed's weight gradient at the end of the backward).
-        # 16-bit modes only: the fp32 parity mode's unfused attention goes through scratch it shares with the decoder's.
-        p.enc_pipe = None
-        if code != F32 and self._fused_attention(D // H):
-            pimg = self._shared("pipe_img", B * 3 * self.img * self.img)
-            plat = self._shared("pipe_latent", rows * D, T)
-            head, tail = [], []
-            self._op(head, L.countr_im2patch, pimg.data_ptr(), patches.data_ptr(), B, self.img, self.img, self.patch, code)
-            self._layernorm(tail, x, "norm", plat, rows, D)
-            assert ops[0][0] is L.countr_im2patch and ops[-1][0] is L.countr_layernorm_fwd
-            p.enc_pipe = head + ops[1:-1] + tail
-            p.pipe_img, p.pipe_latent, p.pipe_latent_bytes = pimg, plat, rows * D * (2 if T in HALF_DTYPES else 4)
+        return {"latent": latent, "x": x, "patches": patches}
 
-        # ---------------- decoder: models_mae_cross.py:150-199
+    def _encoder_pipe_variant(self, p, B, enc):
+        """Pipelined-encoder variant (trainer.FinetuneStep(pipeline_encoder=True); inference.density_maps_stream): the SAME launches
+        reading the next batch's images from a buffer shared by all plans and leaving its latent in another one, so that they can run on
+        their own lane beside this batch's decoder side (which keeps reading this plan's `latent`, down to decoder_embed's weight
+        gradient at the end of the backward).  16-bit modes only: the fp32 parity mode's unfused attention goes through scratch it shares
+        with the decoder's."""
+        L, T, D, rows = self.L, self.tdt, self.D, B * self.N
+        if self.code == F32 or not self._fused_attention(D // self.H):
+            return
+        ops = p.fwd[:p.enc_ops]
+        pimg = self._shared("pipe_img", B * 3 * self.img * self.img)
+        plat = self._shared("pipe_latent", rows * D, T)
+        head, tail = [], []
+        self._op(head, L.countr_im2patch, pimg.data_ptr(), enc["patches"].data_ptr(), B, self.img, self.img, self.patch, self.code)
+        self._layernorm(tail, enc["x"], "norm", plat, rows, D)
+        assert ops[0][0] is L.countr_im2patch and ops[-1][0] is L.countr_layernorm_fwd
+        p.enc_pipe = head + ops[1:-1] + tail
+        p.pipe_img, p.pipe_latent, p.pipe_latent_bytes = pimg, plat, rows * D * (2 if T in HALF_DTYPES else 4)
+
+    def _exemplar_tokens_fwd(self, ops, p, B, S, train):
+        """The exemplar tokens ytok: the shot token (S == 0) or the exemplar CNN's output -> {ytok, tok_rows, Sy, ex0} and, with
+        exemplars, the CNN's buffers that its backward reads."""
+        L, T, f32, code, Dd = self.L, self.tdt, torch.float32, self.code, self.Dd
+        A = lambda k, shape, dt: self._alloc(p, k, shape, dt)
         Sy = max(S, 1)
-        xs = [A("dx0", (rows, Dd), f32)]
-        self._linear(ops, latent, "decoder_embed.weight", xs[0], rows, Dd, D, resid=self._pp("decoder_pos_embed"), res_mod=N)
         # (rows padded to a multiple of 64 with zeros, never written: as a weight gradient's operand the token matrix is then whole k-tiles,
         # so attn.wk / attn.wv join the block's grouped weight-gradient launch instead of four 16-workgroup launches of their own)
         tok_rows = -(-(B * Sy) // 64) * 64
         ytok = A("ytok", (tok_rows, Dd), T)
         if not self._sizing:
             ytok.zero_()
+        tok = {"ytok": ytok, "tok_rows": tok_rows, "Sy": Sy, "ex0": len(ops)}
         if S == 0:
             # y = shot_token broadcast over the batch (models_mae_cross.py:176): ONE row gather with an all-zero index (it was one cast
             # launch per batch element: 32 tiny launches in front of every B = 32 inference forward)
@@ -1008,102 +1076,112 @@ class Engine:
             if not self._sizing:
                 zidx.zero_()
             self._op(ops, L.countr_gather_rows, self._pp("shot_token"), zidx.data_ptr(), ytok.data_ptr(), None, None, 0, B, Dd, F32, code)
-        else:
-            ex0 = len(ops)
-            BS = B * S
-            boxes = A("boxes", (BS, 3, 64, 64), f32)
-            chans = [64, 128, 256, Dd]
-            sizes = [64, 32, 16, 8]
-            # bf16 engine: the exemplar CNN's convolutions write fp32 (c*) and the InstanceNorm stage turns them into bf16 pooled
-            # activations and -- training plans -- the bf16 NORMALISED maps (ch*) its backward reads.  A bf16 conv output is rounded at
-            # 2^-9 of its value; on channels whose mean is several sigma that moves pixels across the ReLU boundary of the normalised
-            # map, and the InstanceNorm backward turned it into cos 0.975 per layer / 0.96 for the CNN's weight gradients against fp32
-            # (tools/diag_exemplar_bf16.py)
-            xh = bool(code == BF16)
-            p.in_xhat = xh
-            c = [A("c%d" % (i + 1), (BS, sizes[i], sizes[i], chans[i]), f32 if xh else T) for i in range(4)]
-            ch = [A("ch%d" % (i + 1), (BS, sizes[i], sizes[i], chans[i]), T) for i in range(4)] if (xh and train) else None
-            p.in_maps = ch if ch is not None else c
-            pl = [A("p%d" % (i + 1), (BS, sizes[i] // 2, sizes[i] // 2, chans[i]), T) for i in range(3)]
-            stats = [A("instats%d" % (i + 1), (BS, chans[i], 2), f32) for i in range(4)]
-            self._op(ops, L.countr_conv3x3_c3_fwd, boxes.data_ptr(), self._pp("decoder_proj1.0.weight"), self._pp("decoder_proj1.0.bias"),
-                     c[0].data_ptr(), BS, 64, 64, F32 if xh else code)
-            in_ws = self._shared("in_ws", L.countr_instnorm_workspace_floats(BS, Dd))
-            self._op(ops, L.countr_instnorm_relu_pool_fwd, c[0].data_ptr(), pl[0].data_ptr(), stats[0].data_ptr(), BS, 64, 64, 64, 0, 1e-5,
-                     code, in_ws.data_ptr(), ch[0].data_ptr() if ch is not None else None, int(xh))
-            for i in (1, 2, 3):
-                wn = "decoder_proj%d.0.weight" % (i + 1)
-                self._conv_fwd(ops, pl[i - 1], self.Wf[wn], self._pp(wn[:-6] + "bias"), c[i], BS, sizes[i], sizes[i], chans[i - 1], chans[i])
-                last = i == 3
-                self._op(ops, L.countr_instnorm_relu_pool_fwd, c[i].data_ptr(), (ytok if last else pl[i]).data_ptr(), stats[i].data_ptr(),
-                         BS, sizes[i], sizes[i], chans[i], int(last), 1e-5, code, in_ws.data_ptr(), ch[i].data_ptr() if ch is not None else None, int(xh))
-        # the cross-attention keys / values depend on the exemplar tokens only: all blocks' wk / wv projections (tiny GEMMs, 4 tiles each)
-        # follow the tokens directly -- with exemplars that is inside the side lane that runs beside the encoder
-        # wk and wv of a block lie side by side in the parameter buffer (weights and biases alike: ParamLayout): ONE product per block
-        # writes k | v as the two column halves of a [B * S, 2 Dd] buffer (countr_xattn_*'s ldkv) -- two launches less on the exemplar lane,
-        # which heads the decoder's critical path in the pipelined forms
-        kv, lay = [], self.layout
+            return tok
+        BS = B * S
+        boxes = A("boxes", (BS, 3, 64, 64), f32)
+        chans = [64, 128, 256, Dd]
+        sizes = [64, 32, 16, 8]
+        # bf16 engine: the exemplar CNN's convolutions write fp32 (c*) and the InstanceNorm stage turns them into bf16 pooled
+        # activations and -- training plans -- the bf16 NORMALISED maps (ch*) its backward reads.  A bf16 conv output is rounded at
+        # 2^-9 of its value; on channels whose mean is several sigma that moves pixels across the ReLU boundary of the normalised
+        # map, and the InstanceNorm backward turned it into cos 0.975 per layer / 0.96 for the CNN's weight gradients against fp32
+        # (tools/diag_exemplar_bf16.py)
+        xh = bool(code == BF16)
+        c = [A("c%d" % (i + 1), (BS, sizes[i], sizes[i], chans[i]), f32 if xh else T) for i in range(4)]
+        ch = [A("ch%d" % (i + 1), (BS, sizes[i], sizes[i], chans[i]), T) for i in range(4)] if (xh and train) else None
+        pl = [A("p%d" % (i + 1), (BS, sizes[i] // 2, sizes[i] // 2, chans[i]), T) for i in range(3)]
+        stats = [A("instats%d" % (i + 1), (BS, chans[i], 2), f32) for i in range(4)]
+        self._op(ops, L.countr_conv3x3_c3_fwd, boxes.data_ptr(), self._pp("decoder_proj1.0.weight"), self._pp("decoder_proj1.0.bias"),
+                 c[0].data_ptr(), BS, 64, 64, F32 if xh else code)
+        in_ws = self._shared("in_ws", L.countr_instnorm_workspace_floats(BS, Dd))
+        self._op(ops, L.countr_instnorm_relu_pool_fwd, c[0].data_ptr(), pl[0].data_ptr(), stats[0].data_ptr(), BS, 64, 64, 64, 0, 1e-5,
+                 code, in_ws.data_ptr(), ch[0].data_ptr() if ch is not None else None, int(xh))
+        for i in (1, 2, 3):
+            wn = "decoder_proj%d.0.weight" % (i + 1)
+            self._conv_fwd(ops, pl[i - 1], self.Wf[wn], self._pp(wn[:-6] + "bias"), c[i], BS, sizes[i], sizes[i], chans[i - 1], chans[i])
+            last = i == 3
+            self._op(ops, L.countr_instnorm_relu_pool_fwd, c[i].data_ptr(), (ytok if last else pl[i]).data_ptr(), stats[i].data_ptr(),
+                     BS, sizes[i], sizes[i], chans[i], int(last), 1e-5, code, in_ws.data_ptr(), ch[i].data_ptr() if ch is not None else None, int(xh))
+        tok.update(boxes=boxes, chans=chans, sizes=sizes, in_xhat=xh, in_maps=ch if ch is not None else c, pl=pl, stats=stats, in_ws=in_ws)
+        return tok
+
+    def _kv_fwd(self, ops, p, B, tok):
+        """-> per decoder block (k, v, row pitch of the two).
+        The cross-attention keys / values depend on the exemplar tokens only: all blocks' wk / wv projections (tiny GEMMs, 4 tiles each)
+        follow the tokens directly -- with exemplars that is inside the side lane that runs beside the encoder.
+        wk and wv of a block lie side by side in the parameter buffer (weights and biases alike: ParamLayout): ONE product per block
+        writes k | v as the two column halves of a [B * S, 2 Dd] buffer (countr_xattn_*'s ldkv) -- two launches less on the exemplar lane,
+        which heads the decoder's critical path in the pipelined forms."""
+        T, Dd, lay, n = self.tdt, self.Dd, self.layout, B * tok["Sy"]
+        ytok = tok["ytok"]
+        kv = []
         for i in range(self.ddepth):
             b = "decoder_blocks.%d" % i
             wk, wv = b + ".attn.wk.weight", b + ".attn.wv.weight"
             if lay.off[wv] == lay.off[wk] + Dd * Dd and lay.off[wv[:-6] + "bias"] == lay.off[wk[:-6] + "bias"] + Dd:
-                kvb = A(b + ".kv", (B * Sy, 2 * Dd), T)
-                self._linear(ops, ytok, wk, kvb, B * Sy, 2 * Dd, Dd)
+                kvb = self._alloc(p, b + ".kv", (n, 2 * Dd), T)
+                self._linear(ops, ytok, wk, kvb, n, 2 * Dd, Dd)
                 kv.append((_Cols(kvb, 0), _Cols(kvb, Dd), 2 * Dd))
             else:
-                k_, v_ = A(b + ".k", (B * Sy, Dd), T), A(b + ".v", (B * Sy, Dd), T)
-                self._linear(ops, ytok, wk, k_, B * Sy, Dd, Dd)
-                self._linear(ops, ytok, wv, v_, B * Sy, Dd, Dd)
+                k_, v_ = self._alloc(p, b + ".k", (n, Dd), T), self._alloc(p, b + ".v", (n, Dd), T)
+                self._linear(ops, ytok, wk, k_, n, Dd, Dd)
+                self._linear(ops, ytok, wv, v_, n, Dd, Dd)
                 kv.append((k_, v_, Dd))
-        if S > 0:
-            p.ex_range = (ex0, len(ops))
-        blk = []
-        for i in range(self.ddepth):
-            b = "decoder_blocks.%d" % i
-            d = {}
-            xin = xs[-1]
-            d["n0"] = A(b + ".n0", (rows, Dd), T)
-            d["m0"], d["r0"] = A(b + ".m0", (rows,), f32), A(b + ".r0", (rows,), f32)
-            d["qkv"] = A(b + ".qkv", (rows + pad, 3 * Dd), T)
-            if pad and not self._sizing:
-                d["qkv"][rows:].zero_()
-            fused = self._fused_attention(Dd // Hd)
-            d["probs"] = A(b + ".probs", (B * Hd * N * N,), T) if (train and not fused) else None
-            d["lse"] = A(b + ".lse", (B * Hd * N,), f32) if (train and fused) else None
-            d["att"] = A(b + ".att", (rows, Dd), T)
-            self._layernorm(ops, xin, b + ".norm0", d["n0"], rows, Dd, d["m0"], d["r0"])
-            self._linear(ops, d["n0"], b + ".selfattn.qkv.weight", d["qkv"], rows, 3 * Dd, Dd)
-            self._attention_fwd(ops, p, d["qkv"], d["att"], B, Hd, Dd, probs=d["probs"], lse=d["lse"])
-            x1 = A(b + ".x1", (rows, Dd), f32)
-            self._linear(ops, d["att"], b + ".selfattn.proj.weight", x1, rows, Dd, Dd, resid=xin)
-            d["n1"] = A(b + ".n1", (rows, Dd), T)
-            d["m1"], d["r1"] = A(b + ".m1", (rows,), f32), A(b + ".r1", (rows,), f32)
-            d["q"] = A(b + ".q", (rows, Dd), T)
-            d["k"], d["v"], d["ldkv"] = kv[i]
-            d["xo"] = A(b + ".xo", (rows, Dd), T)
-            self._layernorm(ops, x1, b + ".norm1", d["n1"], rows, Dd, d["m1"], d["r1"])
-            self._linear(ops, d["n1"], b + ".attn.wq.weight", d["q"], rows, Dd, Dd)
-            if i == 0:
-                p.first_xattn = len(ops)      # the first launch that reads the exemplar tokens' keys / values (decoder_ops_with_exemplar_lane)
-            self._op(ops, L.countr_xattn_fwd, d["q"].data_ptr(), d["k"].data_ptr(), d["v"].data_ptr(), d["xo"].data_ptr(), B, N, Sy, Dd,
-                     Hd, d["ldkv"], (Dd // Hd) ** -0.5, code)
-            x2 = A(b + ".x2", (rows, Dd), f32)
-            self._linear(ops, d["xo"], b + ".attn.proj.weight", x2, rows, Dd, Dd, resid=x1)
-            d["n2"] = A(b + ".n2", (rows, Dd), T)
-            d["m2"], d["r2"] = A(b + ".m2", (rows,), f32), A(b + ".r2", (rows,), f32)
-            d["hpre"] = A(b + ".hpre", (rows, 4 * Dd), T)
-            d["hact"] = A(b + ".hact", (rows, 4 * Dd), T)
-            self._layernorm(ops, x2, b + ".norm2", d["n2"], rows, Dd, d["m2"], d["r2"])
-            self._linear(ops, d["n2"], b + ".mlp.fc1.weight", d["hact"], rows, 4 * Dd, Dd, act=ACT_GELU, pre=d["hpre"])
-            x3 = A(b + ".x3", (rows, Dd), f32)
-            self._linear(ops, d["hact"], b + ".mlp.fc2.weight", x3, rows, Dd, 4 * Dd, resid=x2)
-            d["xin"], d["x1"], d["x2"] = xin, x1, x2
-            xs.append(x3)
-            blk.append(d)
+        return kv
+
+    # ---- CrossAttentionBlock (models_crossvit.py:130-156): x1 = xin + selfattn(norm0 xin); x2 = x1 + xattn(norm1 x1, y); x3 = x2 + mlp(norm2 x2)
+    def _dec_block_fwd(self, ops, p, i, xin, kv, B, Sy, train):
+        L, T, f32 = self.L, self.tdt, torch.float32
+        N, Dd, Hd, rows = self.N, self.Dd, self.Hd, B * self.N
+        b = "decoder_blocks.%d" % i
+        A = lambda k, shape, dt: self._alloc(p, b + k, shape, dt)
+        pad = self.Np - N
+        d = {"xin": xin}
+        d["n0"] = A(".n0", (rows, Dd), T)
+        d["m0"], d["r0"] = A(".m0", (rows,), f32), A(".r0", (rows,), f32)
+        d["qkv"] = A(".qkv", (rows + pad, 3 * Dd), T)
+        if pad and not self._sizing:
+            d["qkv"][rows:].zero_()
+        fused = self._fused_attention(Dd // Hd)
+        d["probs"] = A(".probs", (B * Hd * N * N,), T) if (train and not fused) else None
+        d["lse"] = A(".lse", (B * Hd * N,), f32) if (train and fused) else None
+        d["att"] = A(".att", (rows, Dd), T)
+        self._layernorm(ops, xin, b + ".norm0", d["n0"], rows, Dd, d["m0"], d["r0"])
+        self._linear(ops, d["n0"], b + ".selfattn.qkv.weight", d["qkv"], rows, 3 * Dd, Dd)
+        self._attention_fwd(ops, p, d["qkv"], d["att"], B, Hd, Dd, probs=d["probs"], lse=d["lse"])
+        d["x1"] = A(".x1", (rows, Dd), f32)
+        self._linear(ops, d["att"], b + ".selfattn.proj.weight", d["x1"], rows, Dd, Dd, resid=xin)
+        d["n1"] = A(".n1", (rows, Dd), T)
+        d["m1"], d["r1"] = A(".m1", (rows,), f32), A(".r1", (rows,), f32)
+        d["q"] = A(".q", (rows, Dd), T)
+        d["k"], d["v"], d["ldkv"] = kv
+        d["xo"] = A(".xo", (rows, Dd), T)
+        self._layernorm(ops, d["x1"], b + ".norm1", d["n1"], rows, Dd, d["m1"], d["r1"])
+        self._linear(ops, d["n1"], b + ".attn.wq.weight", d["q"], rows, Dd, Dd)
+        if i == 0:
+            p.first_xattn = len(ops)      # the first launch that reads the exemplar tokens' keys / values (decoder_ops_with_exemplar_lane)
+        self._op(ops, L.countr_xattn_fwd, d["q"].data_ptr(), d["k"].data_ptr(), d["v"].data_ptr(), d["xo"].data_ptr(), B, N, Sy, Dd,
+                 Hd, d["ldkv"], (Dd // Hd) ** -0.5, self.code)
+        d["x2"] = A(".x2", (rows, Dd), f32)
+        self._linear(ops, d["xo"], b + ".attn.proj.weight", d["x2"], rows, Dd, Dd, resid=d["x1"])
+        d["n2"] = A(".n2", (rows, Dd), T)
+        d["m2"], d["r2"] = A(".m2", (rows,), f32), A(".r2", (rows,), f32)
+        d["hpre"] = A(".hpre", (rows, 4 * Dd), T)
+        d["hact"] = A(".hact", (rows, 4 * Dd), T)
+        self._layernorm(ops, d["x2"], b + ".norm2", d["n2"], rows, Dd, d["m2"], d["r2"])
+        self._linear(ops, d["n2"], b + ".mlp.fc1.weight", d["hact"], rows, 4 * Dd, Dd, act=ACT_GELU, pre=d["hpre"])
+        d["x3"] = A(".x3", (rows, Dd), f32)
+        self._linear(ops, d["hact"], b + ".mlp.fc2.weight", d["x3"], rows, Dd, 4 * Dd, resid=d["x2"])
+        return d
+
+    def _head_fwd(self, ops, p, B, x):
+        """decoder_norm and the density head on NHWC maps (tokens [B, N, Dd] already are [B, grid, grid, Dd]) -> what the head's
+        backward reads."""
+        L, T, f32, code, Dd, rows = self.L, self.tdt, torch.float32, self.code, self.Dd, B * self.N
+        A = lambda k, shape, dt: self._alloc(p, k, shape, dt)
         dn = A("dn", (rows, Dd), T)
         mN, rN = A("mN", (rows,), f32), A("rN", (rows,), f32)
-        self._layernorm(ops, xs[-1], "decoder_norm", dn, rows, Dd, mN, rN)
-        # density head on NHWC maps; tokens [B, N, Dd] already are [B, grid, grid, Dd]
+        self._layernorm(ops, x, "decoder_norm", dn, rows, Dd, mN, rN)
         g = self.grid
         hs = [g, 2 * g, 4 * g, 8 * g]
         cin = [Dd, 256, 256, 256]
@@ -1139,162 +1217,168 @@ class Engine:
                 self._op(ops, L.countr_upsample2x_fwd, o1.data_ptr(), out.data_ptr(), B, hs[3], hs[3], 1, F32)
             hc.append(ci)
             hstats.append(si)
-        ex = getattr(p, "ex_range", None)
+        return {"x": x, "dn": dn, "mN": mN, "rN": rN, "hs": hs, "cin": cin, "hin": hin, "hc": hc, "hstats": hstats}
+
+    def _finish_forward(self, p):
+        """The full forward as it is run (p.fwd_par) and the warm-up hints of p.fwd."""
+        ex = p.ex_range
         if ex is None:
             p.fwd_par = p.fwd
-        else:     # [fork | lane 1: exemplar CNN | lane 0: encoder + decoder_embed | join | decoder blocks + head]
-            mark = lambda *a: (None, a, None)
-            p.fwd_par = ([mark("fork"), mark("lane", 1)] + p.fwd[ex[0]:ex[1]] + [mark("lane", 0)] + p.fwd[:ex[0]] + [mark("join")]
-                         + p.fwd[ex[1]:])
-        if ex is None:
             self._auto_warm(p.fwd)
-        else:     # per lane, in the order fwd_par executes: the encoder's last launch warms the first decoder-block panel (not the exemplar
-            self._auto_warm(p.fwd[:ex[0]] + p.fwd[ex[1]:])      # CNN's, which ran beside it), the exemplar lane keeps its hints to itself
+        else:     # [fork | lane 1: exemplar CNN | lane 0: encoder + decoder_embed | join | decoder blocks + head]
+            p.fwd_par = side_by_side(p.fwd[ex[0]:ex[1]], p.fwd[:ex[0]]) + p.fwd[ex[1]:]
+            # per lane, in the order fwd_par executes: the encoder's last launch warms the first decoder-block panel (not the exemplar
+            # CNN's, which ran beside it), the exemplar lane keeps its hints to itself
+            self._auto_warm(p.fwd[:ex[0]] + p.fwd[ex[1]:])
             self._auto_warm(p.fwd[ex[0]:ex[1]])
-        if not train:
-            return p
 
-        p.acc = Plan()
-        for acc, lists in ((0, p), (1, p.acc)):
-            self._acc = acc
-            # =========================== backward (decoder side only) ===========================
-            ops = lists.bwd_head
-            dout = A("dout", (B, 2 * hs[3], 2 * hs[3]), f32)
-            d1 = A("d1", (B, hs[3] * hs[3]), f32)
-            self._op(ops, L.countr_upsample2x_bwd, dout.data_ptr(), d1.data_ptr(), B, hs[3], hs[3], 1, F32)
-            # gradient scratch for maps: dpre (grad of conv output), dup (grad of conv input)
-            dpre = self._shared("dpre", B * hs[3] * hs[3] * 256, T)
-            dup = self._shared("dup", B * hs[3] * hs[3] * 256, T)
-            dact = self._shared("dact", B * hs[2] * hs[2] * 256, T)
-            ddn = A("ddn", (rows, Dd), T)
-            for i in (3, 2, 1, 0):
-                hn = "decode_head%d" % i
-                HW = hs[i] * hs[i]
-                # GroupNorm parameter gradients: the per-block partials {dbeta, dgamma, dw1}[256] stay in this layer's own workspace and
-                # are summed by the table launch that finishes the layer's conv wgrad anyway (they used to be 2-3 colsum launches of 16
-                # workgroups each: ~80 us per step of latency-bound finishers)
-                gws = self._shared("gnbw%d" % i, B * 64 * 3 * 256 + 64 + 16 * B + B * 3 * 256)
-                self._claim(gws.data_ptr())
-                if i == 3:
-                    self._op(ops, L.countr_groupnorm_relu_bwd, hc[i].data_ptr(), None, d1.data_ptr(), self._pp(hn + ".3.weight"),
-                             hstats[i].data_ptr(), self._pp(hn + ".1.weight"), self._pp(hn + ".1.bias"), dpre.data_ptr(),
-                             None, None, None, self._gp(hn + ".3.bias"), gws.data_ptr(), B, HW, 256, 8, code, self._acc)
-                else:
-                    self._op(ops, L.countr_upsample2x_bwd, dup.data_ptr(), dact.data_ptr(), B, hs[i], hs[i], 256, code)
-                    self._op(ops, L.countr_groupnorm_relu_bwd, hc[i].data_ptr(), dact.data_ptr(), None, None, hstats[i].data_ptr(),
-                             self._pp(hn + ".1.weight"), self._pp(hn + ".1.bias"), dpre.data_ptr(), None, None, None, None,
-                             gws.data_ptr(), B, HW, 256, 8, code, self._acc)
-                # the backward's finalize pass leaves per-IMAGE sums behind the split partials: B rows to add, not B * nsplit
-                img = gws.data_ptr() + 4 * L.countr_groupnorm_bwd_image_sums_offset(B, HW)
-                planes = [(0, hn + ".1.bias"), (1, hn + ".1.weight")] + ([(2, hn + ".3.weight")] if i == 3 else [])
-                for plane, pname in planes:
-                    self._reduce_later(ops, gws.data_ptr(), img + plane * 256 * 4, self._gp(pname), B, 3 * 256, 256)
-                self._conv_wgrad(ops, dpre, hin[i], hn + ".0.weight", B, hs[i], hs[i], cin[i], 256, bias_name=hn + ".0.bias")
-                # dgrad == forward conv of dpre with the dgrad-form weights (Cin_gemm = 256 output channels)
-                tgt = dup if i > 0 else ddn
-                self._gemm(ops, code, OP_IM2ROW, OP_ROW, A=dpre.data_ptr(), B=self.Wd[hn + ".0.weight"].data_ptr(), C=tgt.data_ptr(),
-                           ldb=9 * 256, ldc=cin[i], M=B * HW, N=cin[i], K=9 * 256, H=hs[i], W=hs[i], Cin=256,
-                           out_bf16=int(code == BF16))
-            gx = A("gx", (rows, Dd), f32)
-            gxT = A("gxT", (rows, Dd), T) if code == BF16 else None
-            # grouped weight gradients (bf16): the six Linear weight gradients of a block (and decoder_embed's with the last block's) run
-            # as ONE launch behind the block's last LayerNorm backward -- so the operand view of the residual gradient cycles through
-            # four buffers (the three versions the deferred launch still reads stay intact while the next one is written)
-            grouped = code == BF16
-            gxT_alt = [gxT] + [A("gxT%d" % k, (rows, Dd), T) for k in (2, 3, 4)] if grouped else [gxT] * 4
-            gsel = [0]
+    def _bwd_scratch(self, p, B, tok):
+        """Gradient buffers of the decoder-side backward (the same ones for the overwriting and the accumulating lists)."""
+        T, f32, code, Dd, rows = self.tdt, torch.float32, self.code, self.Dd, B * self.N
+        A = lambda k, shape, dt: self._alloc(p, k, shape, dt)
+        n, tok_rows = B * tok["Sy"], tok["tok_rows"]
+        hs3 = 8 * self.grid
+        s = {"dout": A("dout", (B, 2 * hs3, 2 * hs3), f32), "d1": A("d1", (B, hs3 * hs3), f32), "ddn": A("ddn", (rows, Dd), T),
+             "gx": A("gx", (rows, Dd), f32), "gxT": A("gxT", (rows, Dd), T) if code == BF16 else None}
+        # grouped weight gradients (bf16): the six Linear weight gradients of a block (and decoder_embed's with the last block's) run
+        # as ONE launch behind the block's last LayerNorm backward -- so the operand view of the residual gradient cycles through
+        # four buffers (the three versions the deferred launch still reads stay intact while the next one is written)
+        ring = [A("gxT%d" % k, (rows, Dd), T) for k in (2, 3, 4)] + [s["gxT"]] if code == BF16 else [s["gxT"]]
+        s["next_gxT"] = itertools.cycle(ring)
+        s["dh"] = A("dh", (rows, 4 * Dd), T)
+        s["dn_t"] = A("dn_t", (rows, Dd), T)      # grad wrt a LayerNorm output
+        s["dproj_in"] = A("dproj_in", (rows, Dd), T)
+        s["dqkv"] = A("dqkv", (rows, 3 * Dd), T)
+        s["dq"] = A("dq", (rows, Dd), T)
+        # one dK / dV per block: their input gradients (-> dy_tok, read only by the exemplar-token backward) are emitted at
+        # the head of bwd_tok, off the decoder's own dependency chain
+        s["dk"] = [A("dk%d" % i, (n, Dd), f32) for i in range(self.ddepth)]
+        s["dv"] = [A("dv%d" % i, (n, Dd), f32) for i in range(self.ddepth)]
+        s["dkT"] = [A("dkT%d" % i, (tok_rows, Dd), T) if code == BF16 else None for i in range(self.ddepth)]     # (rows padded with zeros, as ytok)
+        s["dvT"] = [A("dvT%d" % i, (tok_rows, Dd), T) if code == BF16 else None for i in range(self.ddepth)]
+        if not self._sizing and code == BF16:
+            for t_ in s["dkT"] + s["dvT"]:
+                t_.zero_()
+        s["dy_tok"] = A("dy_tok", (n, Dd), f32)
+        return s
 
-            def next_gxT():
-                gsel[0] = (gsel[0] + 1) % 4
-                return gxT_alt[gsel[0]]
-            g_t = self._layernorm_bwd(ops, ddn, xs[-1], "decoder_norm", mN, rN, gx, rows, Dd, accumulate=False, dx_t=gxT)
-
-            ops = lists.bwd_rest
-            dh = A("dh", (rows, 4 * Dd), T)
-            dn_t = A("dn_t", (rows, Dd), T)      # grad wrt a LayerNorm output
-            dproj_in = A("dproj_in", (rows, Dd), T)
-            dqkv = A("dqkv", (rows, 3 * Dd), T)
-            dq = A("dq", (rows, Dd), T)
-            # one dK / dV per block: their input gradients (-> dy_tok, read only by the exemplar-token backward) are emitted at
-            # the head of bwd_tok, off the decoder's own dependency chain
-            dk_b = [A("dk%d" % i, (B * Sy, Dd), f32) for i in range(self.ddepth)]
-            dv_b = [A("dv%d" % i, (B * Sy, Dd), f32) for i in range(self.ddepth)]
-            dkT_b = [A("dkT%d" % i, (tok_rows, Dd), T) if code == BF16 else None for i in range(self.ddepth)]     # (rows padded with zeros, as ytok)
-            dvT_b = [A("dvT%d" % i, (tok_rows, Dd), T) if code == BF16 else None for i in range(self.ddepth)]
-            if not self._sizing and code == BF16:
-                for t_ in dkT_b + dvT_b:
-                    t_.zero_()
-            dy_tok = A("dy_tok", (B * Sy, Dd), f32)
-            xws = self._shared("xattn", L.countr_xattn_bwd_workspace_floats(B, N, Sy, Dd))
-            tok_dgrads = []
-            for i in reversed(range(self.ddepth)):
-                b = "decoder_blocks.%d" % i
-                d = blk[i]
-                # ---- mlp: x3 = x2 + fc2(gelu(fc1(LN2(x2))))  (g_t = bf16/fp32 operand view of gx, emitted by the LN backward)
-                grp = [] if grouped else None
-                self._linear_bwd(ops, g_t, d["hact"], b + ".mlp.fc2.weight", rows, Dd, 4 * Dd, dx=dh, gelu_pre=d["hpre"], group=grp)
-                self._linear_bwd(ops, dh, d["n2"], b + ".mlp.fc1.weight", rows, 4 * Dd, Dd, dx=dn_t, group=grp)
-                g_t = self._layernorm_bwd(ops, dn_t, d["x2"], b + ".norm2", d["m2"], d["r2"], gx, rows, Dd, accumulate=True, dx_t=next_gxT())
-                # ---- cross attention: x2 = x1 + proj(xattn(wq(LN1(x1)), wk(y), wv(y)))
-                self._linear_bwd(ops, g_t, d["xo"], b + ".attn.proj.weight", rows, Dd, Dd, dx=dproj_in, group=grp)
-                dk, dv, dkT, dvT = dk_b[i], dv_b[i], dkT_b[i], dvT_b[i]
-                self._op(ops, L.countr_xattn_bwd, d["q"].data_ptr(), d["k"].data_ptr(), d["v"].data_ptr(), dproj_in.data_ptr(), dq.data_ptr(),
-                         dk.data_ptr(), dv.data_ptr(), xws.data_ptr(), B, N, Sy, Dd, Hd, d["ldkv"], (Dd // Hd) ** -0.5, code,
-                         dkT.data_ptr() if dkT is not None else None, dvT.data_ptr() if dvT is not None else None)
-                if i == 0:
-                    ops.append((None, ("tokready",), None))   # every block's dK / dV is final: the exemplar-token backward may start (run_backward_rest_and_tok)
-                self._linear_bwd(ops, dq, d["n1"], b + ".attn.wq.weight", rows, Dd, Dd, dx=dn_t, group=grp)
-                g_t = self._layernorm_bwd(ops, dn_t, d["x1"], b + ".norm1", d["m1"], d["r1"], gx, rows, Dd, accumulate=True, dx_t=next_gxT())
-                dk_t, dv_t = (dk, dv) if dkT is None else (dkT, dvT)    # bf16 copies come out of the cross-attention backward
-                for nm, g_kv in (("wk", dk_t), ("wv", dv_t)):
-                    if grouped:     # over the zero-padded rows: whole k-tiles, same sums
-                        grp.append((g_kv, ytok, b + ".attn.%s.weight" % nm, tok_rows, Dd, Dd, b + ".attn.%s.bias" % nm))
-                    else:
-                        self._linear_wgrad(ops, g_kv, ytok, b + ".attn.%s.weight" % nm, B * Sy, Dd, Dd, bias_name=b + ".attn.%s.bias" % nm)
-                    tok_dgrads.append((g_kv, b + ".attn.%s.weight" % nm))
-                # ---- self attention: x1 = xin + proj(attn(qkv(LN0(xin))))
-                self._linear_bwd(ops, g_t, d["att"], b + ".selfattn.proj.weight", rows, Dd, Dd, dx=dproj_in, group=grp)
-                if d["lse"] is not None:
-                    dlt = self._shared("attn_delta", B * Hd * N)
-                    self._op(ops, L.countr_attn_bwd, d["qkv"].data_ptr(), d["att"].data_ptr(), dproj_in.data_ptr(), d["lse"].data_ptr(),
-                             dlt.data_ptr(), dqkv.data_ptr(), B, N, Hd, Dd // Hd, (Dd // Hd) ** -0.5)
-                else:
-                    self._attention_bwd(ops, d["qkv"], d["probs"], dproj_in, dqkv, B, Hd, Dd)
-                self._linear_bwd(ops, dqkv, d["n0"], b + ".selfattn.qkv.weight", rows, 3 * Dd, Dd, dx=dn_t, group=grp)
-                g_t = self._layernorm_bwd(ops, dn_t, d["xin"], b + ".norm0", d["m0"], d["r0"], gx, rows, Dd, accumulate=True, dx_t=next_gxT())
-                if i == 0:   # ---- decoder_embed (no dgrad: the encoder is frozen)
-                    self._linear_bwd(ops, g_t, latent, "decoder_embed.weight", rows, Dd, D, group=grp)
-                if grouped:      # fc2, fc1, attn.proj, attn.wq, selfattn.proj, selfattn.qkv (, decoder_embed)
-                    self._linear_wgrad_group(ops, grp)
-            # ---- exemplar tokens: dy_tok = sum over blocks of dK Wk + dV Wv
-            ops = lists.bwd_tok
-            for j, (g_kv, wn) in enumerate(tok_dgrads):
-                self._linear_dgrad(ops, g_kv, wn, dy_tok, B * Sy, Dd, Dd, resid=(None if j == 0 else dy_tok), out_bf16=False)
-            if S == 0:
-                ws = self._shared("colsum", 256 * 4096)
-                self._op(ops, L.countr_colsum, dy_tok.data_ptr(), self._gp("shot_token"), ws.data_ptr(), B, Dd, F32, self._acc)
+    def _head_bwd(self, ops, p, B, head, s):
+        """Density head and decoder_norm (bucket 0).  Returns the GEMM-operand view of the residual gradient s["gx"]."""
+        L, T, code, Dd, rows = self.L, self.tdt, self.code, self.Dd, B * self.N
+        hs, cin, hin, hc, hstats = head["hs"], head["cin"], head["hin"], head["hc"], head["hstats"]
+        d1, ddn = s["d1"], s["ddn"]
+        self._op(ops, L.countr_upsample2x_bwd, s["dout"].data_ptr(), d1.data_ptr(), B, hs[3], hs[3], 1, F32)
+        # gradient scratch for maps: dpre (grad of conv output), dup (grad of conv input)
+        dpre = self._shared("dpre", B * hs[3] * hs[3] * 256, T)
+        dup = self._shared("dup", B * hs[3] * hs[3] * 256, T)
+        dact = self._shared("dact", B * hs[2] * hs[2] * 256, T)
+        for i in (3, 2, 1, 0):
+            hn = "decode_head%d" % i
+            HW = hs[i] * hs[i]
+            # GroupNorm parameter gradients: the per-block partials {dbeta, dgamma, dw1}[256] stay in this layer's own workspace and
+            # are summed by the table launch that finishes the layer's conv wgrad anyway (they used to be 2-3 colsum launches of 16
+            # workgroups each: ~80 us per step of latency-bound finishers)
+            gws = self._shared("gnbw%d" % i, B * 64 * 3 * 256 + 64 + 16 * B + B * 3 * 256)
+            self._claim(gws.data_ptr())
+            if i == 3:
+                self._op(ops, L.countr_groupnorm_relu_bwd, hc[i].data_ptr(), None, d1.data_ptr(), self._pp(hn + ".3.weight"),
+                         hstats[i].data_ptr(), self._pp(hn + ".1.weight"), self._pp(hn + ".1.bias"), dpre.data_ptr(),
+                         None, None, None, self._gp(hn + ".3.bias"), gws.data_ptr(), B, HW, 256, 8, code, self._acc)
             else:
-                BS = B * S
-                dyt = A("dyt", (BS, Dd), T) if code == BF16 else None
-                g_y = self._cast(ops, dy_tok, dyt, BS * Dd)
-                dc = [A("dc%d" % (i + 1), (BS, sizes[i], sizes[i], chans[i]), T) for i in range(4)]
-                dpl = [A("dp%d" % (i + 1), (BS, sizes[i] // 2, sizes[i] // 2, chans[i]), T) for i in range(3)]
-                for i in (3, 2, 1, 0):
-                    self._op(ops, L.countr_instnorm_relu_pool_bwd, p.in_maps[i].data_ptr(), (g_y if i == 3 else dpl[i]).data_ptr(), stats[i].data_ptr(),
-                             dc[i].data_ptr(), BS, sizes[i], sizes[i], chans[i], int(i == 3), code, in_ws.data_ptr(), int(p.in_xhat))
-                    wn = "decoder_proj%d.0.weight" % (i + 1)
-                    if i == 0:
-                        ws = self._shared("c3wgrad", L.countr_conv3x3_c3_wgrad_nblocks() * 64 * 28)
-                        self._op(ops, L.countr_conv3x3_c3_wgrad, boxes.data_ptr(), dc[0].data_ptr(), self._gp(wn), self._gp(wn[:-6] + "bias"),
-                                 ws.data_ptr(), BS, 64, 64, code, self._acc)
-                    else:
-                        self._conv_wgrad(ops, dc[i], pl[i - 1], wn, BS, sizes[i], sizes[i], chans[i - 1], chans[i], bias_name=wn[:-6] + "bias")
-                        self._conv_fwd(ops, dc[i], self.Wd[wn], None, dpl[i - 1], BS, sizes[i], sizes[i], chans[i], chans[i - 1])
-            self._flush_reductions(p)
-            for ops_ in (lists.bwd_head, lists.bwd_rest, lists.bwd_tok):
-                self._auto_warm(ops_)
-        self._acc = 0
-        return p
+                self._op(ops, L.countr_upsample2x_bwd, dup.data_ptr(), dact.data_ptr(), B, hs[i], hs[i], 256, code)
+                self._op(ops, L.countr_groupnorm_relu_bwd, hc[i].data_ptr(), dact.data_ptr(), None, None, hstats[i].data_ptr(),
+                         self._pp(hn + ".1.weight"), self._pp(hn + ".1.bias"), dpre.data_ptr(), None, None, None, None,
+                         gws.data_ptr(), B, HW, 256, 8, code, self._acc)
+            # the backward's finalize pass leaves per-IMAGE sums behind the split partials: B rows to add, not B * nsplit
+            img = gws.data_ptr() + 4 * L.countr_groupnorm_bwd_image_sums_offset(B, HW)
+            planes = [(0, hn + ".1.bias"), (1, hn + ".1.weight")] + ([(2, hn + ".3.weight")] if i == 3 else [])
+            for plane, pname in planes:
+                self._reduce_later(ops, gws.data_ptr(), img + plane * 256 * 4, self._gp(pname), B, 3 * 256, 256)
+            self._conv_wgrad(ops, dpre, hin[i], hn + ".0.weight", B, hs[i], hs[i], cin[i], 256, bias_name=hn + ".0.bias")
+            # dgrad == forward conv of dpre with the dgrad-form weights (Cin_gemm = 256 output channels)
+            tgt = dup if i > 0 else ddn
+            self._gemm(ops, code, OP_IM2ROW, OP_ROW, A=dpre.data_ptr(), B=self.Wd[hn + ".0.weight"].data_ptr(), C=tgt.data_ptr(),
+                       ldb=9 * 256, ldc=cin[i], M=B * HW, N=cin[i], K=9 * 256, H=hs[i], W=hs[i], Cin=256,
+                       out_bf16=int(code == BF16))
+        return self._layernorm_bwd(ops, ddn, head["x"], "decoder_norm", head["mN"], head["rN"], s["gx"], rows, Dd, accumulate=False, dx_t=s["gxT"])
+
+    def _dec_block_bwd(self, lists, i, d, s, tok, B, g_t, tok_dgrads, embed_in=None):
+        """Backward of decoder block i into lists.bwd_rest.  g_t = bf16 / fp32 operand view of s["gx"] on entry (emitted by the previous
+        LayerNorm backward); returns the view of the updated gx.  tok_dgrads collects the (dK | dV, weight) pairs whose input gradients
+        head bwd_tok.  embed_in (block 0): decoder_embed's input -- its weight gradient joins the block's group (no dgrad: the encoder
+        is frozen)."""
+        L, code, ops = self.L, self.code, lists.bwd_rest
+        N, D, Dd, Hd, rows = self.N, self.D, self.Dd, self.Hd, B * self.N
+        Sy, ytok, tok_rows = tok["Sy"], tok["ytok"], tok["tok_rows"]
+        b = "decoder_blocks.%d" % i
+        gx, dh, dn_t, dproj_in, dqkv, dq = s["gx"], s["dh"], s["dn_t"], s["dproj_in"], s["dqkv"], s["dq"]
+        xws = self._shared("xattn", L.countr_xattn_bwd_workspace_floats(B, N, Sy, Dd))
+        # ---- mlp: x3 = x2 + fc2(gelu(fc1(LN2(x2))))
+        grp = [] if code == BF16 else None
+        self._linear_bwd(ops, g_t, d["hact"], b + ".mlp.fc2.weight", rows, Dd, 4 * Dd, dx=dh, gelu_pre=d["hpre"], group=grp)
+        self._linear_bwd(ops, dh, d["n2"], b + ".mlp.fc1.weight", rows, 4 * Dd, Dd, dx=dn_t, group=grp)
+        g_t = self._layernorm_bwd(ops, dn_t, d["x2"], b + ".norm2", d["m2"], d["r2"], gx, rows, Dd, accumulate=True, dx_t=next(s["next_gxT"]))
+        # ---- cross attention: x2 = x1 + proj(xattn(wq(LN1(x1)), wk(y), wv(y)))
+        self._linear_bwd(ops, g_t, d["xo"], b + ".attn.proj.weight", rows, Dd, Dd, dx=dproj_in, group=grp)
+        dk, dv, dkT, dvT = s["dk"][i], s["dv"][i], s["dkT"][i], s["dvT"][i]
+        self._op(ops, L.countr_xattn_bwd, d["q"].data_ptr(), d["k"].data_ptr(), d["v"].data_ptr(), dproj_in.data_ptr(), dq.data_ptr(),
+                 dk.data_ptr(), dv.data_ptr(), xws.data_ptr(), B, N, Sy, Dd, Hd, d["ldkv"], (Dd // Hd) ** -0.5, code,
+                 dkT.data_ptr() if dkT is not None else None, dvT.data_ptr() if dvT is not None else None)
+        if i == 0:
+            lists.tok_ready = len(ops)    # every block's dK / dV is final: the exemplar-token backward may start (run_backward_rest_and_tok)
+        self._linear_bwd(ops, dq, d["n1"], b + ".attn.wq.weight", rows, Dd, Dd, dx=dn_t, group=grp)
+        g_t = self._layernorm_bwd(ops, dn_t, d["x1"], b + ".norm1", d["m1"], d["r1"], gx, rows, Dd, accumulate=True, dx_t=next(s["next_gxT"]))
+        dk_t, dv_t = (dk, dv) if dkT is None else (dkT, dvT)    # bf16 copies come out of the cross-attention backward
+        for nm, g_kv in (("wk", dk_t), ("wv", dv_t)):
+            if grp is not None:     # over the zero-padded rows: whole k-tiles, same sums
+                grp.append((g_kv, ytok, b + ".attn.%s.weight" % nm, tok_rows, Dd, Dd, b + ".attn.%s.bias" % nm))
+            else:
+                self._linear_wgrad(ops, g_kv, ytok, b + ".attn.%s.weight" % nm, B * Sy, Dd, Dd, bias_name=b + ".attn.%s.bias" % nm)
+            tok_dgrads.append((g_kv, b + ".attn.%s.weight" % nm))
+        # ---- self attention: x1 = xin + proj(attn(qkv(LN0(xin))))
+        self._linear_bwd(ops, g_t, d["att"], b + ".selfattn.proj.weight", rows, Dd, Dd, dx=dproj_in, group=grp)
+        if d["lse"] is not None:
+            dlt = self._shared("attn_delta", B * Hd * N)
+            self._op(ops, L.countr_attn_bwd, d["qkv"].data_ptr(), d["att"].data_ptr(), dproj_in.data_ptr(), d["lse"].data_ptr(),
+                     dlt.data_ptr(), dqkv.data_ptr(), B, N, Hd, Dd // Hd, (Dd // Hd) ** -0.5)
+        else:
+            self._attention_bwd(ops, d["qkv"], d["probs"], dproj_in, dqkv, B, Hd, Dd)
+        self._linear_bwd(ops, dqkv, d["n0"], b + ".selfattn.qkv.weight", rows, 3 * Dd, Dd, dx=dn_t, group=grp)
+        g_t = self._layernorm_bwd(ops, dn_t, d["xin"], b + ".norm0", d["m0"], d["r0"], gx, rows, Dd, accumulate=True, dx_t=next(s["next_gxT"]))
+        if embed_in is not None:
+            self._linear_bwd(ops, g_t, embed_in, "decoder_embed.weight", rows, Dd, D, group=grp)
+        if grp is not None:      # fc2, fc1, attn.proj, attn.wq, selfattn.proj, selfattn.qkv (, decoder_embed)
+            self._linear_wgrad_group(ops, grp)
+        return g_t
+
+    def _exemplar_tokens_bwd(self, ops, p, B, S, tok, s, tok_dgrads):
+        """dy_tok = sum over blocks of dK Wk + dV Wv, then the shot token's gradient (S == 0) or the exemplar CNN's backward."""
+        L, T, code, Dd, n = self.L, self.tdt, self.code, self.Dd, B * tok["Sy"]
+        A = lambda k, shape, dt: self._alloc(p, k, shape, dt)
+        dy_tok = s["dy_tok"]
+        for j, (g_kv, wn) in enumerate(tok_dgrads):
+            self._linear_dgrad(ops, g_kv, wn, dy_tok, n, Dd, Dd, resid=(None if j == 0 else dy_tok), out_bf16=False)
+        if S == 0:
+            ws = self._shared("colsum", 256 * 4096)
+            self._op(ops, L.countr_colsum, dy_tok.data_ptr(), self._gp("shot_token"), ws.data_ptr(), B, Dd, F32, self._acc)
+            return
+        BS = B * S
+        sizes, chans, pl = tok["sizes"], tok["chans"], tok["pl"]
+        dyt = A("dyt", (BS, Dd), T) if code == BF16 else None
+        g_y = self._cast(ops, dy_tok, dyt, BS * Dd)
+        dc = [A("dc%d" % (i + 1), (BS, sizes[i], sizes[i], chans[i]), T) for i in range(4)]
+        dpl = [A("dp%d" % (i + 1), (BS, sizes[i] // 2, sizes[i] // 2, chans[i]), T) for i in range(3)]
+        for i in (3, 2, 1, 0):
+            self._op(ops, L.countr_instnorm_relu_pool_bwd, tok["in_maps"][i].data_ptr(), (g_y if i == 3 else dpl[i]).data_ptr(), tok["stats"][i].data_ptr(),
+                     dc[i].data_ptr(), BS, sizes[i], sizes[i], chans[i], int(i == 3), code, tok["in_ws"].data_ptr(), int(tok["in_xhat"]))
+            wn = "decoder_proj%d.0.weight" % (i + 1)
+            if i == 0:
+                ws = self._shared("c3wgrad", L.countr_conv3x3_c3_wgrad_nblocks() * 64 * 28)
+                self._op(ops, L.countr_conv3x3_c3_wgrad, tok["boxes"].data_ptr(), dc[0].data_ptr(), self._gp(wn), self._gp(wn[:-6] + "bias"),
+                         ws.data_ptr(), BS, 64, 64, code, self._acc)
+            else:
+                self._conv_wgrad(ops, dc[i], pl[i - 1], wn, BS, sizes[i], sizes[i], chans[i - 1], chans[i], bias_name=wn[:-6] + "bias")
+                self._conv_fwd(ops, dc[i], self.Wd[wn], None, dpl[i - 1], BS, sizes[i], sizes[i], chans[i], chans[i - 1])
 
     # ------------------------------------------------------------------ execution API
     def _load_inputs(self, p, imgs, boxes, S):
@@ -1315,7 +1399,7 @@ class Engine:
         self._load_inputs(p, imgs, boxes, int(shot_num))
         self.run(p.fwd_par)
         if train:
-            p.fwd_gen = getattr(p, "fwd_gen", 0) + 1   # the activations a backward of this plan will read belong to THIS forward
+            p.fwd_gen += 1   # the activations a backward of this plan will read belong to THIS forward
         return p.buf["out"]
 
     def forward_loaded(self, B, shot_num):
@@ -1332,16 +1416,33 @@ class Engine:
         each, ~150 us at 24 exemplars) go to side lane 1 and the main lane runs what does not read the exemplar tokens -- decoder_embed and
         the first block's self-attention half, up to the query projection -- beside them; joined in front of the first cross-attention.
         In the plain forward the chain hides beside the encoder (p.fwd_par); inline it was the head of the decoder's critical path."""
-        dec = p.fwd[p.enc_ops:]
-        ex, xi = getattr(p, "ex_range", None), getattr(p, "first_xattn", None)
-        if ex is None or xi is None or self.code != BF16 or not (p.enc_ops <= ex[0] <= ex[1] <= xi):
-            return dec
-        cached = getattr(p, "_dec_lane", None)
-        if cached is None:
-            mark = lambda *a: (None, a, None)
-            cached = p._dec_lane = ([mark("fork"), mark("lane", 1)] + p.fwd[ex[0]:ex[1]] + [mark("lane", 0)] + p.fwd[p.enc_ops:ex[0]]
-                                    + p.fwd[ex[1]:xi] + [mark("join")] + p.fwd[xi:])
-        return cached
+        if "dec" not in p.sched:
+            ex, xi = p.ex_range, p.first_xattn
+            if ex is None or xi is None or self.code != BF16 or not (p.enc_ops <= ex[0] <= ex[1] <= xi):
+                p.sched["dec"] = p.fwd[p.enc_ops:]
+            else:
+                p.sched["dec"] = side_by_side(p.fwd[ex[0]:ex[1]], p.fwd[p.enc_ops:ex[0]] + p.fwd[ex[1]:xi]) + p.fwd[xi:]
+        return p.sched["dec"]
+
+    def pipelined_forward_ops(self, p, have, ahead):
+        """The forward of plan p with the frozen encoder pipelined across calls / steps: [this batch's encoder, unless its latent is
+        already in place (`have`)] + [the NEXT batch's encoder forward on the lane of its own (`ahead`: PFORK ... PMAIN, closed by
+        pipe_join())] + the decoder side with the exemplar lane.  (False, False) is NOT p.fwd_par: the exemplar CNN runs beside the
+        decoder's head, not beside the encoder."""
+        if p.enc_pipe is None:
+            raise _lib.CountrError("the pipelined forward needs a 16-bit precision and the fused attention kernel")
+        key = ("pipe", bool(have), bool(ahead))
+        if key not in p.sched:
+            lane = [PFORK] + p.enc_pipe + [PMAIN] if ahead else []
+            p.sched[key] = ([] if have else p.fwd[:p.enc_ops]) + lane + self.decoder_ops_with_exemplar_lane(p)
+        return p.sched[key]
+
+    def forward_ops_behind(self, p, first):
+        """The full forward of plan p with the ops `first` at the head of lane 1 (trainer: the deferred optimizer update):
+        [fork | lane 1: first, exemplar CNN | lane 0: the frozen encoder | join | decoder_embed ... density head].  Everything that reads
+        a trainable parameter sits behind `first` on lane 1 or behind the join.  Not cached here: `first` is the caller's."""
+        ex = p.ex_range or (p.enc_ops, p.enc_ops)
+        return side_by_side(first + p.fwd[ex[0]:ex[1]], p.fwd[:p.enc_ops]) + p.fwd[p.enc_ops:ex[0]] + p.fwd[ex[1]:]
 
     def forward_loaded_pipelined(self, B, shot_num, have, ahead):
         """forward_loaded with the frozen encoder pipelined across calls (inference has no trainable side at all: every forward's encoder
@@ -1350,18 +1451,11 @@ class Engine:
         this batch's latent is waiting there (the previous call ran with ahead=True for it) -- it is copied into place and the encoder
         is not run again.  Same launches on the same data as forward_loaded: bit-identical maps (tests/test_inference_gpu.py)."""
         p = self.plan(B, int(shot_num), False)
-        if p.enc_pipe is None:
-            raise _lib.CountrError("the pipelined forward needs a 16-bit precision and the fused attention kernel")
+        ops = self.pipelined_forward_ops(p, have, ahead)
         if have:
             n = p.buf["latent"].numel()
             p.buf["latent"].view(-1).copy_(p.pipe_latent[:n], non_blocking=True)
-        key = (bool(have), bool(ahead))
-        cache = p.__dict__.setdefault("_pipe_fwd", {})
-        if key not in cache:
-            mark = lambda *a: (None, a, None)
-            lane = ([mark("pfork")] + p.enc_pipe + [mark("pmain")]) if ahead else []
-            cache[key] = ([] if have else p.fwd[:p.enc_ops]) + lane + self.decoder_ops_with_exemplar_lane(p)
-        self.run(cache[key])
+        self.run(ops)
         if ahead:
             self.pipe_join()
         return p.buf["out"]
@@ -1421,10 +1515,9 @@ class Engine:
         bits as a cast of the master, half the bytes read).  The tables of pointers are built once."""
         if not self.conv_names and not self.WtT:
             return
-        if getattr(self, "_shadow_tab", None) is None:
+        if self._shadow_tab is None:
             lin = list(self.WtT)                      # Linear weights [N][K]: only the transposed form
             from16 = self.half and all(self.layout.shapes[c][0] % 64 == 0 and self.layout.shapes[c][1] % 64 == 0 for c in lin)
-            self._lin_tab = None
             if lin and from16:
                 m = len(lin)
                 shp = [self.layout.shapes[c] for c in lin]

@@ -117,10 +117,10 @@ def _native_maps(model, images, boxes, shot_num, max_batch, want_sums, have=None
     img = p.buf["img"]
     st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     nw = len(plan)
-    have = getattr(p, "enc_pipe", None) is not None and eng.pipe_owner(have)      # (`have`: the token of the call that ran our encoder)
+    have = p.enc_pipe is not None and eng.pipe_owner(have)      # (`have`: the token of the call that ran our encoder)
     if not have:
         _gather_windows(L, images, plan, h, img, nb, st)
-    plan_next = _native_plan(model, ahead, max_batch) if (ahead is not None and getattr(p, "enc_pipe", None) is not None) else None
+    plan_next = _native_plan(model, ahead, max_batch) if (ahead is not None and p.enc_pipe is not None) else None
     if plan_next is not None and (_bucket(len(plan_next), max_batch) != nb or ahead[0].shape[-2] != h or ahead[0].device != dev):
         plan_next = None
     if plan_next is not None:

@@ -126,18 +126,8 @@ class MaeEngine(Engine):
                 "dqkv": A(".dqkv", (rows, 3 * Dm), T)}
 
     # ------------------------------------------------------------------ plans
-    def plan(self, B, K, train):
-        key = (B, K, bool(train))
-        if key not in self.plans:
-            self._sizing = True
-            try:
-                for tr in (False, True):
-                    self._build(B, K, tr)
-            finally:
-                self._sizing = False
-            self._reserve()
-            self.plans[key] = self._build(B, K, bool(train))
-        return self.plans[key]
+    def _sized_with(self, K, train):
+        return [(K, False), (K, True)]
 
     def _build(self, B, K, train):
         """K = len_keep tokens per image seen by the encoder (models_mae_noct.py:117)."""

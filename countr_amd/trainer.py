@@ -150,6 +150,10 @@ class _GraphStep:
         self._pipe_next = None
         self._pipe_gen = -1
         self._pipe_tok = None
+        self._defer_fwd = {}           # defer_optimizer: (plan, pending key) -> the forward list that applies that update first (_fwd_list)
+        self._copy_stream = None       # host-batch staging (_to_device), created with the first host batch
+        self._staging, self._staged_ev, self._stage_slot, self._consumed_evs = {}, None, 0, [None] * self.STAGING_SLOTS
+        self._capture_agreed = False   # _run_captured_comm: the ranks have agreed on captured / host-issued collectives
         self.grad_scale = 1.0 / self.accum
         # fp16 mode: torch.cuda.amp.GradScaler as the reference uses it (util/misc.py:260-286; GradScaler() defaults: scale 65536, growth
         # x 2 every 2000 clean steps, x 0.5 and NO optimizer step on a non-finite gradient), kept on the device so that the captured step
@@ -185,12 +189,9 @@ class _GraphStep:
         the plan's input buffers.  Device tensors pass through.  Returns device tensors valid on the step's stream."""
         if all(t.is_cuda for t in tensors):
             return tensors
-        if not hasattr(self, "_copy_stream"):
+        if self._copy_stream is None:
             self._copy_stream = torch.cuda.Stream(device=self.eng.device)
-            self._staging = {}
             self._staged_ev = torch.cuda.Event()
-            self._stage_slot = 0
-            self._consumed_evs = [None] * self.STAGING_SLOTS
         self._stage_slot = slot = (self._stage_slot + 1) % self.STAGING_SLOTS
         out = []
         if self._consumed_evs[slot] is not None:
@@ -216,7 +217,7 @@ class _GraphStep:
     STAGING_SLOTS = 3
 
     def _staging_consumed(self):
-        if hasattr(self, "_copy_stream"):
+        if self._copy_stream is not None:
             ev = torch.cuda.Event()
             ev.record(self.stream)
             self._consumed_evs[self._stage_slot] = ev
@@ -341,6 +342,7 @@ class _GraphStep:
             return
         if self._gen != self.eng.generation:   # the engine re-planned (bigger batch elsewhere): old graphs are stale
             self.graphs.clear()
+            self._defer_fwd.clear()
             self._gen = self.eng.generation
         key = (name, S)
         g = self.graphs.get(key)
@@ -363,6 +365,7 @@ class _GraphStep:
         rank's host-issued ones.  Later capture failures are real errors and raise."""
         if self._gen != self.eng.generation:
             self.graphs.clear()
+            self._defer_fwd.clear()
             self._gen = self.eng.generation
         g = self.graphs.get(gk)
         if g is not None:
@@ -370,7 +373,7 @@ class _GraphStep:
             return
         whole(gk[1])                      # the step itself (eager); errors propagate
         torch.cuda.synchronize()
-        first = not getattr(self, "_capture_agreed", False)
+        first = not self._capture_agreed
         g, err = None, None
         try:
             g = torch.cuda.CUDAGraph()
@@ -567,7 +570,7 @@ class _GraphStep:
             for _name, _fn, gkey in phases[:1]:
                 pl = eng.plans.get((self.B, gkey[0], True))
                 if pl is not None:
-                    pl.fwd_gen = getattr(pl, "fwd_gen", 0) + 1
+                    pl.fwd_gen += 1
             # what the window's end reduces / steps is known before anything runs (the sets follow from the shot_nums drawn so far), so
             # the AdamW scalars of an applying step travel with the prologue at the head of its first phase
             ckey, cskip, zfill = None, (), ()
@@ -719,13 +722,6 @@ class FinetuneStep(_GraphStep):
     def _prologue_mask(self):
         return self.mask
 
-    def _pipe_lane(self, p):
-        """The encoder lane's launches, issued at the head of the step on a lane of their own (forked from the main lane)."""
-        if not p.enc_pipe:
-            return []
-        mark = lambda *a: (None, a, None)
-        return [mark("pfork")] + p.enc_pipe + [mark("pmain")]
-
     def _fwd_list(self, p, pc):
         """The forward launch list of plan p; with a pending optimizer update pc (defer_optimizer) the list that applies it first:
         [fork | lane 1: AdamW + shadow refresh, exemplar CNN | lane 0: the frozen encoder | join | decoder_embed ... head].  Everything
@@ -736,26 +732,14 @@ class FinetuneStep(_GraphStep):
             # computed here first) and -- steady / coldnext -- the NEXT batch's frozen-encoder forward runs on its own lane until the end
             # of the step ("pfork" ... eng.pipe_join() behind the optimizer update)
             assert pc is None
-            cache = p.__dict__.setdefault("_pipe_lists", {})
-            if mode not in cache:
-                dec = self.eng.decoder_ops_with_exemplar_lane(p)
-                lane = self._pipe_lane(p)
-                cache[mode] = {"steady": lane + dec, "last": dec, "coldnext": p.fwd[:p.enc_ops] + lane + dec}[mode]
-            return cache[mode]
+            have, ahead = {"steady": (True, True), "last": (True, False), "coldnext": (False, True)}[mode]
+            return self.eng.pipelined_forward_ops(p, have, ahead)
         if pc is None:
             return p.fwd_par
-        cache = p.__dict__.setdefault("_defer_lists", {})
-        if pc not in cache:
-            mark = lambda *a: (None, a, None)
+        if (p, pc) not in self._defer_fwd:
             adam = (lambda st, pc=pc: (self._phase_c(pc, stream=st), 0)[1], (), None)
-            ex = getattr(p, "ex_range", None)
-            enc = p.fwd[:p.enc_ops]
-            if ex is None:
-                lane1, rest = [adam], p.fwd[p.enc_ops:]
-            else:
-                lane1, rest = [adam] + p.fwd[ex[0]:ex[1]], p.fwd[p.enc_ops:ex[0]] + p.fwd[ex[1]:]
-            cache[pc] = [mark("fork"), mark("lane", 1)] + lane1 + [mark("lane", 0)] + enc + [mark("join")] + rest
-        return cache[pc]
+            self._defer_fwd[p, pc] = self.eng.forward_ops_behind(p, [adam])
+        return self._defer_fwd[p, pc]
 
     def _make_sync(self, process_group):
         lay = self.eng.layout   # buckets in backward-completion order: head | decoder blocks + embed | exemplar CNN | shot_token
