@@ -1,0 +1,9 @@
+"""CounTR on the MI355X.  The raw-frame entry points are re-exported here; they load on first use so that `import countr_amd` (the
+build, the CPU tools) stays free of torch."""
+
+
+def __getattr__(name):
+    if name in ("count_frames", "FramePrep"):
+        from . import frames
+        return getattr(frames, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1,0 +1,243 @@
+"""Counting from raw frames: uint8 [H, W, 3] images and pixel-coordinate exemplar boxes in, counts and density maps out.
+
+The preparation the reference leaves to PIL / torchvision on the host -- resize to height 384 with the width a multiple of 16
+(demo_zero.py:23-38, demo.py:42-49), ToTensor, the 64 x 64 exemplar crops (demo.py:60-68) and the 3 x 3 crop-and-upscale for tiny
+exemplars (:84-99) -- runs as HIP kernels on the stream the forward runs on (csrc/frames.hip: countr_frame_resize_u8,
+countr_crop_resize_f32).  The prepared image equals PIL's BILINEAR resize + ToTensor bit for bit, and everything behind it is
+inference.count_images / density_maps unchanged, so the results equal the host-prepared path's.  There is no host fallback."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib, inference
+
+NEW_H = 384
+BOX = 64                    # exemplar crops are 64 x 64 (demo.py:67)
+MAX_BATCHED = 16            # csrc/frames.hip: MAX_FRAMES / MAX_RECTS
+
+
+def new_width(W, H):
+    """Width of the resized frame (demo_zero.py:28-31, demo.py:42-44)."""
+    return 16 * int((W / H * NEW_H) / 16)
+
+
+def scale_boxes(boxes_xyxy, W, H):
+    """Boxes [(x1, y1, x2, y2), ...] in pixels of the ORIGINAL W x H frame -> rects [[y1, x1, y2, x2], ...] of the resized frame, with the
+    reference's scale factors and int() truncation (demo.py:45-46, 60-65).  The corners are inclusive (:66)."""
+    sw, sh = float(new_width(W, H)) / W, float(NEW_H) / H
+    return [[int(y1 * sh), int(x1 * sw), int(y2 * sh), int(x2 * sw)] for x1, y1, x2, y2 in boxes_xyxy]
+
+
+def pil_tables(in_size, out_size):
+    """(ksize, bounds int32 [out, 2], weights int32 [out, ksize]) of countr_pil_bilinear_tables, as numpy arrays."""
+    L = _lib.lib()
+    ksize = L.countr_pil_bilinear_tables(in_size, out_size, None, None)
+    _lib.check(min(ksize, 0), "countr_pil_bilinear_tables")
+    bounds = np.empty((out_size, 2), np.int32)
+    weights = np.empty((out_size, ksize), np.int32)
+    _lib.check(min(L.countr_pil_bilinear_tables(in_size, out_size, bounds.ctypes.data, weights.ctypes.data), 0), "countr_pil_bilinear_tables")
+    return ksize, bounds, weights
+
+
+def _stream(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def crop_resize(image, rects, oh, ow):
+    """countr_crop_resize_f32: image [1, 3, h, w] (or [3, h, w]) fp32 on the device, rects [[y1, x1, y2, x2], ...] inclusive ->
+    [n, 3, oh, ow] = F.interpolate(image[:, y1:y2 + 1, x1:x2 + 1], (oh, ow), bilinear) per rectangle."""
+    if not (image.is_cuda and image.dtype == torch.float32 and image.is_contiguous() and image.shape[-3] == 3 and image.numel() == 3 * image.shape[-2] * image.shape[-1]):
+        raise ValueError("crop_resize: a contiguous fp32 device image [1, 3, h, w] is required")
+    h, w = image.shape[-2:]
+    n = len(rects)
+    out = torch.empty(n, 3, oh, ow, device=image.device, dtype=torch.float32)
+    L = _lib.lib()
+    with torch.cuda.device(image.device):
+        for r0 in range(0, n, MAX_BATCHED):
+            part = [int(v) for r in rects[r0:r0 + MAX_BATCHED] for v in r]
+            arr = (C.c_int * len(part))(*part)
+            _lib.check(L.countr_crop_resize_f32(image.data_ptr(), h, w, arr, len(part) // 4, oh, ow, out[r0:].data_ptr(), _stream(image.device)),
+                       "countr_crop_resize_f32")
+    return out
+
+
+def exemplars(image, boxes_xyxy, W, H):
+    """Exemplar tensors of one prepared frame: image [1, 3, 384, new_W] (FramePrep.prepare), boxes in pixels of the original W x H frame
+    -> (boxes [1, S, 3, 64, 64] on the device, rects [[y1, x1, y2, x2], ...]) as demo.py:60-71 builds them."""
+    rects = scale_boxes(boxes_xyxy, W, H)
+    return crop_resize(image, rects, BOX, BOX).unsqueeze(0), rects
+
+
+def split_rects(h, w):
+    """The nine h // 3 x w // 3 rectangles of the 3 x 3 split, in the order inference.count_image cuts them
+    (FSC_test_cross(few-shot).py:273-320)."""
+    return [[top, left, top + h // 3 - 1, left + w // 3 - 1]
+            for top, left in ((0, 0), (h // 3, 0), (0, w // 3), (h // 3, w // 3), (h * 2 // 3, 0), (h * 2 // 3, w // 3),
+                              (0, w * 2 // 3), (h // 3, w * 2 // 3), (h * 2 // 3, w * 2 // 3))]
+
+
+def split_crops(image):
+    """The nine crops of the 3 x 3 split, each upscaled back to the image's size: [[1, 3, h, w], ...] (views of one buffer)."""
+    h, w = image.shape[-2:]
+    up = crop_resize(image, split_rects(h, w), h, w)
+    return [up[k:k + 1] for k in range(9)]
+
+
+def _is_u8(f):
+    return f.dtype == (torch.uint8 if isinstance(f, torch.Tensor) else np.uint8)
+
+
+class _Slot:
+    """The buffers of one frame position of one frame shape: pinned staging, the device copy, and the event of their last use."""
+
+    def __init__(self, H, W, device):
+        self.host = torch.empty(H, W, 3, dtype=torch.uint8).pin_memory()
+        self.dev = torch.empty(H, W, 3, dtype=torch.uint8, device=device)
+        self.copied = None
+
+
+class FramePrep:
+    """Resize + ToTensor of raw frames on the device.  Owns everything that must not be allocated per call: the tap tables per
+    (in, out) size pair (device copies), and per frame shape in use the uint8 intermediate of the horizontal pass, pinned host staging
+    buffers and device uint8 buffers (one per frame of that shape in a call).  Only the returned fp32 tensors are new."""
+
+    def __init__(self, device="cuda"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.CountrError("FramePrep needs a GPU device: the HIP path has no CPU fallback")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.L = _lib.lib()
+        self._tables = {}      # (in, out) -> (bounds, weights) on the device
+        self._slots = {}       # (H, W) -> [_Slot, ...]
+        self._tmp = {}         # (H, W) -> uint8 [n, H, out_w, 3]
+        self._last = None      # (stream, event) of the previous prepare: a call on another stream waits for it before it reuses the buffers
+
+    def tables(self, in_size, out_size):
+        t = self._tables.get((in_size, out_size))
+        if t is None:
+            _k, bounds, weights = pil_tables(in_size, out_size)
+            t = self._tables[(in_size, out_size)] = (torch.from_numpy(bounds).to(self.device), torch.from_numpy(weights).to(self.device))
+        return t
+
+    def _frame_on_device(self, frame, slot):
+        """The frame's bytes on the device: a contiguous uint8 device tensor is used where it is; a host frame goes through the slot's
+        pinned buffer with an asynchronous copy."""
+        if isinstance(frame, torch.Tensor) and frame.is_cuda:
+            if frame.device != self.device:
+                raise ValueError("FramePrep: frame on %s, this FramePrep is for %s" % (frame.device, self.device))
+            return frame if frame.is_contiguous() else frame.contiguous()
+        if slot.copied is not None:
+            slot.copied.synchronize()          # the pinned buffer's previous copy must have left it (long done unless calls are back to back)
+        if isinstance(frame, torch.Tensor):
+            slot.host.copy_(frame)
+        else:
+            np.copyto(slot.host.numpy(), frame)
+        slot.dev.copy_(slot.host, non_blocking=True)
+        if slot.copied is None:
+            slot.copied = torch.cuda.Event()
+        slot.copied.record(torch.cuda.current_stream(self.device))
+        return slot.dev
+
+    def prepare(self, frames):
+        """frames: uint8 [H, W, 3] each (np.ndarray, CPU tensor or device tensor) -> [[1, 3, 384, new_W] fp32 device tensors], each equal
+        to ToTensor(PIL resize((new_W, 384), BILINEAR)) bit for bit.  Frames of one shape share launches (up to 16 per launch pair)."""
+        out = [None] * len(frames)
+        by_shape = {}
+        for i, f in enumerate(frames):
+            if not _is_u8(f) or len(f.shape) != 3 or f.shape[2] != 3:
+                raise ValueError("FramePrep.prepare: frames are uint8 [H, W, 3], got %s %s" % (f.dtype, tuple(f.shape)))
+            by_shape.setdefault((int(f.shape[0]), int(f.shape[1])), []).append(i)
+        with torch.cuda.device(self.device):
+            st = _stream(self.device)
+            cur = torch.cuda.current_stream(self.device)
+            if self._last is not None and self._last[0] != cur:
+                cur.wait_event(self._last[1])
+            for (H, W), idxs in by_shape.items():
+                ow = new_width(W, H)
+                if ow < 16:
+                    raise ValueError("FramePrep.prepare: a %d x %d frame resizes to width %d" % (W, H, ow))
+                hb, hw = self.tables(W, ow)
+                vb, vw = self.tables(H, NEW_H)
+                slots = self._slots.setdefault((H, W), [])
+                while len(slots) < len(idxs):
+                    slots.append(_Slot(H, W, self.device))
+                nb = min(len(idxs), MAX_BATCHED)
+                tmp = self._tmp.get((H, W))
+                if tmp is None or tmp.shape[0] < nb:
+                    tmp = self._tmp[(H, W)] = torch.empty(nb, H, ow, 3, dtype=torch.uint8, device=self.device)
+                for g0 in range(0, len(idxs), MAX_BATCHED):
+                    sel = idxs[g0:g0 + MAX_BATCHED]
+                    srcs = [self._frame_on_device(frames[i], slots[g0 + k]) for k, i in enumerate(sel)]
+                    for i in sel:
+                        out[i] = torch.empty(1, 3, NEW_H, ow, device=self.device, dtype=torch.float32)
+                    fp = (C.c_void_p * len(sel))(*[s.data_ptr() for s in srcs])
+                    op = (C.c_void_p * len(sel))(*[out[i].data_ptr() for i in sel])
+                    _lib.check(self.L.countr_frame_resize_u8(fp, op, len(sel), H, W, NEW_H, ow, hb.data_ptr(), hw.data_ptr(), vb.data_ptr(),
+                                                             vw.data_ptr(), tmp.data_ptr(), st), "countr_frame_resize_u8")
+            if self._last is None or self._last[0] != cur:
+                self._last = (cur, torch.cuda.Event())
+            self._last[1].record(cur)
+        return out
+
+
+_PREPS = {}
+
+
+def frame_prep(device):
+    """The FramePrep of a device, made on first use (count_frames keeps its tables and workspaces here between calls)."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    p = _PREPS.get(device)
+    if p is None:
+        p = _PREPS[device] = FramePrep(device)
+    return p
+
+
+def prepare_items(device, frames, boxes=None, prep=None):
+    """Raw frames (+ per-frame lists of (x1, y1, x2, y2) boxes in original pixels, or None) -> the items inference.count_images takes:
+    [(image [1, 3, 384, new_W], exemplars [1, S, 3, 64, 64] or an empty [1, 0] tensor, rects or None), ...], all made on the device."""
+    prep = prep or frame_prep(device)
+    images = prep.prepare(frames)
+    items = []
+    for i, im in enumerate(images):
+        bx = boxes[i] if boxes is not None else None
+        if bx is not None and len(bx) > 0:
+            H, W = int(frames[i].shape[0]), int(frames[i].shape[1])
+            ex, rects = exemplars(im, bx, W, H)
+            items.append((im, ex, rects))
+        else:
+            items.append((im, torch.zeros(1, 0, device=im.device), None))
+    return items
+
+
+@torch.no_grad()
+def count_items(model, items, normalization=True, max_s_cnt=1, max_batch=32):
+    """inference.count_images over device-prepared items, with the 3 x 3 split of frames with tiny exemplars (demo.py:79-99) cut and
+    upscaled by countr_crop_resize_f32.  The reference's quirks stay: the count of a split frame is the sum over its nine maps and its
+    normalisation reads the LAST crop's map."""
+    res = [None] * len(items)
+    rest = []
+    for idx, (im, ex, rects) in enumerate(items):
+        if rects is not None and inference._small_exemplars(rects) >= max_s_cnt:
+            dms = inference.density_maps(model, split_crops(im), [ex] * 9, ex.shape[1], max_batch)
+            pred = sum((d.sum() / 60).item() for d in dms)
+            res[idx] = (inference._normalise(pred, dms[-1], rects, normalization), dms[-1])
+        else:
+            rest.append(idx)
+    if rest:
+        for idx, r in zip(rest, inference.count_images(model, [items[i] for i in rest], normalization, max_s_cnt, max_batch)):
+            res[idx] = r
+    return res
+
+
+@torch.no_grad()
+def count_frames(model, frames, boxes=None, normalization=True, max_s_cnt=1, max_batch=32):
+    """Raw frames in, [(count, density map [384, new_W]), ...] out.  frames: uint8 [H, W, 3] each, on the host or on the model's device;
+    boxes: None (zero-shot) or one list of (x1, y1, x2, y2) exemplar boxes per frame, in pixels of the original frame (an empty list =
+    zero-shot for that frame).  Preparation runs on the device (FramePrep, exemplars); frames are then grouped by shot count and
+    counted as inference.count_images counts them -- one forward per <= max_batch windows, the encoder pipelined across groups."""
+    device = next(model.parameters()).device
+    return count_items(model, prepare_items(device, frames, boxes), normalization, max_s_cnt, max_batch)

@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Few-shot counting demo: "this image, these boxes, how many?" on the MI355X engine.
+
+    python demo.py --input_path <image or directory> --boxes "x1,y1,x2,y2;x1,y1,x2,y2;..." [--boxes_json FILE]
+                   [--output_path results] [--model_path weights/FSC147.pth]
+
+The boxes are exemplar rectangles in pixels of the ORIGINAL image (left upper and right lower corner, both inclusive).  --boxes
+applies to every input image; --boxes_json names a JSON file {image file name: [[x1, y1, x2, y2], ...]} that takes precedence for
+the images it lists.  An image without boxes is counted zero-shot.  The frame is handed to the device as decoded uint8 pixels:
+the resize to height 384, the 64 x 64 exemplar crops and, for exemplars under 10 pixels, the 3 x 3 crop-and-upscale all run there
+(countr_amd.frames).  The visualisation is image + exemplar outlines + density / 2, clamped to [0, 1], at the resized size.
+`--model_path ""` runs the randomly initialised model (dry runs / tests)."""
+import json
+import time
+from argparse import ArgumentParser
+from itertools import chain
+from pathlib import Path
+
+import numpy as np
+import torch
+from PIL import Image
+
+import models_mae_cross
+from countr_amd import frames
+
+
+def parse_boxes(text):
+    """ "x1,y1,x2,y2;x1,y1,x2,y2" -> [(x1, y1, x2, y2), ...]"""
+    boxes = []
+    for part in (text or "").split(";"):
+        if not part.strip():
+            continue
+        v = [float(t) for t in part.split(",")]
+        if len(v) != 4:
+            raise ValueError("a box is x1,y1,x2,y2 -- got %r" % part)
+        boxes.append(tuple(v))
+    return boxes
+
+
+def save_visualisation(sample, density_map, rects, path):
+    """sample [3, h, w] in [0, 1], density_map [h, w]: outlines are drawn at 10 (white after the clamp), the density is halved."""
+    _, h, w = sample.shape
+    box_map = torch.zeros(h, w, device=sample.device)
+    for y1, x1, y2, x2 in rects or []:
+        ya, yb, xa, xb = min(y1, h - 1), min(y2, h - 1), min(x1, w - 1), min(x2, w - 1)
+        box_map[ya:yb + 1, xa] = 10
+        box_map[ya:yb + 1, xb] = 10
+        box_map[ya, xa:xb + 1] = 10
+        box_map[yb, xa:xb + 1] = 10
+    fig = torch.clamp(sample + box_map.unsqueeze(0) + density_map.unsqueeze(0) / 2, 0, 1)
+    Image.fromarray((fig.permute(1, 2, 0).cpu().numpy() * 255.0 + 0.5).astype(np.uint8)).save(path)
+
+
+def main():
+    p = ArgumentParser()
+    p.add_argument("--input_path", type=Path, required=True)
+    p.add_argument("--boxes", type=str, default="", help='exemplar boxes of every image: "x1,y1,x2,y2;..." in original pixels')
+    p.add_argument("--boxes_json", type=Path, default=None, help="JSON {file name: [[x1, y1, x2, y2], ...]}")
+    p.add_argument("--output_path", type=Path, default="results")
+    p.add_argument("--model_path", type=str, default="weights/FSC147.pth")
+    p.add_argument("--group_images", type=int, default=8, help="images prepared and counted per call")
+    p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
+    p.add_argument("--no_viz", action="store_true", help="counts only, no viz_*.jpg")
+    args = p.parse_args()
+    args.output_path.mkdir(exist_ok=True, parents=True)
+    device = torch.device("cuda")
+
+    if not args.model_path:
+        torch.manual_seed(0)          # dry runs without a checkpoint: the same random model every time
+    model = models_mae_cross.__dict__["mae_vit_base_patch16"](norm_pix_loss="store_true", precision=args.precision)
+    if args.model_path:
+        checkpoint = torch.load(args.model_path, map_location="cpu", weights_only=False)
+        model.load_state_dict(checkpoint["model"], strict=False)
+        print("Resume checkpoint %s" % args.model_path)
+    model.to(device).eval()
+
+    common = parse_boxes(args.boxes)
+    named = json.load(open(args.boxes_json)) if args.boxes_json else {}
+    if args.input_path.is_dir():
+        inputs = sorted(chain(args.input_path.glob("*.jpg"), args.input_path.glob("*.png")))
+    else:
+        inputs = [args.input_path]
+    done = 0
+    step = max(args.group_images, 1)
+    for g0 in range(0, len(inputs), step):
+        paths = inputs[g0:g0 + step]
+        raw = [np.asarray(Image.open(pth).convert("RGB"), dtype=np.uint8) for pth in paths]      # decoding stays on the host
+        boxes = [[tuple(b) for b in named[pth.name]] if pth.name in named else common for pth in paths]
+        t0 = time.perf_counter()
+        items = frames.prepare_items(device, raw, boxes)
+        results = frames.count_items(model, items)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / len(paths)
+        for pth, (sample, _ex, rects), (pred_cnt, dm) in zip(paths, items, results):
+            done += 1
+            if not args.no_viz:
+                save_visualisation(sample[0], dm.float(), rects, args.output_path / ("viz_%s.jpg" % pth.stem))
+            if len(inputs) > 1:
+                print("[%3d/%d] %s:\tcount = %5.2f  -  time = %5.2f" % (done, len(inputs), pth.name, pred_cnt, dt))
+            else:
+                print("Count:", pred_cnt, "- Time:", dt)
+
+
+if __name__ == "__main__":
+    main()

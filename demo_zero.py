@@ -8,7 +8,9 @@ counted with shot_num = 0 and an empty exemplar tensor (:41-74).  The reference 
 --group_images images (default 8: eight 1920x1080 frames = 32 windows = BASELINE config 5) share ONE forward
 (countr_amd.inference.count_images).  The visualisation (:77-90: image / 2 + density in the red channel / 2 + the count as text,
 resized back to the input size) is written with PIL, since torchvision is not part of this build.
-`--model_path ""` runs the randomly initialised model (dry runs / tests)."""
+`--model_path ""` runs the randomly initialised model (dry runs / tests).  `--device_prep` moves the resize to the device: the frames
+are decoded by PIL, handed over as uint8 pixels and resized by countr_frame_resize_u8 (same bits as the host resize, so same counts);
+the printed time then includes the preparation.  demo.py is the few-shot counterpart (exemplar boxes)."""
 import time
 from argparse import ArgumentParser
 from itertools import chain
@@ -19,7 +21,7 @@ import torch
 from PIL import Image, ImageDraw
 
 import models_mae_cross
-from countr_amd import inference
+from countr_amd import frames, inference
 
 shot_num = 0
 
@@ -56,6 +58,8 @@ def main():
     p.add_argument("--group_images", type=int, default=8, help="images whose windows share one forward (8 x 1920x1080 = 32 windows)")
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     p.add_argument("--no_viz", action="store_true", help="counts only, no viz_*.jpg")
+    p.add_argument("--device_prep", action="store_true",
+                   help="hand the decoded uint8 frames to the device and resize them there (countr_amd.frames) instead of with PIL on the host")
     args = p.parse_args()
     args.output_path.mkdir(exist_ok=True, parents=True)
     device = torch.device("cuda")
@@ -76,9 +80,15 @@ def main():
     done = 0
     for g0 in range(0, len(inputs), max(args.group_images, 1)):
         paths = inputs[g0:g0 + max(args.group_images, 1)]
-        loaded = [load_image(pth) for pth in paths]
-        t0 = time.perf_counter()
-        items = [(s.unsqueeze(0).to(device, non_blocking=True), b.unsqueeze(0).to(device), None) for s, b, _w, _h in loaded]
+        if args.device_prep:
+            raw = [np.asarray(Image.open(pth).convert("RGB"), dtype=np.uint8) for pth in paths]      # decoding stays on the host
+            t0 = time.perf_counter()
+            items = frames.prepare_items(device, raw)
+            loaded = [(im[0], None, r.shape[1], r.shape[0]) for (im, _b, _p), r in zip(items, raw)]
+        else:
+            loaded = [load_image(pth) for pth in paths]
+            t0 = time.perf_counter()
+            items = [(s.unsqueeze(0).to(device, non_blocking=True), b.unsqueeze(0).to(device), None) for s, b, _w, _h in loaded]
         results = inference.count_images(model, items, normalization=False)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / len(paths)

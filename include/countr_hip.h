@@ -377,6 +377,30 @@ int countr_window_gather(const void* const* frames, const int* widths, const int
 int countr_window_blend(const float* outs, int n, int nwin, const int* starts, int H, int W, float* dm, float* sums, float* workspace, void* stream);
 int countr_window_blend_blocks(int H, int W);
 
+/* ---- the front of the inference path: raw 8-bit RGB frames and pixel boxes -> the tensors the window path above consumes (additive
+ * exports, no layout change: the ABI version stays 9).
+ * countr_pil_bilinear_tables (HOST only, touches no GPU): the tap tables of Pillow's 8-bit BILINEAR resample of one axis from in_size to
+ *   out_size pixels -- what transforms.Resize does to a PIL image (demo_zero.py:23-38, demo.py:42-49).  Returns the tap stride ksize
+ *   (= 2 ceil(max(in / out, 1)) + 1) and, unless both pointers are NULL (a query), fills bounds int32 [out_size][2] = {first source
+ *   index, tap count} and weights int32 [out_size][ksize] (fixed point, 2^22 = 1.0; entries behind the tap count are 0).  Output pixel =
+ *   clamp((2^21 + sum_j src[first + j] * weights[j]) >> 22, 0, 255); Pillow runs the horizontal pass first, into 8 bits, then the vertical.
+ * countr_frame_resize_u8: n (1..16) frames of ONE size, uint8 [H, W, 3] interleaved on the device (frames / outs: HOST arrays of n
+ *   device pointers, read at call time) -> outs[i] fp32 planar [3, out_h, out_w] = ToTensor(resize(frame)): float(u8) / 255 as a
+ *   correctly rounded division, equal to PIL + ToTensor bit for bit.  hbounds / hweights (W -> out_w) and vbounds / vweights
+ *   (H -> out_h) are DEVICE copies of the tables above, owned by the caller; tmp: device uint8 [n, H, out_w, 3], the intermediate of
+ *   the horizontal pass, caller-owned.  Two launches on `stream` for all n frames.  16-byte loads / stores when the frame and output
+ *   pointers are 16-byte aligned and out_w % 4 == 0, element-wise otherwise.  Fails (no launch) when the taps of one output pixel do
+ *   not fit the 16-KB row staging (in / out above ~2700 in width).
+ * countr_crop_resize_f32: n (1..16) rectangles rects[n][4] = {y1, x1, y2, x2} (HOST array, corners INCLUSIVE, >= 0; clipped to the
+ *   image as img[:, y1:y2 + 1, x1:x2 + 1] clips) of the fp32 planar image img [3, h, w] -> out fp32 [n, 3, oh, ow], bilinear,
+ *   align_corners=False, no antialias -- F.interpolate(crop, size=(oh, ow), mode="bilinear") with torch's fp32 source coordinates:
+ *   the 64 x 64 exemplar crops (demo.py:60-68) and the 3x3 crop-and-upscale for tiny exemplars (:84-99).  A rectangle that is empty
+ *   after clipping is an error, not a launch. */
+int countr_pil_bilinear_tables(int in_size, int out_size, int* bounds, int* weights);
+int countr_frame_resize_u8(const void* const* frames, void* const* outs, int n, int H, int W, int out_h, int out_w,
+                           const int* hbounds, const int* hweights, const int* vbounds, const int* vweights, void* tmp, void* stream);
+int countr_crop_resize_f32(const float* img, int h, int w, const int* rects, int n, int oh, int ow, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
