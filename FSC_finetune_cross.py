@@ -70,6 +70,9 @@ def get_args_parser():
     p.add_argument("--per_rank_shot", action="store_true",
                    help="reference semantics for N > 1: every rank draws its own shot_num per iteration (FSC_finetune_cross.py:276-284; "
                         "default: one draw shared by all ranks)")
+    p.add_argument("--device_aug", action="store_true",
+                   help="train batches from recipes: loader workers decode and draw, the resize / noise / jitter / blur / warp / crop / "
+                        "density / exemplar work runs as HIP kernels on the step's stream (countr_amd/device_aug.py); no host fallback")
     p.add_argument("--log_every", default=50, type=int, help="iterations between loss reports (each report is a host sync)")
     return p
 
@@ -101,12 +104,18 @@ def main(args):
             step.load_scaler_state(ckpt["scaler"])
         print("With optim & sched!")
     from countr_amd.data import fsc147
-    loader = val_loader = None
+    loader = val_loader = device_aug = None
     if args.synthetic_steps <= 0 and fsc147.available(args):
-        ds = fsc147.TrainData(args, split="train", do_aug=args.do_aug)
+        ds = fsc147.TrainData(args, split="train", do_aug=args.do_aug, device_aug=args.device_aug)
         sampler = torch.utils.data.DistributedSampler(ds, num_replicas=misc.get_world_size(), rank=misc.get_rank(), shuffle=True)
-        loader = torch.utils.data.DataLoader(ds, sampler=sampler, batch_size=args.batch_size, num_workers=args.num_workers,
-                                             pin_memory=args.pin_mem, drop_last=True)   # drop_last: the fused step has a static batch
+        if args.device_aug:      # recipes stay a list (frame sizes differ); DeviceAug pins its own upload arena
+            from countr_amd.device_aug import DeviceAug
+            device_aug = DeviceAug(device, batch=args.batch_size, noise_seed=seed)      # noise keyed like the loss mask: args.seed + rank
+            loader = torch.utils.data.DataLoader(ds, sampler=sampler, batch_size=args.batch_size, num_workers=args.num_workers,
+                                                 collate_fn=fsc147.collate_recipes, drop_last=True)
+        else:
+            loader = torch.utils.data.DataLoader(ds, sampler=sampler, batch_size=args.batch_size, num_workers=args.num_workers,
+                                                 pin_memory=args.pin_mem, drop_last=True)   # drop_last: the fused step has a static batch
         n_iter = len(loader)
         dsv = fsc147.TrainData(args, split="val", do_aug=False)                         # :146-155, :185-191
         vsampler = torch.utils.data.DistributedSampler(dsv, num_replicas=misc.get_world_size(), rank=misc.get_rank(), shuffle=True)
@@ -130,6 +139,8 @@ def main(args):
         train_acc = torch.zeros(2, dtype=torch.float64, device=device)
         if loader is not None:
             loader.sampler.set_epoch(epoch)                                             # :260-261
+            if device_aug is not None:
+                loader.dataset.set_epoch(epoch)      # the epoch enters the noise counters (before the workers copy the dataset)
         it_data = iter(loader) if loader is not None else None
         # the loop's own device work (mask draw, error sums) runs on the step's stream: from another stream every step pays two
         # cross-queue hand-overs (inputs ready -> step, step done -> caller), ~50 us of idle GPU per step on MI355X
@@ -139,11 +150,18 @@ def main(args):
         def fetch(it):
             if it >= n_iter:
                 return None
+            if it_data is not None and device_aug is not None:
+                # recipes -> device tensors on the step's stream, in the tuple layout of the host loader; m_flag stays on the host
+                recipes = next(it_data)
+                d_imgs, d_boxes, d_gt, m_flags = device_aug.batch(recipes)
+                return d_imgs, d_gt, None, d_boxes, None, m_flags, None
             if it_data is not None:
                 return next(it_data)
             return make_batch(B, shots=3, seed=seed * 100003 + epoch * n_iter + it, device=device)
-        ahead = fetch(0)
+        ahead = fetch(0) if device_aug is None else None
         with step.on_stream():
+            if device_aug is not None:
+                ahead = fetch(0)                 # DeviceAug's kernels belong on the step's stream
             for it in range(n_iter):
                 if it % args.accum_iter == 0:                                               # :270-271 (per accumulation window)
                     lr = lr_sched.adjust_learning_rate(None, it / n_iter + epoch, args)

@@ -1,4 +1,4 @@
-"""CounTR on the MI355X.  The raw-frame entry points are re-exported here; they load on first use so that `import countr_amd` (the
+"""CounTR on the MI355X.  The raw-frame entry points and the device augmentation are re-exported here; they load on first use so that `import countr_amd` (the
 build, the CPU tools) stays free of torch."""
 
 
@@ -6,4 +6,7 @@ def __getattr__(name):
     if name in ("count_frames", "FramePrep"):
         from . import frames
         return getattr(frames, name)
+    if name == "DeviceAug":
+        from . import device_aug
+        return device_aug.DeviceAug
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

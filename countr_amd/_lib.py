@@ -41,6 +41,23 @@ class GemmArgs(C.Structure):
     ]
 
 
+class AugImage(C.Structure):
+    """countr_aug_image of include/countr_hip.h: one image of a device-augmentation batch (csrc/augment.hip)."""
+    _fields_ = [
+        ("src", C.c_void_p), ("jit", C.c_void_p), ("blr", C.c_void_p), ("noise", C.c_void_p), ("win", C.c_void_p),
+        ("counter", C.c_uint64),
+        ("brightness", C.c_double), ("contrast", C.c_double), ("saturation", C.c_double), ("hue", C.c_double),
+        ("affine", C.c_double * 6),
+        ("kx", C.c_float * 7), ("ky", C.c_float * 9),
+        ("h", C.c_int), ("w", C.c_int), ("win_h", C.c_int), ("win_w", C.c_int),
+        ("nops", C.c_int), ("order", C.c_int * 4),
+        ("noise_mode", C.c_int), ("win_mode", C.c_int), ("flip", C.c_int), ("start_h", C.c_int), ("start_w", C.c_int),
+        ("rects", C.c_int * 12),
+        ("cell_off", C.c_int), ("cell_cnt", C.c_int),
+    ]
+
+
+AUG_MAX_IMAGES = 32
 _libs = {}
 
 
@@ -141,6 +158,13 @@ _SIGS = {
     "countr_pil_bilinear_tables": [_i, _i, _vp, _vp],
     "countr_frame_resize_u8": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "countr_crop_resize_f32": [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp],
+    "countr_aug_normal": [_vp, _i64, _f, C.c_uint64, C.c_uint64, _vp],
+    "countr_aug_partials_floats": [_i],
+    "countr_aug_jitter": [_vp, _i, C.c_uint64, _vp, _vp],
+    "countr_aug_blur": [_vp, _i, _vp],
+    "countr_aug_window": [_vp, _i, _vp, _vp],
+    "countr_aug_density": [_vp, _i, _vp, _i, _vp, _vp],
+    "countr_aug_exemplars": [_vp, _i, _vp, _vp],
     "countr_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp],
 }
 _RESTYPES = {"countr_xattn_bwd_workspace_floats": C.c_int64, "countr_groupnorm_bwd_image_sums_offset": C.c_int64}

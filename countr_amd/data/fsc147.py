@@ -13,6 +13,16 @@ Augmentation branch (util/FSC147.py:130-253).  What is pinned against the refere
     semantics with this module's own parameter draws (same distributions, not the same random streams): "parity unpinned" for
     those three ops -- neither library is installed, so no reference output exists to compare with.
 
+Device augmentation (TrainData(..., device_aug=True), recipe_train below): the loader worker only decodes the frame, makes the draws
+and works out the few hundred dot cells; the pixel-rate work -- resize, noise, jitter, blur, warp, flip, crop, density filter, exemplar
+crops -- runs as HIP kernels in the main process (countr_amd/device_aug.py, csrc/augment.hip) with transform_train_aug /
+transform_train_noaug as their oracle.  The draws from the `random` module keep their order (mosaic coin, flip coin, then the mosaic's
+draws or the two crop starts), so for one random.Random(seed) both paths agree on which samples are mosaics, on the flip, on the crop
+and on the whole mosaic output.  The jitter / blur / affine parameters keep their distributions (AugParams).  The Gaussian noise keeps
+its distribution, N(0, 0.1^2) per element, but comes from a counter-based stream on the device -- Philox4x32-10 + Box-Muller keyed by
+(args.seed + rank, sample counter), include/countr_hip.h -- instead of np.random: the same stance as for the three third-party ops.
+A mosaic sample is finished on the host by mosaic(), but no longer pays for the noise / jitter / blur / warp chain it throws away.
+
 PIL's Image.resize(BILINEAR / BICUBIC) is what torchvision.transforms.Resize calls for PIL inputs; exemplar crops are resized
 as TENSORS by the reference (torchvision 0.14.1: bilinear, no antialias) == F.interpolate(mode="bilinear", align_corners=False)."""
 import json
@@ -327,6 +337,74 @@ def transform_train_aug(image, rects, dots, im_id, ctx, rng=random, nprng=np.ran
     return {"image": out_img.contiguous().float(), "boxes": boxes, "pos": torch.tensor([]), "gt_density": out_dens, "m_flag": m_flag}
 
 
+def scaled_rects(rects, sh, sw, limit=3):
+    """The exemplar rectangles as exemplar_crops scales them: [(y1, x1, y2, x2), ...], corners inclusive."""
+    out = []
+    for box in rects[:limit]:
+        b = [int(k) for k in box]
+        out.append((int(b[0] * sh), int(b[1] * sw), int(b[2] * sh), int(b[3] * sw)))
+    return out
+
+
+def _cells_array(cells):
+    """Sorted, duplicate-free int32 [n, 2] of (row, col)."""
+    return np.array(sorted(set(cells)), dtype=np.int32).reshape(-1, 2)
+
+
+def recipe_train(image, rects, dots, im_id, ctx, do_aug=True, rng=random, nprng=np.random, params=None, noise_counter=0):
+    """What a loader worker hands over with device_aug: the decoded frame, every decision of transform_train_aug (do_aug) or
+    transform_train_noaug taken with the same draws from `rng` in the same order, and the final dot cells -- (row, col) of every dot
+    of the 384 x 384 target after scaling, the affine map, int() truncation, the drop rule, the flip and the crop, in float64 exactly
+    as the host transform places them.  kind: "aug" (the device runs the chain), "plain" (resize + crop) or "mosaic" (image and dot
+    map finished here by mosaic(); the chain the mosaic branch discards is not computed)."""
+    W, H = image.size
+    new_h, new_w = flex_resize(H, W)
+    sh, sw = float(new_h) / H, float(new_w) / W
+    rec = {"frame": torch.from_numpy(np.asarray(image, dtype=np.uint8).copy()), "new_h": new_h, "new_w": new_w,
+           "rects": scaled_rects(rects, sh, sw), "m_flag": 0, "im_id": im_id, "n_dots": len(dots)}
+    if not do_aug:
+        rng.random()                                   # the mosaic coin, drawn and ignored (transform_train_noaug)
+        start = rng.randint(0, new_w - MAX_HW)
+        cells = []
+        for d in dots:
+            y, x = _scaled_dot(d, sh, sw, new_h, new_w)
+            if y < MAX_HW and start <= x < start + MAX_HW:
+                cells.append((y, x - start))
+        rec.update(kind="plain", start_h=0, start_w=start, cells=_cells_array(cells))
+        return rec
+    mosaic_flag = rng.random() < 0.25
+    pr = None if mosaic_flag else (params or AugParams(nprng))
+    flip = rng.random() > 0.5
+    if mosaic_flag:
+        from PIL import Image
+        img_t = to_tensor(image.resize((new_w, new_h), Image.BILINEAR))
+        out_img, out_dens, m_flag = mosaic(img_t, dots, sh, sw, im_id, ctx, rng)
+        rec.update(kind="mosaic", flip=bool(flip), m_flag=m_flag, image=out_img.contiguous().float(), dens=out_dens,
+                   cells=np.argwhere(out_dens.numpy() != 0).astype(np.int32).reshape(-1, 2))
+        return rec
+    start_w = rng.randint(0, new_w - 1 - 383)
+    start_h = rng.randint(0, new_h - 1 - 383)
+    M = affine_matrix(new_h, new_w, pr.rotate, pr.scale, pr.shear, pr.tx, pr.ty)
+    cells = []
+    for d in dots:
+        y, x = _scaled_dot(d, sh, sw, new_h, new_w)
+        xa, ya, _ = M @ np.array([x, y, 1.0])
+        if 0 <= xa < new_w and 0 <= ya < new_h:
+            r, c = int(ya), int(xa)
+            if flip:
+                c = new_w - 1 - c
+            if start_h <= r < start_h + MAX_HW and start_w <= c < start_w + MAX_HW:
+                cells.append((r - start_h, c - start_w))
+    rec.update(kind="aug", params=pr, noise_counter=int(noise_counter), flip=bool(flip), start_h=start_h, start_w=start_w,
+               cells=_cells_array(cells))
+    return rec
+
+
+def collate_recipes(batch):
+    """collate_fn of the device_aug train loader: the recipes stay a list (frame sizes differ)."""
+    return list(batch)
+
+
 def transform_val(image, rects, dots):
     """ResizeValImage.__call__ (util/FSC147.py:316-366): 384x384, gaussian sigma 4 radius 7, x60."""
     from PIL import Image
@@ -453,8 +531,11 @@ class TrainData(Dataset):
     default) the train split goes through transform_train_aug; it needs args.class_file (ImageClasses_FSC147.txt) for the
     cross-image mosaic, as util/FSC147.py:35-41 does."""
 
-    def __init__(self, args, split="train", do_aug=True):
+    def __init__(self, args, split="train", do_aug=True, device_aug=False):
         anno, split_file, self.im_dir = _paths(args)
+        # device_aug: train items are recipes (recipe_train) for countr_amd.device_aug.DeviceAug; use collate_fn=collate_recipes
+        self.device_aug = bool(device_aug) and split == "train"
+        self.epoch = 0
         self.annotations = json.load(open(anno))
         splits = json.load(open(split_file))
         self.img = list(splits[split])
@@ -490,12 +571,23 @@ class TrainData(Dataset):
     def __len__(self):
         return len(self.img)
 
+    def set_epoch(self, epoch):
+        """device_aug: the epoch enters the noise counters (call before the epoch's iterator is made, as sampler.set_epoch is)."""
+        self.epoch = int(epoch)
+
+    def noise_counter(self, idx):
+        """64-bit counter of sample idx in the current epoch: unique per (epoch, sample), and the same again in a resumed run."""
+        return self.epoch * len(self.img) + int(idx)
+
     def __getitem__(self, idx):
         im_id = self.img[idx]
         anno = self.annotations[im_id]
         dots = np.array(anno["points"])
         rects = [[b[0][1], b[0][0], b[2][1], b[2][0]] for b in anno["box_examples_coordinates"]]
         image = self.open_image(im_id)
+        if self.device_aug:
+            return recipe_train(image, rects, dots, im_id, self, do_aug=self.do_aug, nprng=self._worker_nprng() if self.do_aug else None,
+                                noise_counter=self.noise_counter(idx))
         if self.split != "train":
             s = transform_val(image, rects, dots)
         elif self.do_aug:

@@ -401,6 +401,64 @@ int countr_frame_resize_u8(const void* const* frames, void* const* outs, int n, 
                            const int* hbounds, const int* hweights, const int* vbounds, const int* vweights, void* tmp, void* stream);
 int countr_crop_resize_f32(const float* img, int h, int w, const int* rects, int n, int oh, int ow, float* out, void* stream);
 
+/* ---- train-time augmentation of the finetuning loader on the device (csrc/augment.hip; additive exports, the ABI version stays 9).
+ * The oracle of every call is the named host function of countr_amd/data/fsc147.py (transform_train_aug and its parts).  All images are
+ * fp32 planar [3, h, w] on the device; `imgs` is a HOST array of n (1..COUNTR_AUG_MAX_IMAGES) descriptors read at call time, one per
+ * image of the batch, sizes free per image; every call is a fixed number of launches on `stream` whatever n is, and allocates nothing.
+ * 16-byte accesses where a buffer is 16-byte aligned and h * w (jitter) / w (blur) is a multiple of 4, element-wise otherwise.
+ * Each call reads only the descriptor fields named for it. */
+#define COUNTR_AUG_MAX_IMAGES 32
+typedef struct countr_aug_image {
+  const float* src;      /* the clean resized frame (countr_frame_resize_u8): input of the jitter, source of the exemplars */
+  float* jit;            /* output of countr_aug_jitter, input of countr_aug_blur */
+  float* blr;            /* output of countr_aug_blur (a buffer of its own) */
+  const float* noise;    /* noise_mode 2: an explicit noise image [3, h, w], added as it is (already scaled by 0.1) */
+  const float* win;      /* input of countr_aug_window, [3, win_h, win_w] */
+  uint64_t counter;      /* noise_mode 1: this image's noise counter */
+  double brightness, contrast, saturation, hue;   /* color_jitter's factors (hue: the shift); rounded to fp32 as torch rounds a Python float */
+  double affine[6];      /* win_mode 1: output pixel (y, x) of the warp samples (row, col) = (affine[2] + y affine[0] + x affine[1],
+                            affine[5] + y affine[3] + x affine[4]) -- matrix rows and offset as warp_affine hands them to scipy */
+  float kx[7], ky[9];    /* normalised blur weights along x and y (gaussian_blur's k1d) */
+  int h, w;              /* size of src / jit / blr */
+  int win_h, win_w;      /* size of win */
+  int nops, order[4];    /* the first nops (0..4) entries of order run: 0 brightness, 1 contrast, 2 saturation, 3 hue, each at most once */
+  int noise_mode;        /* 0 none, 1 generator, 2 explicit */
+  int win_mode;          /* 0 copy, 1 affine warp (bilinear, zero outside) */
+  int flip;              /* != 0: the window is cut from the horizontally flipped image */
+  int start_h, start_w;  /* first row / column of the 384 x 384 window */
+  int rects[12];         /* three exemplar rectangles {y1, x1, y2, x2} of src, corners inclusive (countr_crop_resize_f32's convention) */
+  int cell_off, cell_cnt;/* this image's range of the cell list of countr_aug_density */
+} countr_aug_image;
+/* The normal stream.  Element e of stream (seed, counter): g = e / 4, j = e % 4, (r0, r1, r2, r3) = Philox4x32-10(counter = (g, 1,
+ * counter lo, counter hi), key = (seed lo, seed hi)) -- counter word 1 is 1 where the loss mask of countr_step_prologue uses 0, so the
+ * two stay disjoint under one seed.  Box-Muller in fp32 on (a, b) = (r0, r1) for j = 0, 1 and (r2, r3) for j = 2, 3:
+ * u1 = ((a >> 9) + 1) 2^-23 in (0, 1], u2 = (b >> 8) 2^-24 in [0, 1) (both exact), rad = sqrtf(-2 logf(u1)),
+ * z = rad * cos(2 pi u2) for even j, rad * sin(2 pi u2) for odd j (sincospif(2 u2)).
+ * countr_aug_normal: out[e] = scale * z[e] for e < n.  An image's noise is 0.1f * z[e], e its index in the flattened [3, h, w]. */
+int countr_aug_normal(float* out, int64_t n, float scale, uint64_t seed, uint64_t counter, void* stream);
+/* countr_aug_jitter: jit <- color_jitter(clamp(src + noise, 0, 1), order[:nops], ...) (noise_mode 0: no noise, no clamp).  _blend clamps
+ * after every op; the contrast op blends with the mean of _gray over the whole image at that point of the chain: launch 1 runs the noise
+ * and the ops in front of it and leaves 128 partial sums per image in `partials` (fp32 [countr_aug_partials_floats(n)]), launch 2 adds
+ * them in one fixed order and runs the rest in place (skipped when no image has a contrast op).  Bit-reproducible. */
+int countr_aug_partials_floats(int n);
+int countr_aug_jitter(const countr_aug_image* imgs, int n, uint64_t seed, float* partials, void* stream);
+/* countr_aug_blur: blr <- gaussian_blur(jit, (7, 9), sigma) with the caller's weights: 7 taps along x, then 9 along y, reflect padding
+ * that does not repeat the edge pixel.  One launch. */
+int countr_aug_blur(const countr_aug_image* imgs, int n, void* stream);
+/* countr_aug_window: out [n, 3, 384, 384] (16-byte aligned) <- rows start_h.., columns start_w.. of win (win_mode 0), or of
+ * warp_affine(win) = scipy.ndimage.affine_transform(order=1, mode="constant", cval=0) (win_mode 1), flipped left-right first when flip
+ * is set.  The source coordinate is computed in double as scipy does; a coordinate strictly outside [0, size - 1] on either axis
+ * gives 0.  The window must lie inside win_h x win_w.  One launch; the full warp is never stored. */
+int countr_aug_window(const countr_aug_image* imgs, int n, float* out, void* stream);
+/* countr_aug_density: out [n, 384, 384] (16-byte aligned) <- 60 * scipy.ndimage.gaussian_filter(dot map, sigma=(1, 1)) where the dot
+ * map of image i is 1 at the cells cells[cell_off .. cell_off + cell_cnt) and 0 elsewhere; a cell is (row << 16) | col, row and col
+ * < 384 (others are ignored), duplicates allowed.  cells: DEVICE int32 [ncells].  Radius 4, weights exp(-x^2 / 2) normalised in
+ * double, mode "reflect" (the edge sample repeats), axis 0 into an fp32 intermediate, then axis 1.  One launch. */
+int countr_aug_density(const countr_aug_image* imgs, int n, const int* cells, int ncells, float* out, void* stream);
+/* countr_aug_exemplars: out [n, 3, 3, 64, 64] (16-byte aligned) <- the three rectangles of every src, each resized as
+ * countr_crop_resize_f32 resizes it (same arithmetic), in one launch for the batch. */
+int countr_aug_exemplars(const countr_aug_image* imgs, int n, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
