@@ -73,11 +73,17 @@ def get_args_parser():
     p.add_argument("--device_aug", action="store_true",
                    help="train batches from recipes: loader workers decode and draw, the resize / noise / jitter / blur / warp / crop / "
                         "density / exemplar work runs as HIP kernels on the step's stream (countr_amd/device_aug.py); no host fallback")
+    p.add_argument("--device_mosaic", action="store_true",
+                   help="with --device_aug and --do_aug: the mosaic samples are built on the device too -- the workers hand over the "
+                        "draws and the decoded frames of the four pieces, one more HIP kernel crops, resizes and cross-fades them "
+                        "(csrc/mosaic.hip)")
     p.add_argument("--log_every", default=50, type=int, help="iterations between loss reports (each report is a host sync)")
     return p
 
 
 def main(args):
+    if args.device_mosaic and not (args.device_aug and args.do_aug):
+        raise SystemExit("--device_mosaic needs --device_aug and --do_aug: it moves the mosaic of the device augmentation to the GPU")
     misc.init_distributed_mode(args)
     device = torch.device("cuda", args.gpu)
     torch.cuda.set_device(device)
@@ -106,7 +112,7 @@ def main(args):
     from countr_amd.data import fsc147
     loader = val_loader = device_aug = None
     if args.synthetic_steps <= 0 and fsc147.available(args):
-        ds = fsc147.TrainData(args, split="train", do_aug=args.do_aug, device_aug=args.device_aug)
+        ds = fsc147.TrainData(args, split="train", do_aug=args.do_aug, device_aug=args.device_aug, device_mosaic=args.device_mosaic)
         sampler = torch.utils.data.DistributedSampler(ds, num_replicas=misc.get_world_size(), rank=misc.get_rank(), shuffle=True)
         if args.device_aug:      # recipes stay a list (frame sizes differ); DeviceAug pins its own upload arena
             from countr_amd.device_aug import DeviceAug

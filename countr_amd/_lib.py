@@ -57,6 +57,16 @@ class AugImage(C.Structure):
     ]
 
 
+class MosaicPiece(C.Structure):
+    """countr_mosaic_piece: one quadrant source of a device mosaic (csrc/mosaic.hip)."""
+    _fields_ = [("src", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("start_h", C.c_int), ("start_w", C.c_int), ("length", C.c_int)]
+
+
+class MosaicImage(C.Structure):
+    """countr_mosaic_image: the four pieces, the cross-fade half width and the batch row of one mosaic."""
+    _fields_ = [("piece", MosaicPiece * 4), ("bl", C.c_int), ("row", C.c_int)]
+
+
 AUG_MAX_IMAGES = 32
 _libs = {}
 
@@ -165,6 +175,7 @@ _SIGS = {
     "countr_aug_window": [_vp, _i, _vp, _vp],
     "countr_aug_density": [_vp, _i, _vp, _i, _vp, _vp],
     "countr_aug_exemplars": [_vp, _i, _vp, _vp],
+    "countr_aug_mosaic": [_vp, _i, _vp, _i, _vp],
     "countr_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp],
 }
 _RESTYPES = {"countr_xattn_bwd_workspace_floats": C.c_int64, "countr_groupnorm_bwd_image_sums_offset": C.c_int64}

@@ -21,7 +21,9 @@ draws or the two crop starts), so for one random.Random(seed) both paths agree o
 and on the whole mosaic output.  The jitter / blur / affine parameters keep their distributions (AugParams).  The Gaussian noise keeps
 its distribution, N(0, 0.1^2) per element, but comes from a counter-based stream on the device -- Philox4x32-10 + Box-Muller keyed by
 (args.seed + rank, sample counter), include/countr_hip.h -- instead of np.random: the same stance as for the three third-party ops.
-A mosaic sample is finished on the host by mosaic(), but no longer pays for the noise / jitter / blur / warp chain it throws away.
+A mosaic sample is finished on the host by mosaic(), but no longer pays for the noise / jitter / blur / warp chain it throws away;
+with device_mosaic=True the worker only makes the mosaic's draws and dot cells (mosaic_plan) and hands over the decoded frames of the
+pieces: the crops, their resize and the cross-fades run in countr_aug_mosaic (csrc/mosaic.hip) with mosaic() as the oracle.
 
 PIL's Image.resize(BILINEAR / BICUBIC) is what torchvision.transforms.Resize calls for PIL inputs; exemplar crops are resized
 as TENSORS by the reference (torchvision 0.14.1: bilinear, no antialias) == F.interpolate(mode="bilinear", align_corners=False)."""
@@ -351,16 +353,78 @@ def _cells_array(cells):
     return np.array(sorted(set(cells)), dtype=np.int32).reshape(-1, 2)
 
 
-def recipe_train(image, rects, dots, im_id, ctx, do_aug=True, rng=random, nprng=np.random, params=None, noise_counter=0):
+def _frame_of(image):
+    return torch.from_numpy(np.asarray(image, dtype=np.uint8).copy())
+
+
+def mosaic_plan(frame, dots, sh, sw, new_h, new_w, im_id, ctx, rng):
+    """mosaic() without its pixel work: the same draws from `rng` in the same order, and the dot cells of the map it would return
+    -> (frames, frame ids, bl, pieces, cells, m_flag).  frames: the distinct decoded uint8 [H, W, 3] frames the pieces are cut
+    from, the sample's own first (also when no quadrant shows it); a foreign image is decoded once however often it is drawn.
+    pieces: (frame index, new_h, new_w, start_h, start_w, length) of quadrants 0..3, sizes and starts on the frame's flex_resize'd
+    image.  cells: sorted int32 [n, 2] (row, col) of the 384 x 384 dot map -- a dot of piece k lands where _mosaic_piece puts it on
+    the resize_l grid and is kept when it lies in the piece's 192 x 192 core, which quadrant k of the map shows."""
+    bl = rng.randint(10, 20)
+    resize_l = 192 + 2 * bl
+    frames, ids = [frame], [im_id]
+    sizes = {im_id: (int(frame.shape[0]), int(frame.shape[1]), new_h, new_w)}       # (H, W, flex_resize(H, W)) per decoded image
+    pieces, cells, m_flag = [], [], 0
+
+    def place(q, t_dots, t_sh, t_sw, th, tw, length, start_w, start_h):
+        for d in t_dots:
+            y, x = _scaled_dot(d, t_sh, t_sw, th, tw)
+            if start_h <= y < start_h + length and start_w <= x < start_w + length:
+                r = min(resize_l - 1, int((y - start_h) * resize_l / length))
+                c = min(resize_l - 1, int((x - start_w) * resize_l / length))
+                if bl <= r < resize_l - bl and bl <= c < resize_l - bl:
+                    cells.append((r - bl + 192 * (q % 2), c - bl + 192 * (q // 2)))
+
+    if dots.shape[0] >= 70:
+        for q in range(4):
+            length = rng.randint(150, 384)
+            start_w = rng.randint(0, new_w - length)
+            start_h = rng.randint(0, new_h - length)
+            pieces.append((0, new_h, new_w, start_h, start_w, length))
+            place(q, dots, sh, sw, new_h, new_w, length, start_w, start_h)
+    else:
+        m_flag = 1
+        prob = rng.random()
+        gt_pos = rng.randint(0, 3) if prob > 0.25 else rng.randint(0, 4)
+        for q in range(4):
+            if q == gt_pos:
+                t_id, t_dots, t_sh, t_sw, th, tw = im_id, dots, sh, sw, new_h, new_w
+            else:
+                t_id = ctx.train_set[rng.randint(0, len(ctx.train_set) - 1)]
+                t_dots = np.array(ctx.annotations[t_id]["points"])
+                if t_id not in sizes:
+                    timage = ctx.open_image(t_id)
+                    sizes[t_id] = (timage.size[1], timage.size[0]) + flex_resize(timage.size[1], timage.size[0])
+                    frames.append(_frame_of(timage))
+                    ids.append(t_id)
+                H, W, th, tw = sizes[t_id]
+                t_sw, t_sh = float(tw) / W, float(th) / H
+            length = rng.randint(250, 384)
+            start_w = rng.randint(0, tw - length)
+            start_h = rng.randint(0, th - length)
+            pieces.append((ids.index(t_id), th, tw, start_h, start_w, length))
+            if ctx.class_dict[im_id] == ctx.class_dict[t_id]:
+                place(q, t_dots, t_sh, t_sw, th, tw, length, start_w, start_h)
+    return frames, ids, bl, pieces, _cells_array(cells), m_flag
+
+
+def recipe_train(image, rects, dots, im_id, ctx, do_aug=True, rng=random, nprng=np.random, params=None, noise_counter=0,
+                 device_mosaic=False):
     """What a loader worker hands over with device_aug: the decoded frame, every decision of transform_train_aug (do_aug) or
     transform_train_noaug taken with the same draws from `rng` in the same order, and the final dot cells -- (row, col) of every dot
     of the 384 x 384 target after scaling, the affine map, int() truncation, the drop rule, the flip and the crop, in float64 exactly
     as the host transform places them.  kind: "aug" (the device runs the chain), "plain" (resize + crop) or "mosaic" (image and dot
-    map finished here by mosaic(); the chain the mosaic branch discards is not computed)."""
+    map finished here by mosaic(); the chain the mosaic branch discards is not computed).  With device_mosaic a mosaic sample is
+    "mosaic_dev": no pixel work here, only mosaic_plan's draws and cells and the decoded frames of the pieces (frames, frame_ids,
+    bl, pieces; frame stays the sample's own frame, frames[0], the source of the exemplars) -- countr_aug_mosaic builds the image."""
     W, H = image.size
     new_h, new_w = flex_resize(H, W)
     sh, sw = float(new_h) / H, float(new_w) / W
-    rec = {"frame": torch.from_numpy(np.asarray(image, dtype=np.uint8).copy()), "new_h": new_h, "new_w": new_w,
+    rec = {"frame": _frame_of(image), "new_h": new_h, "new_w": new_w,
            "rects": scaled_rects(rects, sh, sw), "m_flag": 0, "im_id": im_id, "n_dots": len(dots)}
     if not do_aug:
         rng.random()                                   # the mosaic coin, drawn and ignored (transform_train_noaug)
@@ -375,6 +439,10 @@ def recipe_train(image, rects, dots, im_id, ctx, do_aug=True, rng=random, nprng=
     mosaic_flag = rng.random() < 0.25
     pr = None if mosaic_flag else (params or AugParams(nprng))
     flip = rng.random() > 0.5
+    if mosaic_flag and device_mosaic:
+        frames, ids, bl, pieces, cells, m_flag = mosaic_plan(rec["frame"], dots, sh, sw, new_h, new_w, im_id, ctx, rng)
+        rec.update(kind="mosaic_dev", flip=bool(flip), m_flag=m_flag, frames=frames, frame_ids=ids, bl=bl, pieces=pieces, cells=cells)
+        return rec
     if mosaic_flag:
         from PIL import Image
         img_t = to_tensor(image.resize((new_w, new_h), Image.BILINEAR))
@@ -531,10 +599,13 @@ class TrainData(Dataset):
     default) the train split goes through transform_train_aug; it needs args.class_file (ImageClasses_FSC147.txt) for the
     cross-image mosaic, as util/FSC147.py:35-41 does."""
 
-    def __init__(self, args, split="train", do_aug=True, device_aug=False):
+    def __init__(self, args, split="train", do_aug=True, device_aug=False, device_mosaic=False):
+        if device_mosaic and not (device_aug and do_aug):
+            raise ValueError("device_mosaic needs device_aug and do_aug: the mosaic belongs to the augmented recipe loader")
         anno, split_file, self.im_dir = _paths(args)
         # device_aug: train items are recipes (recipe_train) for countr_amd.device_aug.DeviceAug; use collate_fn=collate_recipes
         self.device_aug = bool(device_aug) and split == "train"
+        self.device_mosaic = bool(device_mosaic) and self.device_aug      # mosaic samples as "mosaic_dev" recipes (recipe_train)
         self.epoch = 0
         self.annotations = json.load(open(anno))
         splits = json.load(open(split_file))
@@ -587,7 +658,7 @@ class TrainData(Dataset):
         image = self.open_image(im_id)
         if self.device_aug:
             return recipe_train(image, rects, dots, im_id, self, do_aug=self.do_aug, nprng=self._worker_nprng() if self.do_aug else None,
-                                noise_counter=self.noise_counter(idx))
+                                noise_counter=self.noise_counter(idx), device_mosaic=self.device_mosaic)
         if self.split != "train":
             s = transform_val(image, rects, dots)
         elif self.do_aug:

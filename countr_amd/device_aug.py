@@ -9,7 +9,13 @@ boxes [B, 3, 3, 64, 64], gt [B, 384, 384], fp32 -- with HIP kernels on the curre
 
 Plain recipes (--no_do_aug) skip the middle (the window is cut from the clean frame), mosaic recipes upload the image the host's
 mosaic() finished.  One host-to-device copy and seven launches per batch plus two per distinct frame size for the resize (batches
-above 32 images go in groups of 32).  There is no host fallback."""
+above 32 images go in groups of 32).  There is no host fallback.
+
+"mosaic_dev" recipes (TrainData(..., device_mosaic=True)) bring the decoded frames of their four pieces and the draws instead of a
+finished image: every frame is uploaded and resized with the others (frames of one size share a launch pair), and one more launch,
+countr_aug_mosaic (csrc/mosaic.hip), crops, resizes and cross-fades the pieces straight into imgs[b].  The window launch still writes
+such a row first (a plain crop of the sample's own clean frame, so that its table stays one entry per batch row); the mosaic launch
+follows it on the same stream and overwrites the row."""
 import ctypes as C
 
 import numpy as np
@@ -116,6 +122,27 @@ class DeviceAug:
             setattr(self, name, t)
         return t
 
+    @staticmethod
+    def _frame(fr):
+        fr = fr.numpy() if isinstance(fr, torch.Tensor) else np.asarray(fr)
+        if fr.dtype != np.uint8 or fr.ndim != 3 or fr.shape[2] != 3:
+            raise ValueError("DeviceAug.batch: frames are uint8 [H, W, 3]")
+        return fr
+
+    @staticmethod
+    def _mosaic_entry(row, r, clean_of):
+        """countr_mosaic_image of mosaic_dev recipe r for batch row `row`; clean_of(k) -> (device address, (h, w)) of its frame k."""
+        m = _lib.MosaicImage()
+        m.bl, m.row = int(r["bl"]), row
+        if len(r["pieces"]) != 4:
+            raise ValueError("DeviceAug.batch: a mosaic_dev recipe has four pieces")
+        for q, (k, nh, nw, start_h, start_w, length) in zip(m.piece, r["pieces"]):
+            ptr, (h, w) = clean_of(int(k))
+            if (h, w) != (int(nh), int(nw)):
+                raise ValueError("DeviceAug.batch: piece of %s drawn on %d x %d, its frame resizes to %d x %d" % (r["im_id"], nh, nw, h, w))
+            q.src, q.h, q.w, q.start_h, q.start_w, q.length = ptr, h, w, int(start_h), int(start_w), int(length)
+        return m
+
     def batch(self, recipes, noise=None):
         """recipes: a list of fsc147.recipe_train results -> (imgs [B, 3, 384, 384], boxes [B, 3, 3, 64, 64], gt [B, 384, 384],
         m_flags [B] (a host list)).  noise: None (the generator: Philox stream (noise_seed, recipe counter)) or a list with, per
@@ -135,10 +162,21 @@ class DeviceAug:
                 cur.wait_event(self._last[1])
             self.launches = 0
             # ---- one upload: frames (16-byte aligned each), mosaic images, explicit noise, dot cells
-            off, f_off, m_off, n_off = 0, [], {}, {}
+            # frames: slot i < B is recipe i's own frame, the foreign frames of the mosaic_dev recipes follow
+            frames = [self._frame(r["frames"][0] if r["kind"] == "mosaic_dev" else r["frame"]) for r in recipes]
+            shapes = [(r["new_h"], r["new_w"]) for r in recipes]
+            slot_of = {}                                   # (recipe, index in its frames) -> slot
             for i, r in enumerate(recipes):
+                if r["kind"] == "mosaic_dev":
+                    slot_of[(i, 0)] = i
+                    for k in range(1, len(r["frames"])):
+                        slot_of[(i, k)] = len(frames)
+                        frames.append(self._frame(r["frames"][k]))
+                        shapes.append(fsc147.flex_resize(frames[-1].shape[0], frames[-1].shape[1]))
+            off, f_off, m_off, n_off = 0, [], {}, {}
+            for fr in frames:
                 f_off.append(off)
-                off += _pad16(r["frame"].numel())
+                off += _pad16(fr.size)
             for i, r in enumerate(recipes):
                 if r["kind"] == "mosaic":
                     m_off[i] = off
@@ -153,12 +191,9 @@ class DeviceAug:
             stage.reserve(off)
             hb = stage.host.numpy()
             cell_rng, k = [], 0
+            for s, fr in enumerate(frames):
+                hb[f_off[s]:f_off[s] + fr.size] = fr.reshape(-1)
             for i, r in enumerate(recipes):
-                fr = r["frame"]
-                fr = fr.numpy() if isinstance(fr, torch.Tensor) else np.asarray(fr)
-                if fr.dtype != np.uint8 or fr.ndim != 3 or fr.shape[2] != 3:
-                    raise ValueError("DeviceAug.batch: frames are uint8 [H, W, 3]")
-                hb[f_off[i]:f_off[i] + fr.size] = fr.reshape(-1)
                 if i in m_off:
                     hb[m_off[i]:m_off[i] + 3 * OUT * OUT * 4].view(np.float32)[:] = r["image"].numpy().reshape(-1)
                 if i in n_off:
@@ -175,16 +210,16 @@ class DeviceAug:
             stage.upload(off)
             base = stage.dev.data_ptr()
             # ---- workspaces: clean / ping / pong hold every image of the batch back to back (sizes padded to 16 bytes)
-            sizes = [_pad4(3 * r["new_h"] * r["new_w"]) for r in recipes]
+            # (only the B own frames can go through the chain: ping / pong end where the foreign frames begin)
+            sizes = [_pad4(3 * nh * nw) for nh, nw in shapes]
             w_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-            total = int(w_off[-1])
-            clean = self._grow("_clean", total, torch.float32)
-            ping = self._grow("_ping", total, torch.float32)
-            pong = self._grow("_pong", total, torch.float32)
+            clean = self._grow("_clean", int(w_off[-1]), torch.float32)
+            ping = self._grow("_ping", int(w_off[B]), torch.float32)
+            pong = self._grow("_pong", int(w_off[B]), torch.float32)
             # ---- resize + ToTensor: frames of one (H, W) share a launch pair
             by_shape = {}
-            for i, r in enumerate(recipes):
-                by_shape.setdefault((int(r["frame"].shape[0]), int(r["frame"].shape[1]), r["new_h"], r["new_w"]), []).append(i)
+            for s, fr in enumerate(frames):
+                by_shape.setdefault((int(fr.shape[0]), int(fr.shape[1])) + tuple(shapes[s]), []).append(s)
             need = max(min(len(ix), MAX_BATCHED) * H * nw * 3 for (H, W, nh, nw), ix in by_shape.items())
             tmp = self._grow("_tmp", need, torch.uint8)
             for (H, W, nh, nw), idxs in by_shape.items():
@@ -202,7 +237,7 @@ class DeviceAug:
             boxes = torch.empty(B, 3, 3, BOX, BOX, device=dev, dtype=torch.float32)
             gt = torch.empty(B, OUT, OUT, device=dev, dtype=torch.float32)
             table = (_lib.AugImage * B)()
-            chain = []
+            chain, mosaics = [], []
             for i, r in enumerate(recipes):
                 d, h, w = table[i], r["new_h"], r["new_w"]
                 d.src = clean.data_ptr() + 4 * int(w_off[i])
@@ -224,8 +259,14 @@ class DeviceAug:
                 elif r["kind"] == "plain":
                     d.win, d.win_h, d.win_w, d.win_mode = d.src, h, w, 0
                     d.start_h, d.start_w = r["start_h"], r["start_w"]
-                else:
+                elif r["kind"] == "mosaic":
                     d.win, d.win_h, d.win_w, d.win_mode = base + m_off[i], OUT, OUT, 0
+                elif r["kind"] == "mosaic_dev":
+                    d.win, d.win_h, d.win_w, d.win_mode = d.src, h, w, 0      # a valid window; countr_aug_mosaic overwrites the row
+                    mosaics.append(self._mosaic_entry(i, r, lambda k, i=i: (clean.data_ptr() + 4 * int(w_off[slot_of[(i, k)]]),
+                                                                            shapes[slot_of[(i, k)]])))
+                else:
+                    raise ValueError("DeviceAug.batch: unknown recipe kind %r" % (r["kind"],))
             # ---- the chain on the augmented images, then the three outputs for every image
             G = _lib.AUG_MAX_IMAGES
             if chain:
@@ -243,6 +284,10 @@ class DeviceAug:
                 _lib.check(self.L.countr_aug_exemplars(part, n, boxes[g0:].data_ptr(), st), "countr_aug_exemplars")
                 _lib.check(self.L.countr_aug_density(part, n, base + c_off, max(ncells, 1), gt[g0:].data_ptr(), st), "countr_aug_density")
                 self.launches += 3
+            for g0 in range(0, len(mosaics), G):       # after the window launches: the rows of the mosaic_dev recipes
+                sub = (_lib.MosaicImage * len(mosaics[g0:g0 + G]))(*mosaics[g0:g0 + G])
+                _lib.check(self.L.countr_aug_mosaic(sub, len(sub), imgs.data_ptr(), B, st), "countr_aug_mosaic")
+                self.launches += 1
             if self._last is None or self._last[0] != cur:
                 self._last = (cur, torch.cuda.Event())
             self._last[1].record(cur)

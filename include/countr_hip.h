@@ -459,6 +459,31 @@ int countr_aug_density(const countr_aug_image* imgs, int n, const int* cells, in
  * countr_crop_resize_f32 resizes it (same arithmetic), in one launch for the batch. */
 int countr_aug_exemplars(const countr_aug_image* imgs, int n, float* out, void* stream);
 
+/* ---- the mosaic branch of that augmentation on the device (csrc/mosaic.hip; an additive export with a descriptor of its own:
+ * countr_aug_image keeps its layout and the ABI version stays 9).  The oracle is fsc147.mosaic() with _blend_pair: piece k is the
+ * length x length crop at (start_h, start_w) of a clean resized frame, resized to resize_l x resize_l, resize_l = 192 + 2 bl, as
+ * F.interpolate(mode="bilinear", align_corners=False) resizes it (countr_crop_resize_f32's arithmetic).  Pieces 0 / 1 are joined along
+ * the rows into the left half and 2 / 3 into the right half, the two halves along the columns: the 192-line cores are put side by side,
+ * then line 192 + i takes weight (i + bl) / (2 bl) and the first piece's line resize_l - 1 - bl + i the weight (bl - i) / (2 bl), line
+ * 191 - i mixes with the second piece's line bl - i in the same way, i < bl (index_select's own lines: the asymmetry is the
+ * reference's); each join ends with a clamp to [0, 1].  Products and sums are rounded one by one, as torch rounds them. */
+typedef struct countr_mosaic_piece {
+  const float* src;      /* a clean resized frame, fp32 planar [3, h, w] on the device (countr_frame_resize_u8) */
+  int h, w;              /* its size */
+  int start_h, start_w;  /* first row / column of the crop */
+  int length;            /* the crop's edge, 1..min(h, w); start + length lies inside the frame */
+} countr_mosaic_piece;
+typedef struct countr_mosaic_image {
+  countr_mosaic_piece piece[4];   /* quadrants 0 top left, 1 bottom left, 2 top right, 3 bottom right; pieces may share a frame */
+  int bl;                /* half width of the cross-fade, 10..20 */
+  int row;               /* the row of `out` this image is written to, 0..out_rows - 1 */
+} countr_mosaic_image;
+/* countr_aug_mosaic: out[imgs[i].row] [3, 384, 384] <- the mosaic of imgs[i], i < n (1..COUNTR_AUG_MAX_IMAGES; a HOST array read at call
+ * time).  out: the batch tensor [out_rows, 3, 384, 384], 16-byte aligned; rows no descriptor names are left as they are.  One launch on
+ * `stream`, nothing allocated; the resized pieces and the halves are never stored: a pixel evaluates the one, two or four piece samples
+ * it depends on.  Bit-reproducible.  Every argument is checked before anything touches the GPU. */
+int countr_aug_mosaic(const countr_mosaic_image* imgs, int n, float* out, int out_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,8 +7,14 @@
   (c) sustained images/s of "10-worker loader + augmentation + FinetuneStep": host path against the recipe path, alternated, two
       repeats each
 
+With --device_mosaic the two recipe paths are compared instead, mosaic samples finished by the host's mosaic() against "mosaic_dev"
+recipes for countr_aug_mosaic, alternated in the same run:
+  (m1) one worker's time per MOSAIC recipe on either path over the same seeded samples, and the bytes a recipe hands over
+  (m2) DeviceAug.batch for the batch of (b) with its mosaic samples on either path (device events)
+  (c)  sustained images/s, --device_aug against --device_aug --device_mosaic, two repeats each
+
 Frames, dots and boxes are generated from a seed (no dataset needed); a frame is "decoded" by building it in the worker.
-Usage: python tools/bench_aug.py [--batch 8] [--iters 60] [--workers 10] [--samples 6]"""
+Usage: python tools/bench_aug.py [--batch 8] [--iters 60] [--workers 10] [--samples 6] [--device_mosaic [--mosaic_samples 24]]"""
 import argparse
 import json
 import os
@@ -29,9 +35,10 @@ from countr_amd.data import fsc147  # noqa: E402
 class SynthTrain(torch.utils.data.Dataset):
     """FSC147-shaped items from a seed, with what fsc147.mosaic needs of a dataset (train_set, annotations, class_dict, open_image)."""
 
-    def __init__(self, n, seed, mode, epoch_len=None):
+    def __init__(self, n, seed, mode, epoch_len=None, device_mosaic=False):
         rs = np.random.RandomState(seed)
         self.mode = mode                                # "host" | "recipe"
+        self.device_mosaic = device_mosaic              # recipe mode: mosaic samples as mosaic_dev recipes
         self.train_set = ["%d.png" % k for k in range(n)]
         self.img = list(self.train_set)
         self.sizes, self.annotations, self.class_dict = {}, {}, {}
@@ -73,9 +80,50 @@ class SynthTrain(torch.utils.data.Dataset):
         image, rects, dots, im_id = self.item(idx)
         nprng = np.random.RandomState((torch.initial_seed() + idx) % (2 ** 32))
         if self.mode == "recipe":
-            return fsc147.recipe_train(image, rects, dots, im_id, self, do_aug=True, nprng=nprng, noise_counter=self.epoch * len(self) + idx)
+            return fsc147.recipe_train(image, rects, dots, im_id, self, do_aug=True, nprng=nprng, noise_counter=self.epoch * len(self) + idx,
+                                       device_mosaic=self.device_mosaic)
         s = fsc147.transform_train_aug(image, rects, dots, im_id, self, nprng=nprng)
         return s["image"], s["gt_density"], len(dots), s["boxes"], s["m_flag"]
+
+
+def recipe_bytes(rec):
+    """Bytes of the arrays a recipe carries from the worker to the main process."""
+    n = 0
+    for key, v in rec.items():
+        if key == "frame" and "frames" in rec:          # frames[0] again
+            continue
+        for t in (v if key == "frames" else [v]):
+            if isinstance(t, torch.Tensor):
+                n += t.numel() * t.element_size()
+            elif isinstance(t, np.ndarray):
+                n += t.nbytes
+    return n
+
+
+def stats(v):
+    return {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v)), "n": len(v)}
+
+
+def time_mosaic_recipes(ds, n):
+    """(m1): recipe_train for the first n samples whose seeded mosaic coin comes up, host mosaic() and mosaic_dev plan in turn."""
+    ms, nbytes, flags = {"host": [], "device": []}, {"host": [], "device": []}, []
+    torch.set_num_threads(1)
+    idx = seed = 0
+    while len(flags) < n:
+        seed += 1
+        if random.Random(seed).random() >= 0.25:
+            continue
+        image, rects, dots, im_id = ds.item(idx % len(ds))
+        idx += 1
+        for path in ("host", "device", "device", "host"):
+            t0 = time.perf_counter()
+            rec = fsc147.recipe_train(image, rects, dots, im_id, ds, do_aug=True, rng=random.Random(seed), nprng=None,
+                                      device_mosaic=path == "device")
+            ms[path].append((time.perf_counter() - t0) * 1e3)
+            nbytes[path].append(recipe_bytes(rec))
+        flags.append(rec["m_flag"])
+    return {"host_mosaic_ms": stats(ms["host"]), "mosaic_dev_ms": stats(ms["device"]), "host_mosaic_bytes": stats(nbytes["host"][::2]),
+            "mosaic_dev_bytes": stats(nbytes["device"][::2]), "cross_image_mosaics": int(sum(flags)), "samples": len(flags)}
 
 
 def main():
@@ -86,6 +134,8 @@ def main():
     ap.add_argument("--samples", type=int, default=6, help="host samples timed in (a) per round")
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--precision", default="bf16")
+    ap.add_argument("--device_mosaic", action="store_true", help="compare the two recipe paths: host mosaic() against mosaic_dev recipes")
+    ap.add_argument("--mosaic_samples", type=int, default=24, help="mosaic recipes timed in (m1)")
     args = ap.parse_args()
     import models_mae_cross
     from countr_amd.device_aug import DeviceAug
@@ -100,13 +150,18 @@ def main():
     da = DeviceAug(dev, batch=B, noise_seed=1)
     n_items = B * (args.iters + 2 * args.workers + 4)
     ds_host, ds_rec = SynthTrain(n_items, 0, "host"), SynthTrain(n_items, 0, "recipe")
+    ds_mos = SynthTrain(n_items, 0, "recipe", device_mosaic=True)
     res = {"batch": B, "workers": args.workers}
+    if args.device_mosaic:
+        res["m1_worker_per_mosaic_recipe"] = time_mosaic_recipes(ds_rec, args.mosaic_samples)
 
     # ---- (a) and (b), alternated
     random.seed(0)
     recipes = [ds_rec[i] for i in range(B)]
     res["frame_sizes_hw"] = [list(r["frame"].shape[:2]) for r in recipes]
     res["recipe_kinds"] = [r["kind"] for r in recipes]
+    random.seed(0)
+    recipes_m = [ds_mos[i] for i in range(B)]             # the same draws: the same samples, mosaics as mosaic_dev
     host_ms, dev_ms = [], []
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     with step.on_stream():
@@ -131,6 +186,24 @@ def main():
         res["a_host_ms_per_sample"] = {"median": float(np.median(host_ms)), "min": float(min(host_ms)), "max": float(max(host_ms)), "n": len(host_ms)}
         res["b_device_ms_per_batch"] = {"wall_median": float(np.median([d[0] for d in dev_ms])), "gpu_median": float(np.median([d[1] for d in dev_ms])),
                                         "gpu_min": float(min(d[1] for d in dev_ms)), "launches": da.launches, "n": len(dev_ms)}
+        if args.device_mosaic:
+            gpu = {"host_mosaic": [], "mosaic_dev": []}
+            launches = {}
+            for _ in range(3):
+                da.batch(recipes_m)
+            for rnd in range(2 * args.rounds):
+                for name, recs in (("host_mosaic", recipes), ("mosaic_dev", recipes_m)):
+                    for _ in range(5):
+                        torch.cuda.synchronize()
+                        e0.record()
+                        da.batch(recs)
+                        e1.record()
+                        torch.cuda.synchronize()
+                        gpu[name].append(e0.elapsed_time(e1))
+                    launches[name] = da.launches
+            res["m2_device_ms_per_batch"] = {"host_mosaic": stats(gpu["host_mosaic"]), "mosaic_dev": stats(gpu["mosaic_dev"]), "launches": launches,
+                                            "kinds": [r["kind"] for r in recipes_m],
+                                            "uploaded_frames": sum(len(r["frames"]) if r["kind"] == "mosaic_dev" else 1 for r in recipes_m)}
         # the finetune step alone, on device-resident batches (as bench.py times it)
         imgs, boxes, gt, _ = out
         nxt = da.batch(recipes)
@@ -149,14 +222,14 @@ def main():
 
         # ---- (c) loader + augmentation + step, sustained
         def run(mode):
-            ds = ds_rec if mode == "device" else ds_host
-            kw = dict(collate_fn=fsc147.collate_recipes) if mode == "device" else dict(pin_memory=True)
+            ds = {"device": ds_rec, "device_mosaic": ds_mos, "host": ds_host}[mode]
+            kw = dict(collate_fn=fsc147.collate_recipes) if mode != "host" else dict(pin_memory=True)
             dl = torch.utils.data.DataLoader(ds, batch_size=B, shuffle=False, num_workers=args.workers, drop_last=True, **kw)
             it = iter(dl)
 
             def fetch():
                 b = next(it)
-                if mode == "device":
+                if mode != "host":
                     i_, b_, g_, _m = da.batch(b)
                     return i_, b_, g_
                 return b[0], b[3], b[1]
@@ -176,16 +249,23 @@ def main():
             del it
             return B * args.iters / dt
         torch.set_num_threads(1)
-        order = ["host", "device", "host", "device"]
-        rates = {"host": [], "device": []}
+        order = ["device", "device_mosaic", "device", "device_mosaic"] if args.device_mosaic else ["host", "device", "host", "device"]
+        rates = {mode: [] for mode in order}
         for mode in order:
             rates[mode].append(run(mode))
         res["c_images_per_s"] = rates
         # what bounds the recipe path: one worker's time per recipe (decode + draws + host mosaic for a quarter of the samples)
+        random.seed(1)
         t0 = time.perf_counter()
         kinds = [ds_rec[i]["kind"] for i in range(16)]
         res["recipe_ms_per_sample_one_thread"] = (time.perf_counter() - t0) * 1e3 / 16
         res["recipe_mosaics_in_16"] = kinds.count("mosaic")
+        if args.device_mosaic:
+            random.seed(1)                               # the same draws: the same sixteen samples
+            t0 = time.perf_counter()
+            kinds = [ds_mos[i]["kind"] for i in range(16)]
+            res["mosaic_dev_recipe_ms_per_sample_one_thread"] = (time.perf_counter() - t0) * 1e3 / 16
+            res["mosaic_dev_recipes_in_16"] = kinds.count("mosaic_dev")
     print(json.dumps(res))
 
 
