@@ -6,7 +6,8 @@ gradient all-reduce + AdamW, graph-captured, bf16 (no GradScaler), LR schedule p
 Launch one process per GPU: `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 FSC_pretrain.py ...`.
 Data: with the FSC147 files present images come from countr_amd/data/fsc147.py (PIL restatement of ResizePreTrainImage +
 RandomResizedCrop/flip, util/FSC147.py:58-83,369-374); `--synthetic_steps K` trains on synthetic 384x384 images instead (K
-iterations per epoch) and is the automatic fallback when the dataset is absent.  TensorBoard / W&B logging is
+iterations per epoch) and is the automatic fallback when the dataset is absent.  `--device_aug` moves that transform to the GPU
+(countr_amd/pretrain_aug.py: the workers hand over the decoded frame and the draws, HIP kernels build the batch).  TensorBoard / W&B logging is
 replaced by JSON lines on stdout and log.txt."""
 import argparse
 import json
@@ -61,6 +62,9 @@ def get_args_parser():
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     p.add_argument("--synthetic_steps", default=0, type=int,
                    help="K > 0: K iterations per epoch on synthetic images; 0: FSC147 from --data_path (synthetic, 50 it/epoch, if absent)")
+    p.add_argument("--device_aug", action="store_true",
+                   help="build the batches on the GPU: the workers only decode and draw (fsc147.recipe_pretrain), both Pillow resizes, "
+                        "the crop, the flip and ToTensor run as HIP kernels (countr_amd.pretrain_aug); ignored on synthetic images")
     p.add_argument("--log_every", default=20, type=int, help="iterations between loss reports (each report is a host sync)")
     return p
 
@@ -88,14 +92,20 @@ def main(args):
             step.load_scaler_state(ckpt["scaler"])
         print("With optim & sched!")
     from countr_amd.data import fsc147
-    loader = None
+    loader = aug = None
     if args.synthetic_steps <= 0 and fsc147.available(args):
-        ds = fsc147.PretrainData(args)
+        ds = fsc147.PretrainData(args, device_aug=args.device_aug)
         sampler = torch.utils.data.DistributedSampler(ds, num_replicas=misc.get_world_size(), rank=misc.get_rank(), shuffle=True)
+        if args.device_aug:      # the loader hands over recipes (a list: frame sizes differ); PretrainAug builds the batch on the step's stream
+            from countr_amd.pretrain_aug import PretrainAug
+            aug = PretrainAug(device)
         loader = torch.utils.data.DataLoader(ds, sampler=sampler, batch_size=args.batch_size, num_workers=args.num_workers,
-                                             pin_memory=args.pin_mem, drop_last=True)   # drop_last: the fused step has a static batch
+                                             pin_memory=args.pin_mem and aug is None, drop_last=True,      # drop_last: the fused step has a static batch
+                                             collate_fn=fsc147.collate_pretrain_recipes if aug is not None else None)
         n_iter = len(loader)
     else:
+        if args.device_aug:
+            print("--device_aug ignored: synthetic images are made on the device already")
         if args.synthetic_steps <= 0:
             print("FSC147 not found under %s: training on synthetic images" % args.data_path)
         n_iter = args.synthetic_steps if args.synthetic_steps > 0 else 50
@@ -111,7 +121,9 @@ def main(args):
             for it in range(n_iter):
                 if it % args.accum_iter == 0:                                               # :258-259 (per accumulation window)
                     lr = lr_sched.adjust_learning_rate(None, it / n_iter + epoch, args)
-                if it_data is not None:
+                if aug is not None:
+                    imgs = aug.batch(next(it_data))      # one upload + the HIP transform on this stream; a new device tensor per batch
+                elif it_data is not None:
                     imgs = next(it_data)     # host tensor: load() stages it over PCIe on a copy stream while the previous step computes
                 else:
                     imgs = torch.rand(args.batch_size, 3, 384, 384, device=device, generator=g)

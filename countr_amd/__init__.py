@@ -9,4 +9,7 @@ def __getattr__(name):
     if name == "DeviceAug":
         from . import device_aug
         return device_aug.DeviceAug
+    if name == "PretrainAug":
+        from . import pretrain_aug
+        return pretrain_aug.PretrainAug
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

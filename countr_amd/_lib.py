@@ -67,7 +67,14 @@ class MosaicImage(C.Structure):
     _fields_ = [("piece", MosaicPiece * 4), ("bl", C.c_int), ("row", C.c_int)]
 
 
+class PretrainImage(C.Structure):
+    """countr_pretrain_image: one sample of a device pretraining batch (csrc/pretrain_aug.hip)."""
+    _fields_ = [("frame", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("i", C.c_int), ("j", C.c_int), ("ch", C.c_int), ("cw", C.c_int),
+                ("flip", C.c_int), ("row", C.c_int)]
+
+
 AUG_MAX_IMAGES = 32
+PRETRAIN_MAX_IMAGES = 16
 _libs = {}
 
 
@@ -176,6 +183,10 @@ _SIGS = {
     "countr_aug_density": [_vp, _i, _vp, _i, _vp, _vp],
     "countr_aug_exemplars": [_vp, _i, _vp, _vp],
     "countr_aug_mosaic": [_vp, _i, _vp, _i, _vp],
+    "countr_pil_tables": [_i, _i, _i, _vp, _vp],
+    "countr_pretrain_aug_layout": [_vp, _i, _vp],
+    "countr_pretrain_aug_tables": [_vp, _i, _vp, _vp],
+    "countr_pretrain_aug": [_vp, _i, _vp, _vp, _vp, _i, _vp],
     "countr_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp],
 }
 _RESTYPES = {"countr_xattn_bwd_workspace_floats": C.c_int64, "countr_groupnorm_bwd_image_sums_offset": C.c_int64}

@@ -25,6 +25,10 @@ A mosaic sample is finished on the host by mosaic(), but no longer pays for the 
 with device_mosaic=True the worker only makes the mosaic's draws and dot cells (mosaic_plan) and hands over the decoded frames of the
 pieces: the crops, their resize and the cross-fades run in countr_aug_mosaic (csrc/mosaic.hip) with mosaic() as the oracle.
 
+The pretrain transform has the same split (PretrainData(..., device_aug=True), recipe_pretrain below): the worker decodes and makes
+the draws of transform_pretrain in its order, both Pillow resizes, the crop, the flip and ToTensor run in countr_amd/pretrain_aug.py
+(csrc/pretrain_aug.hip), equal to transform_pretrain bit for bit.
+
 PIL's Image.resize(BILINEAR / BICUBIC) is what torchvision.transforms.Resize calls for PIL inputs; exemplar crops are resized
 as TENSORS by the reference (torchvision 0.14.1: bilinear, no antialias) == F.interpolate(mode="bilinear", align_corners=False)."""
 import json
@@ -518,6 +522,25 @@ def transform_pretrain(image, rng=random):
     return to_tensor(image)
 
 
+def recipe_pretrain(image, rng=random):
+    """What a loader worker hands over with device_aug: the decoded frame and the decisions of transform_pretrain, taken with the
+    same draws from `rng` in the same order (random_resized_crop_params on the 16-multiple size, then the flip coin) -> {"frame":
+    uint8 [H, W, 3], "crop": (i, j, ch, cw) on the frame resized to multiples of 16, "flip": bool}.  No resampling happens here:
+    both resizes, the flip and ToTensor run in countr_amd.pretrain_aug.PretrainAug.batch with transform_pretrain as the oracle."""
+    W, H = image.size
+    w16, h16 = 16 * int(W / 16), 16 * int(H / 16)
+    if w16 < 1 or h16 < 1:
+        raise ValueError("height and width must be > 0")      # Pillow's own words for the resize to a zero size
+    i, j, ch, cw = random_resized_crop_params(w16, h16, rng=rng)
+    flip = rng.random() < 0.5
+    return {"frame": _frame_of(image), "crop": (i, j, ch, cw), "flip": bool(flip)}
+
+
+def collate_pretrain_recipes(batch):
+    """collate_fn of the device_aug pretrain loader: the recipes stay a list (frame sizes differ)."""
+    return list(batch)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # test-time loader: TestData of FSC_test_cross(few-shot).py:82-190 (pinned by tests/golden/data_test.npz, generated by exec'ing that class)
 # ---------------------------------------------------------------------------------------------------------------
@@ -669,9 +692,11 @@ class TrainData(Dataset):
 
 
 class PretrainData(Dataset):
-    """FSC_pretrain.py:114-143 -> image [3, 384, 384] (the density file it also opens is never used downstream)."""
+    """FSC_pretrain.py:114-143 -> image [3, 384, 384] (the density file it also opens is never used downstream).  With device_aug
+    the items are recipes (recipe_pretrain) for countr_amd.pretrain_aug.PretrainAug; use collate_fn=collate_pretrain_recipes."""
 
-    def __init__(self, args):
+    def __init__(self, args, device_aug=False):
+        self.device_aug = bool(device_aug)
         _, split_file, self.im_dir = _paths(args)
         self.img = list(json.load(open(split_file))["train"])
         random.shuffle(self.img)
@@ -680,7 +705,8 @@ class PretrainData(Dataset):
         return len(self.img)
 
     def __getitem__(self, idx):
-        return transform_pretrain(_open_rgb(os.path.join(self.im_dir, self.img[idx])))
+        image = _open_rgb(os.path.join(self.im_dir, self.img[idx]))
+        return recipe_pretrain(image) if self.device_aug else transform_pretrain(image)
 
 
 def available(args):

@@ -40,6 +40,21 @@ def pil_tables(in_size, out_size):
     return ksize, bounds, weights
 
 
+BILINEAR, BICUBIC = 0, 1   # countr_pil_tables' filters
+
+
+def pil_filter_tables(filter, in_size, out_size):
+    """(ksize, bounds int32 [out, 2], weights int32 [out, ksize]) of countr_pil_tables for BILINEAR or BICUBIC, as numpy arrays.  The
+    bicubic weights have negative lobes: a pixel's sum is shifted arithmetically and then clamped to 0..255."""
+    L = _lib.lib()
+    ksize = L.countr_pil_tables(filter, in_size, out_size, None, None)
+    _lib.check(min(ksize, 0), "countr_pil_tables")
+    bounds = np.empty((out_size, 2), np.int32)
+    weights = np.empty((out_size, ksize), np.int32)
+    _lib.check(min(L.countr_pil_tables(filter, in_size, out_size, bounds.ctypes.data, weights.ctypes.data), 0), "countr_pil_tables")
+    return ksize, bounds, weights
+
+
 def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 

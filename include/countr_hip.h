@@ -484,6 +484,41 @@ typedef struct countr_mosaic_image {
  * it depends on.  Bit-reproducible.  Every argument is checked before anything touches the GPU. */
 int countr_aug_mosaic(const countr_mosaic_image* imgs, int n, float* out, int out_rows, void* stream);
 
+/* ---- the pretraining loader's transform on the device (csrc/pretrain_aug.hip; additive exports, the ABI version stays 9).  The oracle
+ * is fsc147.transform_pretrain: Pillow BILINEAR resize of the frame to multiples of 16 (H16 = 16 (H / 16), W16 likewise), crop, Pillow
+ * BICUBIC resize of the crop to 384 x 384, horizontal flip, ToTensor -- reproduced bit for bit.
+ * countr_pil_tables (HOST only, touches no GPU): countr_pil_bilinear_tables for both filters, same query form and layout.  filter 0 is
+ *   BILINEAR (equal to countr_pil_bilinear_tables), filter 1 is BICUBIC: a = -0.5, support 2 max(in / out, 1), tap stride
+ *   2 ceil(support) + 1, negative weights rounded as int(-0.5 + w 2^22).  The sum of a pixel can be negative: shift arithmetically, then
+ *   clamp. */
+int countr_pil_tables(int filter, int in_size, int out_size, int* bounds, int* weights);
+#define COUNTR_PRETRAIN_MAX_IMAGES 16
+typedef struct countr_pretrain_image {
+  const void* frame;     /* the decoded frame, uint8 [H, W, 3] interleaved on the device (16-byte loads when 16-byte aligned) */
+  int H, W;              /* its size, each >= 16 */
+  int i, j, ch, cw;      /* the crop: first row, first column, height, width, in the coordinates of the H16 x W16 frame */
+  int flip;              /* != 0: the output is mirrored left-right */
+  int row;               /* the row of the batch tensor this sample is written to */
+} countr_pretrain_image;
+/* All three take a HOST array of n (1..COUNTR_PRETRAIN_MAX_IMAGES) descriptors read at call time, sizes free per sample, and check every
+ * argument before anything touches the GPU.
+ * countr_pretrain_aug_layout (HOST only): sizes[0] = the group's tap stride (the largest ksize of its 4 n axes), sizes[1] = ints of the
+ *   table workspace, sizes[2] = bytes of the image workspace, sizes[3 + 4 s + a] = first int of the table of sample s, axis a (0: W -> W16
+ *   and 1: H -> H16, bilinear; 2: cw -> 384 and 3: ch -> 384, bicubic) in the table workspace: bounds int32 [out][2], then weights int32
+ *   [out][stride], as countr_pil_tables lays them out but with the group's stride (zeros behind an axis' own ksize).  sizes holds
+ *   3 + 4 n entries.
+ * countr_pretrain_aug_tables: fills the table workspace (DEVICE int32 [sizes[1]]) in one launch, one thread per (sample, axis, output
+ *   index), in fp64 with Pillow's operation order and without fused multiply-adds: equal to countr_pil_tables bit for bit.
+ * countr_pretrain_aug: out[imgs[s].row] [3, 384, 384] <- the transform of sample s; out is the batch tensor [out_rows, 3, 384, 384], fp32,
+ *   16-byte aligned; workspace: DEVICE bytes [sizes[2]], 16-byte aligned.  Four launches on `stream` whatever n and the sizes are: the
+ *   stage-1 horizontal and vertical pass (each into 8 bits; a pass whose sizes are equal is skipped and its successor reads its input),
+ *   the bicubic horizontal pass over the crop rectangle (taps relative to the crop: the filter clamps at the crop's edges), the bicubic
+ *   vertical pass + flip + float(u8) / 255 with a 16-byte store per plane.  int32 accumulators as Pillow's.  Table entries are clamped
+ *   to the rectangle they index, so a wrong table cannot read outside a frame.  Nothing is allocated. */
+int countr_pretrain_aug_layout(const countr_pretrain_image* imgs, int n, int64_t* sizes);
+int countr_pretrain_aug_tables(const countr_pretrain_image* imgs, int n, int* tables, void* stream);
+int countr_pretrain_aug(const countr_pretrain_image* imgs, int n, const int* tables, void* workspace, float* out, int out_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
