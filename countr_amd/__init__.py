@@ -6,6 +6,9 @@ def __getattr__(name):
     if name in ("count_frames", "FramePrep"):
         from . import frames
         return getattr(frames, name)
+    if name in ("count_carpk", "CarpkPrep"):
+        from . import carpk
+        return getattr(carpk, name)
     if name == "DeviceAug":
         from . import device_aug
         return device_aug.DeviceAug

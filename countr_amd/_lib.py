@@ -187,6 +187,9 @@ _SIGS = {
     "countr_pretrain_aug_layout": [_vp, _i, _vp],
     "countr_pretrain_aug_tables": [_vp, _i, _vp, _vp],
     "countr_pretrain_aug": [_vp, _i, _vp, _vp, _vp, _i, _vp],
+    "countr_carpk_prep_u8": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "countr_carpk_count_blocks": [_i, _i],
+    "countr_carpk_count": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     "countr_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp],
 }
 _RESTYPES = {"countr_xattn_bwd_workspace_floats": C.c_int64, "countr_groupnorm_bwd_image_sums_offset": C.c_int64}

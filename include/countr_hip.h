@@ -519,6 +519,29 @@ int countr_pretrain_aug_layout(const countr_pretrain_image* imgs, int n, int64_t
 int countr_pretrain_aug_tables(const countr_pretrain_image* imgs, int n, int* tables, void* stream);
 int countr_pretrain_aug(const countr_pretrain_image* imgs, int n, const int* tables, void* workspace, float* out, int out_rows, void* stream);
 
+/* ---- the CARPK scripts' own preparation and count rule (csrc/carpk.hip; additive exports, the ABI version stays 9).
+ * countr_carpk_prep_u8: n (1..16) uint8 [H, W, 3] frames on the device (frames: HOST array of n device pointers; shapes: HOST int
+ *   [n][2] = {H, W}, free per frame) -> img fp32 [n, 3, out_h, out_cols] = F.interpolate(frame / 255, (out_h, out_w), bilinear,
+ *   align_corners=False)[..., :out_cols], what torchvision 0.14.1's Resize does to a TENSOR (FSC_test_CARPK.py:154, :191: no antialias,
+ *   not Pillow's resample), 1 <= out_cols <= out_w: only the columns that are kept are computed (FSC_finetune_CARPK.py:225-226 crops
+ *   the left 384 after the resize); and the nrects (0..32) rectangles rects[nrects][5] = {frame, y1, x1, y2, x2} (HOST array, corners
+ *   INCLUSIVE and >= 0, in pixels of the ORIGINAL frame; clipped as frame[y1:y2 + 1, x1:x2 + 1] clips; empty after clipping = error)
+ *   -> ex fp32 [nrects, 3, 64, 64], the same interpolation of the rectangle / 255 (:166-171).  Source coordinates as torch computes
+ *   them: scale = in / out in fp32, src = scale * (dst + 0.5) - 0.5 clamped at 0.  ONE launch; 16-byte stores when out_cols % 4 == 0 and
+ *   img / ex are 16-byte aligned, one pixel per thread otherwise (out_w = 683).  ex may be NULL when nrects == 0.
+ * countr_carpk_count: the count rule of FSC_test_CARPK.py:220-243 on n (1..16) stitched maps fp32 [n, H, W] with two rectangles per map,
+ *   rects[n][2][4] = (a, b, c, d) (HOST array, >= 0) -> out fp32 [n][4] = {pred, total, n_over, e_cnt}:
+ *     cell = sum of a 16 x 16 block / 60 over floor(H / 16) x floor(W / 16) blocks (trailing rows / columns dropped, as the stride-16
+ *     convolution drops them); total = sum of the cells; n_over = cells > 1.224;
+ *     e_cnt = (sum over both rectangles of sum(map[a : a + c + 1, b : b + d + 1]) / 60) / 2, slices clipped to the map, empty = 0 (which
+ *     rectangles the script's line :238 really cuts is the caller's business: countr_amd/data/carpk.py::script_rects); pred = total - n_over + (e_cnt <= 0.5 ? 2 : 0).
+ *   Two launches (partials, fold) through workspace fp32 [n * countr_carpk_count_blocks(H, W) * 4]; every sum has a fixed order, no
+ *   atomics: two runs give the same bits. */
+int countr_carpk_prep_u8(const void* const* frames, const int* shapes, int n, const int* rects, int nrects, int out_h, int out_w,
+                         int out_cols, float* img, float* ex, void* stream);
+int countr_carpk_count_blocks(int H, int W);
+int countr_carpk_count(const float* maps, int n, int H, int W, const int* rects, float* out, float* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
