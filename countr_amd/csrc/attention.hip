@@ -369,8 +369,6 @@ __global__ void xattn_bwd_finish_kernel(const float* __restrict__ partial, float
 
 }  // namespace
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 extern "C" int countr_softmax_fwd_ld(const float* s, void* p, int64_t rows, int n, int ld, int out_bf16, void* stream) {
   if (!s || !p || n <= 0 || ld < n || ld > 64 * SMAX_PER_LANE) { countr_set_error("countr_softmax_fwd: need 0 < n <= ld <= 1024"); return -1; }
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);

@@ -9,7 +9,8 @@
 //   countr_aug_window     warp_affine (= scipy affine_transform order 1, constant 0) + horizontal flip + the 384 x 384 crop in one store
 //                         pass -- the full warp is never materialised; copy mode cuts the same window out of an unwarped image
 //   countr_aug_density    60 * scipy gaussian_filter(dot map, sigma 1) on 384 x 384 straight from the list of dot cells
-//   countr_aug_exemplars  the arithmetic of countr_crop_resize_f32 (frames.hip) for the three exemplars of every image of a batch
+//   countr_aug_exemplars  the formula of countr_crop_resize_f32 (frames.hip; bilinear.hpp) for the three exemplars of every image of a
+//                         batch: the same formula, contraction off here, on there
 // Every kernel serves a whole batch of differently sized images from a table of per-image descriptors passed by value (built here from
 // the caller's HOST array of countr_aug_image), so launches per batch do not grow with the batch.  fp32 only: both library builds
 // export the same code.
@@ -20,8 +21,7 @@
 
 // the host functions round every product and sum on its own (torch CPU kernels, scipy's C loops): no fused multiply-adds here
 #pragma clang fp contract(off)
-
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
+#include "bilinear.hpp"      // contraction OFF (below the pragma): exemplar_kernel rounds every product and sum on its own, as torch's CPU kernel does
 
 namespace {
 
@@ -89,7 +89,6 @@ struct JitImg {
 };
 struct JitArgs { JitImg im[MAX_IMGS]; };
 
-__device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
 __device__ __forceinline__ float gray_of(float r, float g, float b) { return (0.2989f * r + 0.587f * g) + 0.114f * b; }
 
 // _rgb2hsv -> remainder(h + shift, 1) -> _hsv2rgb of fsc147.py, operation for operation
@@ -143,13 +142,12 @@ __device__ __forceinline__ void apply_ops(const JitImg& d, int k0, int k1, float
   }
 }
 
+// PX pixels of a plane: one 16-byte access (PX = 4) or one element
 template <int PX> __device__ __forceinline__ void ldpx(const float* p, float (&v)[PX]) {
-  if constexpr (PX == 4) { const float4 t = *reinterpret_cast<const float4*>(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-  else v[0] = p[0];
+  if constexpr (PX == 4) ld4<float>(p, v); else v[0] = p[0];
 }
 template <int PX> __device__ __forceinline__ void stpx(float* p, const float (&v)[PX]) {
-  if constexpr (PX == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1 % PX], v[2 % PX], v[3 % PX]);
-  else p[0] = v[0];
+  if constexpr (PX == 4) st4<float>(p, v); else p[0] = v[0];
 }
 
 // pass A of image d for workgroup `part`: noise, the ops in front of the contrast op, the workgroup's grey sum
@@ -427,7 +425,7 @@ struct BoxImg {
 };
 struct BoxArgs { BoxImg im[MAX_IMGS]; };
 
-// crop_resize_kernel of frames.hip (torch's upsample_bilinear2d, align_corners=False) with the image taken from the table
+// crop_resize_kernel of frames.hip (torch's upsample_bilinear2d, align_corners=False) with the image taken from the table, contraction off
 __global__ __launch_bounds__(256) void exemplar_kernel(const BoxArgs a, float* __restrict__ out, int n) {
   constexpr int per = BOX / 4, chunks = NBOX * 3 * BOX * per / 256;      // 36 workgroup-sized chunks per image
   for (int blk = blockIdx.x; blk < n * chunks; blk += gridDim.x) {
@@ -439,25 +437,14 @@ __global__ __launch_bounds__(256) void exemplar_kernel(const BoxArgs a, float* _
     const int c = (int)((row / BOX) % 3), r = (int)((row / (3 * BOX)) % NBOX);
     const BoxImg& d = a.im[b];
     const int ch = d.ch[r], cw = d.cw[r];
-    const float sy = (float)ch / (float)BOX, sx = (float)cw / (float)BOX;
-    const float fy = fmaxf(sy * ((float)oy + 0.5f) - 0.5f, 0.f);
-    const int y1 = min((int)fy, ch - 1), yp = y1 < ch - 1 ? 1 : 0;
-    const float ly = fy - (float)y1, ly0 = 1.f - ly;
-    const float* s0 = d.src + ((int64_t)c * d.h + d.y0[r] + y1) * d.w + d.x0[r];
-    const float* s1 = s0 + (int64_t)yp * d.w;
+    const float* org = d.src + ((int64_t)c * d.h + d.y0[r]) * d.w + d.x0[r];
+    const BilinearRow t = bilinear_row(org, d.w, ch, cw, bilinear_scale(ch, BOX), bilinear_scale(cw, BOX), oy);
     float v[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float fx = fmaxf(sx * ((float)(q * 4 + e) + 0.5f) - 0.5f, 0.f);
-      const int x1 = min((int)fx, cw - 1), xp = x1 < cw - 1 ? 1 : 0;
-      const float lx = fx - (float)x1, lx0 = 1.f - lx;
-      v[e] = ly0 * (lx0 * s0[x1] + lx * s0[x1 + xp]) + ly * (lx0 * s1[x1] + lx * s1[x1 + xp]);
-    }
+    for (int e = 0; e < 4; ++e) v[e] = bilinear_at(t, q * 4 + e);
     *reinterpret_cast<float4*>(out + row * BOX + (int64_t)q * 4) = make_float4(v[0], v[1], v[2], v[3]);
   }
 }
-
-int blocks_for(int64_t threads) { return (int)max((int64_t)1, min((int64_t)2048, (threads + 255) / 256)); }
 
 bool table_ok(const countr_aug_image* imgs, int n, const char* who) {
   static thread_local char msg[160];
@@ -475,7 +462,7 @@ extern "C" int countr_aug_partials_floats(int n) { return (n < 1 ? 1 : n) * PART
 
 extern "C" int countr_aug_normal(float* out, int64_t n, float scale, uint64_t seed, uint64_t counter, void* stream) {
   if (!out || n < 1 || n > ((int64_t)1 << 33)) { countr_set_error("countr_aug_normal: bad args (1 <= n <= 2^33)"); return -1; }
-  hipLaunchKernelGGL(normal_kernel, dim3(blocks_for((n + 3) / 4)), dim3(256), 0, STREAM(stream), out, (long long)n, scale,
+  hipLaunchKernelGGL(normal_kernel, dim3(countr_blocks_for((n + 3) / 4, 2048)), dim3(256), 0, STREAM(stream), out, (long long)n, scale,
                      (unsigned int)seed, (unsigned int)(seed >> 32), (unsigned int)counter, (unsigned int)(counter >> 32));
   COUNTR_LAUNCH_CHECK("countr_aug_normal");
 }
@@ -549,7 +536,7 @@ extern "C" int countr_aug_window(const countr_aug_image* imgs, int n, float* out
     d.mode = s.win_mode; d.flip = s.flip ? 1 : 0;
     for (int k = 0; k < 6; ++k) d.m[k] = s.affine[k];
   }
-  hipLaunchKernelGGL(window_kernel, dim3(blocks_for((int64_t)n * OUT * (OUT / 4))), dim3(256), 0, STREAM(stream), a, out, n);
+  hipLaunchKernelGGL(window_kernel, dim3(countr_blocks_for((int64_t)n * OUT * (OUT / 4), 2048)), dim3(256), 0, STREAM(stream), a, out, n);
   COUNTR_LAUNCH_CHECK("countr_aug_window");
 }
 
@@ -580,13 +567,13 @@ extern "C" int countr_aug_exemplars(const countr_aug_image* imgs, int n, float* 
     d.src = s.src; d.h = s.h; d.w = s.w;
     for (int r = 0; r < NBOX; ++r) {
       const int* q = s.rects + 4 * r;                              // {y1, x1, y2, x2}, inclusive; clipped as img[:, y1:y2 + 1, x1:x2 + 1] clips
-      if (q[0] < 0 || q[1] < 0) { countr_set_error("countr_aug_exemplars: negative rectangle corner"); return -1; }
-      const int y0 = min(q[0], s.h), x0 = min(q[1], s.w);
-      const int ch = (int)(min((int64_t)q[2] + 1, (int64_t)s.h) - y0), cw = (int)(min((int64_t)q[3] + 1, (int64_t)s.w) - x0);
-      if (ch < 1 || cw < 1) { countr_set_error("countr_aug_exemplars: a rectangle is empty after clipping to the image"); return -1; }
-      d.y0[r] = y0; d.x0[r] = x0; d.ch[r] = ch; d.cw[r] = cw;
+      if (!clip_rect(q[0], q[1], q[2], q[3], s.h, s.w, &d.y0[r], &d.x0[r], &d.ch[r], &d.cw[r])) {
+        countr_set_error(q[0] < 0 || q[1] < 0 ? "countr_aug_exemplars: negative rectangle corner"
+                                              : "countr_aug_exemplars: a rectangle is empty after clipping to the image");
+        return -1;
+      }
     }
   }
-  hipLaunchKernelGGL(exemplar_kernel, dim3(blocks_for((int64_t)n * NBOX * 3 * BOX * (BOX / 4))), dim3(256), 0, STREAM(stream), a, out, n);
+  hipLaunchKernelGGL(exemplar_kernel, dim3(countr_blocks_for((int64_t)n * NBOX * 3 * BOX * (BOX / 4), 2048)), dim3(256), 0, STREAM(stream), a, out, n);
   COUNTR_LAUNCH_CHECK("countr_aug_exemplars");
 }

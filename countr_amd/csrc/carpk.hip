@@ -2,14 +2,13 @@
 //   countr_carpk_prep_u8  uint8 [H, W, 3] frames -> the fp32 planar image of torchvision's TENSOR Resize (0.14.1: plain
 //                         F.interpolate(frame / 255, bilinear, align_corners=False), no antialias -- not Pillow's resample of
 //                         frames.hip) and the 64 x 64 exemplars cut from the ORIGINAL-resolution frame (FSC_test_CARPK.py:154-172,
-//                         :191), both in one launch
+//                         :191), both in one launch; the source index is bilinear.hpp's, the blend on uint8 / 255 is this file's
 //   countr_carpk_count    the script's count rule on stitched maps (:220-243): 16 x 16 cell sums / 60, minus one per cell above
 //                         1.224, plus 2 when the two exemplar rectangles hold at most half an object each
 // uint8 / fp32 only: the bf16 and the fp16 build of the library export the same code.
 #include "common.hpp"
+#include "bilinear.hpp"      // contraction ON (above the pragma below): the source index of carpk_prep_kernel may be fused, as it always has been
 #include "../../include/countr_hip.h"
-
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
 namespace {
 
@@ -26,16 +25,9 @@ struct PrepArgs {
   int y0[MAX_RECTS], x0[MAX_RECTS], ch[MAX_RECTS], cw[MAX_RECTS];   // first row / column and size after clipping to the frame
 };
 
-// torch's area_pixel_compute_source_index (align_corners=False): scale = in / out in fp32, src = scale * (dst + 0.5) - 0.5 clamped at 0
-__device__ __forceinline__ void source_index(int in_size, int out_size, int dst, int* i0, int* step, float* l1) {
-  const float scale = (float)in_size / (float)out_size;
-  const float s = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-  const int i = min((int)s, in_size - 1);
-  *i0 = i; *step = i < in_size - 1 ? 1 : 0; *l1 = s - (float)i;
-}
-
-// No fused multiply-adds in this file: the vector and the scalar form of the kernel below must give the same bits (the training crop
-// equals the test image's left columns), and torch's CPU kernel rounds every product.
+// No fused multiply-adds in the blend of the kernel below: its vector and its scalar form must give the same bits (the training crop
+// equals the test image's left columns), and torch's CPU kernel rounds every product.  The source index (bilinear_src, parsed above
+// this pragma) may be contracted; it is one function for both forms.
 #pragma clang fp contract(off)
 
 // One work item = PX neighbouring output pixels of one row, all three channels: the 2 x 2 source neighbourhood of a pixel (12 bytes of
@@ -77,14 +69,14 @@ __global__ __launch_bounds__(256) void carpk_prep_kernel(const PrepArgs a, float
     }
     int y1, yp, x1, xp;
     float ly, lx;
-    source_index(ch, oh, oy, &y1, &yp, &ly);
+    bilinear_src(ch, bilinear_scale(ch, oh), oy, &y1, &yp, &ly);
     const float ly0 = 1.f - ly;
     const uint8_t* r0 = src + (int64_t)y1 * W * 3;
     const uint8_t* r1 = r0 + (int64_t)yp * W * 3;
     float v[3][PX];
 #pragma unroll
     for (int e = 0; e < PX; ++e) {
-      source_index(cw, ow, ox0 + e, &x1, &xp, &lx);
+      bilinear_src(cw, bilinear_scale(cw, ow), ox0 + e, &x1, &xp, &lx);
       const float lx0 = 1.f - lx;
       const uint8_t* p00 = r0 + x1 * 3;
       const uint8_t* p01 = p00 + xp * 3;
@@ -180,17 +172,17 @@ extern "C" int countr_carpk_prep_u8(const void* const* frames, const int* shapes
   for (int j = 0; j < MAX_RECTS; ++j) {
     if (nrects == 0) { a.rf[j] = 0; a.y0[j] = a.x0[j] = 0; a.ch[j] = a.cw[j] = 1; continue; }
     const int* r = rects + 5 * (j < nrects ? j : nrects - 1);      // {frame, y1, x1, y2, x2}, corners inclusive
-    if (r[0] < 0 || r[0] >= n || r[1] < 0 || r[2] < 0) { countr_set_error("countr_carpk_prep_u8: rectangle of a frame that is not there, or negative corner"); return -1; }
-    const int H = a.H[r[0]], W = a.W[r[0]];
-    const int y0 = min(r[1], H), x0 = min(r[2], W);                // frame[y1:y2 + 1, x1:x2 + 1]: slicing clips both ends to the frame
-    const int ch = (int)(min((int64_t)r[3] + 1, (int64_t)H) - y0), cw = (int)(min((int64_t)r[4] + 1, (int64_t)W) - x0);
-    if (ch < 1 || cw < 1) { countr_set_error("countr_carpk_prep_u8: a rectangle is empty after clipping to its frame"); return -1; }
-    a.rf[j] = r[0]; a.y0[j] = y0; a.x0[j] = x0; a.ch[j] = ch; a.cw[j] = cw;
+    const char* bad = "countr_carpk_prep_u8: rectangle of a frame that is not there, or negative corner";
+    if (r[0] < 0 || r[0] >= n) { countr_set_error(bad); return -1; }
+    a.rf[j] = r[0];
+    if (!clip_rect(r[1], r[2], r[3], r[4], a.H[r[0]], a.W[r[0]], &a.y0[j], &a.x0[j], &a.ch[j], &a.cw[j])) {      // corners inclusive
+      countr_set_error(r[1] < 0 || r[2] < 0 ? bad : "countr_carpk_prep_u8: a rectangle is empty after clipping to its frame"); return -1;
+    }
   }
   const bool vec = (out_cols & 3) == 0 && (((uintptr_t)img) & 15) == 0 && (nrects == 0 || (((uintptr_t)ex) & 15) == 0);
   const int px = vec ? 4 : 1;
   const int64_t threads = (int64_t)n * out_h * (out_cols / px) + (int64_t)nrects * BOX * (BOX / px);
-  const int blocks = (int)max((int64_t)1, min((int64_t)MAX_BLOCKS, (threads + 255) / 256));
+  const int blocks = countr_blocks_for(threads, MAX_BLOCKS);
   if (vec) hipLaunchKernelGGL(carpk_prep_kernel<true>, dim3(blocks), dim3(256), 0, STREAM(stream), a, img, ex, n, nrects, out_h, out_w, out_cols);
   else hipLaunchKernelGGL(carpk_prep_kernel<false>, dim3(blocks), dim3(256), 0, STREAM(stream), a, img, ex, n, nrects, out_h, out_w, out_cols);
   COUNTR_LAUNCH_CHECK("countr_carpk_prep_u8");

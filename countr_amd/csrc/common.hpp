@@ -237,6 +237,13 @@ int countr_check_launch(const char* what);
 #define COUNTR_ZERO_VEC_FLOATS 8192
 const float* countr_zero_vec(int n);
 #define COUNTR_LAUNCH_CHECK(what) return countr_check_launch(what)
+#define STREAM(s) reinterpret_cast<hipStream_t>(s)      // the exports take the stream as void*
+// workgroups of 256 threads for a grid-stride loop over `threads` items: at least one, at most `cap`
+static inline int countr_blocks_for(int64_t threads, int cap) {
+  const int64_t b = (threads + 255) / 256;
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+__device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
 
 // K order of the 3x3 convolutions' implicit GEMMs in linear.hip / gemm256.hip (K = 9 taps x Cin, k-tile = 64 channels of one tap):
 // channel-chunk-major -- k-tile t is tap t % 9 of chunk t / 9, so nine consecutive k-tiles read the SAME 128-byte pieces of the

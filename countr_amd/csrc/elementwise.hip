@@ -712,7 +712,6 @@ __global__ __launch_bounds__(256) void amp_check_kernel(const float* __restrict_
 
 }  // namespace
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
 static inline int nblocks(int64_t work, int per_block = 256, int cap = 4096) {
   int64_t b = (work + per_block - 1) / per_block;
   return (int)(b < 1 ? 1 : (b > cap ? cap : b));

@@ -3,8 +3,6 @@
 #include "common.hpp"
 #include "../../include/countr_hip.h"
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 // dst[r,:] = (idx[r] >= 0 ? src[idx[r],:] : default_row[:]) + add[r % add_mod,:]     (4 columns per thread)
 template <typename TS, typename TD>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const TS* __restrict__ src, const int* __restrict__ idx, TD* __restrict__ dst,

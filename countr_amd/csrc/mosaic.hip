@@ -4,15 +4,14 @@
 // (fsc147.mosaic_plan), the frames come from countr_frame_resize_u8 (countr_amd/device_aug.py::DeviceAug).
 //   countr_aug_mosaic     out[row] [3, 384, 384] <- the mosaic of its four pieces.  Neither the four resized pieces nor the two 384-line
 //                         halves are stored: every output pixel evaluates the one (quadrant interior), two (a seam band) or four (where
-//                         the bands cross) bilinear piece samples it depends on and mixes them in the reference's order
+//                         the bands cross) bilinear piece samples (bilinear.hpp) it depends on and mixes them in the reference's order
 // fp32 only: both library builds export the same code.
 #include "common.hpp"
 #include "../../include/countr_hip.h"
 
 // torch's CPU kernels round every product and sum on its own: no fused multiply-adds here
 #pragma clang fp contract(off)
-
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
+#include "bilinear.hpp"      // contraction OFF (below the pragma): a piece sample rounds every product and sum on its own, as exemplar_kernel does
 
 namespace {
 
@@ -32,36 +31,15 @@ struct MosImg {
 };
 struct MosArgs { MosImg im[MAX_IMGS]; };
 
-__device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
-
-// line r of a resized piece, channel c: the two source rows and their weights (exemplar_kernel's arithmetic, augment.hip)
-struct RowTap {
-  const float* s0;
-  const float* s1;
-  float ly, ly0, scale;
-  int length;
-};
-__device__ __forceinline__ RowTap row_tap(const MosPiece& p, int c, int r) {
-  RowTap t;
-  const float fy = fmaxf(p.scale * ((float)r + 0.5f) - 0.5f, 0.f);
-  const int y1 = min((int)fy, p.length - 1), yp = y1 < p.length - 1 ? 1 : 0;
-  t.ly = fy - (float)y1; t.ly0 = 1.f - t.ly;
-  t.s0 = p.org + (int64_t)c * p.plane + (int64_t)y1 * p.w;
-  t.s1 = t.s0 + (int64_t)yp * p.w;
-  t.scale = p.scale; t.length = p.length;
-  return t;
-}
-__device__ __forceinline__ float sample(const RowTap& t, int col) {
-  const float fx = fmaxf(t.scale * ((float)col + 0.5f) - 0.5f, 0.f);
-  const int x1 = min((int)fx, t.length - 1), xp = x1 < t.length - 1 ? 1 : 0;
-  const float lx = fx - (float)x1, lx0 = 1.f - lx;
-  return t.ly0 * (lx0 * t.s0[x1] + lx * t.s0[x1 + xp]) + t.ly * (lx0 * t.s1[x1] + lx * t.s1[x1 + xp]);
+// line r of a resized piece, channel c
+__device__ __forceinline__ BilinearRow row_tap(const MosPiece& p, int c, int r) {
+  return bilinear_row(p.org + (int64_t)c * p.plane, p.w, p.length, p.length, p.scale, p.scale, r);
 }
 
 // output line y of one half (two pieces joined along the rows): the kept line of the piece y lies in, and inside the band of bl lines
 // either side of the seam the neighbour's overhanging line it is mixed with (weights and line indices of _blend_pair)
 struct HalfRow {
-  RowTap kept, over;
+  BilinearRow kept, over;
   float w_kept, w_over;
   bool seam;
 };
@@ -80,8 +58,8 @@ __device__ __forceinline__ HalfRow half_row(const MosImg& d, int half, int c, in
   return h;
 }
 __device__ __forceinline__ float half_at(const HalfRow& h, int col) {
-  float v = sample(h.kept, col);
-  if (h.seam) v = v * h.w_kept + sample(h.over, col) * h.w_over;
+  float v = bilinear_at(h.kept, col);
+  if (h.seam) v = v * h.w_kept + bilinear_at(h.over, col) * h.w_over;
   return clamp01(v);
 }
 

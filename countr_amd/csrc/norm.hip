@@ -1014,8 +1014,6 @@ __global__ __launch_bounds__(256) void in_bwd_split_kernel(const T* __restrict__
 
 }  // namespace
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 extern "C" int countr_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y, float* mean,
                                     float* rstd, int rows, int D, float eps, int out_bf16, void* stream) {
   if (!x || !gamma || !beta || !y || D % 4 || D > 2048 || rows <= 0) { countr_set_error("countr_layernorm_fwd: bad args (need D % 4 == 0, D <= 2048)"); return -1; }

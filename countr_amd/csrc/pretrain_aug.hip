@@ -7,81 +7,19 @@
 //   countr_pretrain_aug          four launches: stage 1 horizontal, stage 1 vertical (uint8 [H, W, 3] -> uint8 [H16, W16, 3]), the
 //                                bicubic horizontal pass over the crop rectangle, the bicubic vertical pass + flip + ToTensor into the
 //                                batch tensor
-// Every pass goes into 8 bits before the next one, as Pillow's does, with int32 accumulators; the result equals PIL + ToTensor bit for bit.
-// One table row is ONE function (table_row) for the host export and the device kernel, compiled with fp contraction off: an fma in
-// (xx + 0.5) * scale - support or in the cubic would change the last bit of a double and with it a rounded tap.
+// The tables and the bodies of the passes are pil_resample.hpp's (shared with frames.hip); the kernels here take every sample's sizes and
+// buffers from a descriptor.  The result equals PIL + ToTensor bit for bit.
 // uint8 / fp32 only: the bf16 and the fp16 build of the library export the same code.
 #include "common.hpp"
+#include "pil_resample.hpp"
 #include "../../include/countr_hip.h"
-
-#include <math.h>
-
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
 namespace {
 
-constexpr int PRECISION_BITS = 32 - 8 - 2;      // Pillow's fixed point: weights are int(+-0.5 + w * 2^22)
 constexpr int MAX_IMAGES = COUNTR_PRETRAIN_MAX_IMAGES;
 constexpr int OUT = 384;
-constexpr int STAGE_BYTES = 16384;              // LDS staging of one source row segment (horizontal passes)
 constexpr int MAX_BLOCKS = 2048;
 constexpr int MAX_KSIZE = 1 << 12;
-
-struct Axis {
-  double scale, support, ss;
-  int ksize;
-};
-
-// precompute_coeffs' per-axis constants.  filter 0: bilinear (support 1), 1: bicubic (support 2)
-__host__ __device__ inline Axis axis_of(int filter, int in_size, int out_size) {
-#pragma clang fp contract(off)
-  Axis a;
-  a.scale = (double)in_size / (double)out_size;
-  const double fs = a.scale < 1.0 ? 1.0 : a.scale;
-  a.support = (filter == 1 ? 2.0 : 1.0) * fs;
-  a.ss = 1.0 / fs;                              // (Pillow multiplies by this reciprocal; so does this file)
-  const double k = ceil(a.support) * 2 + 1;
-  a.ksize = k > (double)(1 << 30) ? 1 << 30 : (int)k;
-  return a;
-}
-
-__host__ __device__ inline double filter_of(int filter, double x) {
-#pragma clang fp contract(off)
-  if (x < 0.0) x = -x;
-  if (filter == 1) {                            // bicubic_filter, a = -0.5
-    const double a = -0.5;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-  }
-  return x < 1.0 ? 1.0 - x : 0.0;               // bilinear_filter
-}
-
-// Row xx of the tables of one axis: bounds[2 xx] = {first source index, tap count}, weights[xx * stride ..] = the taps in fixed point,
-// zeros behind the tap count up to `stride` (>= the axis' ksize).  The weights are summed in a first loop and evaluated again in the
-// second (the same operations give the same doubles), so that no per-row array of doubles is needed.
-__host__ __device__ inline void table_row(int filter, const Axis& ax, int in_size, int xx, int stride, int* bounds, int* weights) {
-#pragma clang fp contract(off)
-  const double center = (xx + 0.5) * ax.scale;
-  int xmin = (int)(center - ax.support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + ax.support + 0.5);
-  if (xmax > in_size) xmax = in_size;
-  xmax -= xmin;
-  double ww = 0.0;
-  for (int x = 0; x < xmax; ++x) ww += filter_of(filter, (x + xmin - center + 0.5) * ax.ss);
-  int* k = weights + (int64_t)xx * stride;
-  for (int x = 0; x < stride; ++x) {
-    double w = 0.0;
-    if (x < xmax) {
-      w = filter_of(filter, (x + xmin - center + 0.5) * ax.ss);
-      if (ww != 0.0) w /= ww;
-    }
-    k[x] = w < 0 ? (int)(-0.5 + w * (double)(1 << PRECISION_BITS)) : (int)(0.5 + w * (double)(1 << PRECISION_BITS));
-  }
-  bounds[2 * xx] = xmin;
-  bounds[2 * xx + 1] = xmax;
-}
 
 // ---- the tables of a group on the device
 struct TableJob {
@@ -104,11 +42,6 @@ __global__ __launch_bounds__(256) void tables_kernel(const TableArgs a, int* __r
 }
 
 // ---- the image passes
-__device__ __forceinline__ uint8_t clip8(int v) {      // (an arithmetic shift: a negative sum of the bicubic lobes clips to 0)
-  v >>= PRECISION_BITS;
-  return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
-
 // One sample of a horizontal pass: rows y0 .. y0 + rows of src (uint8 interleaved, `pitch` pixels per row), columns x0 .. x0 + in_w
 // -> dst uint8 [rows, out_w, 3].  Taps are relative to x0 and clamp at in_w: Pillow crops first, so the filter sees the crop's edges.
 struct HSample {
@@ -125,9 +58,7 @@ struct HArgs {
   int n, items, stride;
 };
 
-// Horizontal pass.  One work item = (sample, source row, tile of `tile` output pixels): the bytes of the row the tile's taps touch are
-// staged in LDS with 16-byte loads and every thread resamples one output pixel (3 channels) from there.  Table entries are clamped to
-// the staged range, so a wrong table cannot make the kernel read outside the rectangle.
+// Horizontal pass (pil_hpass_item).  One work item = (sample, source row, tile of `tile` output pixels).
 __global__ __launch_bounds__(256) void hpass_kernel(const HArgs a, const int* __restrict__ ws) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[STAGE_BYTES];
   for (int it = blockIdx.x; it < a.items; it += gridDim.x) {
@@ -137,45 +68,8 @@ __global__ __launch_bounds__(256) void hpass_kernel(const HArgs a, const int* __
     const int local = it - s.first;
     const int t = local % s.tiles, y = local / s.tiles;
     const int* bounds = ws + s.tab;
-    const int* weights = bounds + 2 * s.out_w;
-    const int xo0 = t * s.tile, xo1 = min(s.out_w, xo0 + s.tile);
-    int xs = bounds[2 * xo0], xe = bounds[2 * (xo1 - 1)] + bounds[2 * (xo1 - 1) + 1];
-    xs = max(0, min(xs, s.in_w));
-    xe = max(xs, min(xe, s.in_w));
-    const int64_t b0 = ((int64_t)(s.y0 + y) * s.pitch + s.x0 + xs) * 3;      // first byte of the segment in src
-    const int64_t a0 = s.vec ? (b0 & ~(int64_t)15) : b0;
-    const int head = (int)(b0 - a0);
-    const int span = min((xe - xs) * 3, STAGE_BYTES - 16 - head);           // (the host sized `tile` so that this never cuts)
-    if (s.vec) {
-      const int nvec = (head + span + 15) >> 4;
-      for (int v = threadIdx.x; v < nvec; v += 256) {
-        const int64_t off = a0 + (int64_t)v * 16;
-        if (off + 16 <= s.src_bytes) {
-          *reinterpret_cast<uint4*>(stage + v * 16) = *reinterpret_cast<const uint4*>(s.src + off);
-        } else {
-          for (int b = 0; b < 16; ++b) stage[v * 16 + b] = off + b < s.src_bytes ? s.src[off + b] : (uint8_t)0;
-        }
-      }
-    } else {
-      for (int b = threadIdx.x; b < span; b += 256) stage[b] = s.src[a0 + b];
-    }
-    __syncthreads();
-    const int xo = xo0 + threadIdx.x;
-    if (xo < xo1) {
-      int xmin = bounds[2 * xo], cnt = bounds[2 * xo + 1];
-      xmin = max(xs, min(xmin, xe));
-      cnt = max(0, min(min(cnt, a.stride), min(xe - xmin, (span - (xmin - xs) * 3) / 3)));
-      const int* k = weights + (int64_t)xo * a.stride;
-      const uint8_t* p = stage + head + (xmin - xs) * 3;
-      int r = 1 << (PRECISION_BITS - 1), g = r, b = r;
-      for (int j = 0; j < cnt; ++j) {
-        const int w = k[j];
-        r += (int)p[3 * j] * w; g += (int)p[3 * j + 1] * w; b += (int)p[3 * j + 2] * w;
-      }
-      uint8_t* o = s.dst + ((int64_t)y * s.out_w + xo) * 3;
-      o[0] = clip8(r); o[1] = clip8(g); o[2] = clip8(b);
-    }
-    __syncthreads();
+    pil_hpass_item(s.src, s.src_bytes, s.pitch, s.x0, s.y0 + y, s.in_w, bounds, bounds + 2 * s.out_w, a.stride,
+                   s.dst + (int64_t)y * s.out_w * 3, s.out_w, s.tile, t, s.vec != 0, stage);
   }
 }
 
@@ -202,10 +96,8 @@ __global__ __launch_bounds__(256) void vpass_u8_kernel(const VArgs a, const int*
     const int per = s.row_bytes >> 2;
     const int q = local % per, yo = local / per;
     const int* bounds = ws + s.tab;
-    int ymin = bounds[2 * yo], cnt = bounds[2 * yo + 1];
-    ymin = max(0, min(ymin, s.in_h));
-    cnt = max(0, min(min(cnt, a.stride), s.in_h - ymin));
-    const int* k = bounds + 2 * s.out_h + (int64_t)yo * a.stride;
+    int ymin, cnt;
+    const int* k = pil_vtaps(bounds, bounds + 2 * s.out_h, a.stride, s.in_h, yo, &ymin, &cnt);
     const uint8_t* p = s.src + (int64_t)ymin * s.row_bytes + 4 * q;
     int acc[4];
 #pragma unroll
@@ -248,44 +140,16 @@ __global__ __launch_bounds__(256) void vpass_f32_kernel(const FArgs a, const int
     const int yo = fy % OUT;
     const FSample& s = a.s[fy / OUT];
     const int* bounds = ws + s.tab;
-    int ymin = bounds[2 * yo], cnt = bounds[2 * yo + 1];
-    ymin = max(0, min(ymin, s.in_h));
-    cnt = max(0, min(min(cnt, a.stride), s.in_h - ymin));
-    const int* k = bounds + 2 * OUT + (int64_t)yo * a.stride;
+    int ymin, cnt;
+    const int* k = pil_vtaps(bounds, bounds + 2 * OUT, a.stride, s.in_h, yo, &ymin, &cnt);
     const int qs = s.flip ? PER - 1 - q : q;      // source group of this output group
-    const uint8_t* p = s.src + ((int64_t)ymin * OUT + (int64_t)qs * 4) * 3;
     int acc[12];
-#pragma unroll
-    for (int e = 0; e < 12; ++e) acc[e] = 1 << (PRECISION_BITS - 1);
-    for (int j = 0; j < cnt; ++j, p += OUT * 3) {
-      const int w = k[j];
-      const uint32_t* p4 = reinterpret_cast<const uint32_t*>(p);      // (12 qs bytes into a row of 1152 bytes of a 16-byte aligned buffer)
-      const uint32_t w0 = p4[0], w1 = p4[1], w2 = p4[2];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        acc[e] += (int)((w0 >> (8 * e)) & 255u) * w;
-        acc[4 + e] += (int)((w1 >> (8 * e)) & 255u) * w;
-        acc[8 + e] += (int)((w2 >> (8 * e)) & 255u) * w;
-      }
-    }
-    float v[12];
-#pragma unroll
-    for (int e = 0; e < 12; ++e) v[e] = (float)clip8(acc[e]) / 255.0f;      // ToTensor: a correctly rounded division, not x * (1 / 255)
-    // acc[e] is byte e of the 12: source pixel e / 3, channel e % 3; a flipped sample stores the four pixels in reverse order
-    float* o = out + (int64_t)s.row * 3 * plane + (int64_t)yo * OUT + (int64_t)q * 4;
-    if (s.flip) {
-      *reinterpret_cast<float4*>(o) = make_float4(v[9], v[6], v[3], v[0]);
-      *reinterpret_cast<float4*>(o + plane) = make_float4(v[10], v[7], v[4], v[1]);
-      *reinterpret_cast<float4*>(o + 2 * plane) = make_float4(v[11], v[8], v[5], v[2]);
-    } else {
-      *reinterpret_cast<float4*>(o) = make_float4(v[0], v[3], v[6], v[9]);
-      *reinterpret_cast<float4*>(o + plane) = make_float4(v[1], v[4], v[7], v[10]);
-      *reinterpret_cast<float4*>(o + 2 * plane) = make_float4(v[2], v[5], v[8], v[11]);
-    }
+    // (12 qs bytes into a row of 1152 bytes of a 16-byte aligned buffer)
+    pil_vacc<12>(s.src + ((int64_t)ymin * OUT + (int64_t)qs * 4) * 3, OUT * 3, k, cnt, acc);
+    pil_store_planes<12>(out + (int64_t)s.row * 3 * plane + (int64_t)yo * OUT + (int64_t)q * 4, plane, acc, s.flip != 0);
   }
 }
 
-int blocks_for(int64_t threads) { return (int)max((int64_t)1, min((int64_t)MAX_BLOCKS, (threads + 255) / 256)); }
 int64_t pad16(int64_t n) { return (n + 15) & ~(int64_t)15; }
 
 // Where everything of a group lives: the four tables of every sample in the table workspace (ints), and in the byte workspace the
@@ -339,21 +203,12 @@ bool fail(const char* fn, const char* why) {
   return false;
 }
 
-// output pixels per horizontal work item: the source bytes of a tile (+ alignment slack) must fit the LDS staging buffer
-int tile_of(int in_size, int out_size, int filter) {
-  const Axis ax = axis_of(filter, in_size, out_size);
-  int tile = 256;
-  while (tile >= 1 && ((int64_t)ceil(ax.scale * (tile - 1)) + ax.ksize + 1) * 3 + 48 > STAGE_BYTES) tile >>= 1;
-  return tile;
-}
-
 }  // namespace
 
 extern "C" int countr_pil_tables(int filter, int in_size, int out_size, int* bounds, int* weights) {
   if (filter != 0 && filter != 1) { countr_set_error("countr_pil_tables: filter is 0 (bilinear) or 1 (bicubic)"); return -1; }
-  if (in_size < 1 || out_size < 1) { countr_set_error("countr_pil_tables: sizes must be >= 1 (and in / out below 2^19)"); return -1; }
-  const Axis ax = axis_of(filter, in_size, out_size);
-  if (ax.ksize > 1 << 20) { countr_set_error("countr_pil_tables: sizes must be >= 1 (and in / out below 2^19)"); return -1; }
+  Axis ax;
+  if (!axis_ok(filter, in_size, out_size, &ax)) { countr_set_error("countr_pil_tables: sizes must be >= 1 (and in / out below 2^19)"); return -1; }
   if (!bounds && !weights) return ax.ksize;
   if (!bounds || !weights) { countr_set_error("countr_pil_tables: pass both tables, or neither to ask for the tap stride"); return -1; }
   for (int xx = 0; xx < out_size; ++xx) table_row(filter, ax, in_size, xx, ax.ksize, bounds, weights);
@@ -383,7 +238,7 @@ extern "C" int countr_pretrain_aug_tables(const countr_pretrain_image* imgs, int
       a.rows += j.out_size;
     }
   }
-  hipLaunchKernelGGL(tables_kernel, dim3(blocks_for(a.rows)), dim3(256), 0, STREAM(stream), a, tables);
+  hipLaunchKernelGGL(tables_kernel, dim3(countr_blocks_for(a.rows, MAX_BLOCKS)), dim3(256), 0, STREAM(stream), a, tables);
   COUNTR_LAUNCH_CHECK("countr_pretrain_aug_tables");
 }
 
@@ -450,8 +305,8 @@ extern "C" int countr_pretrain_aug(const countr_pretrain_image* imgs, int n, con
   }
   // the launch count is fixed: a pass with no work in this group (every sample skips it) still launches one idle block
   hipLaunchKernelGGL(hpass_kernel, dim3(max(1, min(MAX_BLOCKS, h1.items))), dim3(256), 0, STREAM(stream), h1, tables);
-  hipLaunchKernelGGL(vpass_u8_kernel, dim3(blocks_for(v1.total)), dim3(256), 0, STREAM(stream), v1, tables);
+  hipLaunchKernelGGL(vpass_u8_kernel, dim3(countr_blocks_for(v1.total, MAX_BLOCKS)), dim3(256), 0, STREAM(stream), v1, tables);
   hipLaunchKernelGGL(hpass_kernel, dim3(max(1, min(MAX_BLOCKS, h2.items))), dim3(256), 0, STREAM(stream), h2, tables);
-  hipLaunchKernelGGL(vpass_f32_kernel, dim3(blocks_for((int64_t)n * OUT * (OUT / 4))), dim3(256), 0, STREAM(stream), f, tables, out);
+  hipLaunchKernelGGL(vpass_f32_kernel, dim3(countr_blocks_for((int64_t)n * OUT * (OUT / 4), MAX_BLOCKS)), dim3(256), 0, STREAM(stream), f, tables, out);
   COUNTR_LAUNCH_CHECK(fn);
 }

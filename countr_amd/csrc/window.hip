@@ -8,8 +8,6 @@
 #include "common.hpp"
 #include "../../include/countr_hip.h"
 
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 namespace {
 
 constexpr int WIN = 384;

@@ -29,30 +29,29 @@ def scale_boxes(boxes_xyxy, W, H):
     return [[int(y1 * sh), int(x1 * sw), int(y2 * sh), int(x2 * sw)] for x1, y1, x2, y2 in boxes_xyxy]
 
 
-def pil_tables(in_size, out_size):
-    """(ksize, bounds int32 [out, 2], weights int32 [out, ksize]) of countr_pil_bilinear_tables, as numpy arrays."""
-    L = _lib.lib()
-    ksize = L.countr_pil_bilinear_tables(in_size, out_size, None, None)
-    _lib.check(min(ksize, 0), "countr_pil_bilinear_tables")
-    bounds = np.empty((out_size, 2), np.int32)
-    weights = np.empty((out_size, ksize), np.int32)
-    _lib.check(min(L.countr_pil_bilinear_tables(in_size, out_size, bounds.ctypes.data, weights.ctypes.data), 0), "countr_pil_bilinear_tables")
-    return ksize, bounds, weights
-
-
 BILINEAR, BICUBIC = 0, 1   # countr_pil_tables' filters
 
 
-def pil_filter_tables(filter, in_size, out_size):
-    """(ksize, bounds int32 [out, 2], weights int32 [out, ksize]) of countr_pil_tables for BILINEAR or BICUBIC, as numpy arrays.  The
-    bicubic weights have negative lobes: a pixel's sum is shifted arithmetically and then clamped to 0..255."""
-    L = _lib.lib()
-    ksize = L.countr_pil_tables(filter, in_size, out_size, None, None)
-    _lib.check(min(ksize, 0), "countr_pil_tables")
-    bounds = np.empty((out_size, 2), np.int32)
-    weights = np.empty((out_size, ksize), np.int32)
-    _lib.check(min(L.countr_pil_tables(filter, in_size, out_size, bounds.ctypes.data, weights.ctypes.data), 0), "countr_pil_tables")
+def _tables(export, *args):
+    """(ksize, bounds int32 [out, 2], weights int32 [out, ksize]) of a host table export (..., in_size, out_size, bounds, weights)."""
+    fn = getattr(_lib.lib(), export)
+    ksize = fn(*args, None, None)
+    _lib.check(min(ksize, 0), export)
+    bounds = np.empty((args[-1], 2), np.int32)
+    weights = np.empty((args[-1], ksize), np.int32)
+    _lib.check(min(fn(*args, bounds.ctypes.data, weights.ctypes.data), 0), export)
     return ksize, bounds, weights
+
+
+def pil_tables(in_size, out_size):
+    """The tables of countr_pil_bilinear_tables, as numpy arrays: equal to pil_filter_tables(BILINEAR, ...), through the older export."""
+    return _tables("countr_pil_bilinear_tables", in_size, out_size)
+
+
+def pil_filter_tables(filter, in_size, out_size):
+    """The tables of countr_pil_tables for BILINEAR or BICUBIC, as numpy arrays.  The bicubic weights have negative lobes: a pixel's sum
+    is shifted arithmetically and then clamped to 0..255."""
+    return _tables("countr_pil_tables", filter, in_size, out_size)
 
 
 def _stream(device):
@@ -132,7 +131,7 @@ class FramePrep:
     def tables(self, in_size, out_size):
         t = self._tables.get((in_size, out_size))
         if t is None:
-            _k, bounds, weights = pil_tables(in_size, out_size)
+            _k, bounds, weights = pil_filter_tables(BILINEAR, in_size, out_size)
             t = self._tables[(in_size, out_size)] = (torch.from_numpy(bounds).to(self.device), torch.from_numpy(weights).to(self.device))
         return t
 

@@ -456,13 +456,13 @@ int countr_aug_window(const countr_aug_image* imgs, int n, float* out, void* str
  * double, mode "reflect" (the edge sample repeats), axis 0 into an fp32 intermediate, then axis 1.  One launch. */
 int countr_aug_density(const countr_aug_image* imgs, int n, const int* cells, int ncells, float* out, void* stream);
 /* countr_aug_exemplars: out [n, 3, 3, 64, 64] (16-byte aligned) <- the three rectangles of every src, each resized as
- * countr_crop_resize_f32 resizes it (same arithmetic), in one launch for the batch. */
+ * countr_crop_resize_f32 resizes it (same formula; fp contraction off here, on there), in one launch for the batch. */
 int countr_aug_exemplars(const countr_aug_image* imgs, int n, float* out, void* stream);
 
 /* ---- the mosaic branch of that augmentation on the device (csrc/mosaic.hip; an additive export with a descriptor of its own:
  * countr_aug_image keeps its layout and the ABI version stays 9).  The oracle is fsc147.mosaic() with _blend_pair: piece k is the
  * length x length crop at (start_h, start_w) of a clean resized frame, resized to resize_l x resize_l, resize_l = 192 + 2 bl, as
- * F.interpolate(mode="bilinear", align_corners=False) resizes it (countr_crop_resize_f32's arithmetic).  Pieces 0 / 1 are joined along
+ * F.interpolate(mode="bilinear", align_corners=False) resizes it (countr_crop_resize_f32's formula, contraction off).  Pieces 0 / 1 are joined along
  * the rows into the left half and 2 / 3 into the right half, the two halves along the columns: the 192-line cores are put side by side,
  * then line 192 + i takes weight (i + bl) / (2 bl) and the first piece's line resize_l - 1 - bl + i the weight (bl - i) / (2 bl), line
  * 191 - i mixes with the second piece's line bl - i in the same way, i < bl (index_select's own lines: the asymmetry is the

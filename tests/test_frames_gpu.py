@@ -78,6 +78,20 @@ def test_frame_resize_scalar_path_odd_width(hip):
         assert torch.equal(got.cpu(), want)
 
 
+def test_frame_resize_wide_frame_halves_the_horizontal_tile(hip):
+    """2400 -> 100 columns: scale 24 and 49 taps, so 256 output pixels would stage (ceil(24 * 255) + 49 + 1) * 3 + 48 = 18 558 bytes of a
+    row and the 16 384-byte staging buffer takes 128 per work item instead -- with 16-byte loads (aligned frame) and without."""
+    H_, W_, oh, ow = 8, 2400, 4, 100
+    for f in make_frames(H_, W_):
+        want = pil_path(f, ow, oh)
+        got = raw_resize(hip, [torch.from_numpy(f).cuda()], oh, ow)[0]
+        assert torch.equal(got.cpu(), want)
+        buf = torch.empty(H_ * W_ * 3 + 1, dtype=torch.uint8, device="cuda")
+        buf[1:].copy_(torch.from_numpy(f).cuda().view(-1))
+        got = raw_resize(hip, [buf[1:].view(H_, W_, 3)], oh, ow)[0]
+        assert torch.equal(got.cpu(), want)
+
+
 def test_frame_resize_batched_eight_and_side_stream(hip):
     from countr_amd.frames import FramePrep
     frames = [make_frames(1080, 1920, seed=k)[0] for k in range(7)] + [make_frames(1080, 1920)[1]]

@@ -168,6 +168,25 @@ def test_unaligned_frames(hip):
     assert torch.equal(got, want), _differing(got, want)
 
 
+def test_wide_crop_halves_the_horizontal_tile(hip):
+    """A 16 x 8208 frame (both multiples of 16: stage 1 is skipped) with the crop 16 x 8100: the bicubic horizontal pass runs at scale
+    21.09 with 87 taps, 256 output pixels would stage (ceil(21.09 * 255) + 87 + 1) * 3 + 48 = 16 449 bytes of a row and the 16 384-byte
+    staging buffer takes 128 per work item instead.  Flip off and on."""
+    from countr_amd.data import fsc147 as D
+    from countr_amd.pretrain_aug import PretrainAug
+    H, W, crop = 16, 8208, (0, 0, 16, 8100)
+    image = _image(H, W, salt=5000)
+    recipes, want = [], []
+    for flip in (False, True):
+        rec = D.recipe_pretrain(image, Scripted(H, W, crop, flip))
+        assert rec["crop"] == crop and rec["flip"] == flip
+        recipes.append(rec)
+        want.append(D.transform_pretrain(image, Scripted(H, W, crop, flip)))
+    got = PretrainAug("cuda").batch(recipes).cpu()
+    want = torch.stack(want)
+    assert torch.equal(got, want), _differing(got, want)
+
+
 def test_batch_on_the_step_stream_feeds_the_step(hip):
     """batch() inside PretrainStep.on_stream(), then load + step: the loss of the step equals the one from the host-built tensor."""
     from countr_amd.data import fsc147 as D
