@@ -5,7 +5,9 @@
 loaded as TestData does (countr_amd/data/fsc147.py::test_item, pinned against the reference class in tests/golden/data_test.npz;
 `--external`: the split's own exemplar crops, cut to --box_bound, serve every image -- :96-129).
 Without a dataset (none is available offline) `--synthetic N` evaluates N synthetic wide images through the same
-sliding-window / stitching / normalisation code (countr_amd/inference.py)."""
+sliding-window / stitching / normalisation code (countr_amd/inference.py).
+`--report` writes the reference's evaluation report into --output_dir (:379-453: full_<stem>__<count>.png and boxes_<stem>.png per image,
+results.csv, log.txt, test_stat.png), composed on the device (countr_amd/report.py); without it nothing is written."""
 import argparse
 import json
 import os
@@ -49,6 +51,8 @@ def get_args_parser():
     p.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "fp16"], help="the reference tests in fp32")
     p.add_argument("--synthetic", default=0, type=int, help="evaluate N synthetic images instead of FSC147")
     p.add_argument("--group_images", default=8, type=int, help="images whose sliding windows share forward batches (up to 32 windows each)")
+    p.add_argument("--report", action="store_true", help="write the reference's evaluation report (pictures, results.csv, log.txt, test_stat.png) into --output_dir")
+    p.add_argument("--report_workers", default=4, type=int, help="threads that encode the report's PNGs (at most 8)")
     return p
 
 
@@ -69,7 +73,15 @@ def main(args):
             k = 3 if args.box_bound < 0 else min(args.box_bound, 3)
             boxes = torch.from_numpy(rs.uniform(0, 1, size=(k, 3, 64, 64)).astype(np.float32)) if k else torch.zeros(0)
             pos = [(10 * j, 10 * j, 10 * j + 40, 10 * j + 40) for j in range(k)]
-            items.append(("synthetic_%d" % i, img, boxes, pos, int(rs.randint(5, 200))))
+            gt_cnt = int(rs.randint(5, 200))
+            gt_map = None
+            if args.report:       # a generator of its own: the images and counts above are those of a run without --report
+                from scipy import ndimage
+                ds = np.random.RandomState(args.seed + 1000003 * (i + 1))
+                dots = np.zeros((384, w), dtype=np.float32)
+                dots[ds.randint(0, 384, gt_cnt), ds.randint(0, w, gt_cnt)] = 1
+                gt_map = torch.from_numpy(ndimage.gaussian_filter(dots, sigma=(1, 1), order=0)) * 60
+            items.append(("synthetic_%d" % i, img, boxes, pos, gt_cnt, gt_map))
     else:
         from countr_amd.data import fsc147
         annotations = json.load(open(os.path.join(args.data_path, args.anno_file)))
@@ -79,28 +91,41 @@ def main(args):
         if args.external:     # FSC_test_cross(few-shot).py:96-129: the split's own exemplar crops, cut to --box_bound, for every image
             ext = fsc147.external_exemplars(annotations, split, im_dir, args.box_bound)
         for im_id in split:
-            img, dots, boxes, pos, _gt_map = fsc147.test_item(annotations, im_dir, im_id, args.box_bound, ext)
-            items.append((im_id, img, boxes, [tuple(r) for r in pos], dots.shape[0]))
+            img, dots, boxes, pos, gt_map = fsc147.test_item(annotations, im_dir, im_id, args.box_bound, ext)
+            items.append((im_id, img, boxes, [tuple(r) for r in pos], dots.shape[0], gt_map if args.report else None))
     from countr_amd.parallel import shard_batch
     lo, hi = shard_batch(len(items), misc.get_rank(), misc.get_world_size())   # replicas only: images sharded, no collective
     mae = rmse = nae = 0.0
     # windows are batched ACROSS images (every 384-px window is an independent forward): groups of --group_images images go
     # through inference.count_images together
     mine = items[lo:hi]
+    writer = None
+    if args.report:      # every rank writes the pictures of its own images; rank 0 writes the summary files (of its shard, as the reference's does)
+        from countr_amd.report import ReportItem, ReportWriter
+        writer = ReportWriter(args.output_dir, workers=args.report_workers, external=args.external, summary=misc.is_main_process())
     t0 = time.time()
     preds = []
     for g0 in range(0, len(mine), args.group_images):
         grp = mine[g0:g0 + args.group_images]
-        its = [(img.unsqueeze(0).to(device), boxes.unsqueeze(0).to(device), pos) for _name, img, boxes, pos, _gt in grp]
-        preds += [p for p, _dm in inference.count_images(model, its, normalization=bool(args.normalization), max_s_cnt=args.max_s_cnt)]
+        its = [(img.unsqueeze(0).to(device), boxes.unsqueeze(0).to(device), pos) for _name, img, boxes, pos, _gt, _map in grp]
+        if writer is None:
+            preds += [p for p, _dm in inference.count_images(model, its, normalization=bool(args.normalization), max_s_cnt=args.max_s_cnt)]
+            continue
+        res = inference.count_images(model, its, normalization=bool(args.normalization), max_s_cnt=args.max_s_cnt, return_crops=True)
+        preds += [r[0] for r in res]
+        for c0 in range(0, len(grp), 16):      # (a report launch takes 16 images); the encodes overlap the next group's forward
+            writer.add_group([ReportItem(name, s, b, pos, gt_cnt, gt_map) for (name, _i, _b, pos, gt_cnt, gt_map), (s, b, _p)
+                              in zip(grp[c0:c0 + 16], its[c0:c0 + 16])], res[c0:c0 + 16])
     torch.cuda.synchronize()
     t_inf = time.time() - t0
-    for (name, _img, _boxes, _pos, gt_cnt), pred in zip(mine, preds):
+    for (name, _img, _boxes, _pos, gt_cnt, _map), pred in zip(mine, preds):
         err = abs(pred - gt_cnt)
         mae += err; rmse += err ** 2; nae += err / gt_cnt if gt_cnt > 0 else 0
         print("%s: pred_cnt: %5.3f, gt_cnt: %5.3f, error: %5.3f" % (name, pred, gt_cnt, err))
     n = max(hi - lo, 1)
     print(json.dumps({"MAE": mae / n, "RMSE": (rmse / n) ** 0.5, "NAE": nae / n, "images": hi - lo, "mean_infer_time_s": t_inf / n}))
+    if writer is not None:
+        writer.close(timing={"Mean infer time": t_inf / n, "Mean overall time": (time.time() - t0) / n})
 
 
 if __name__ == "__main__":

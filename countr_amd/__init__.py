@@ -1,4 +1,4 @@
-"""CounTR on the MI355X.  The raw-frame entry points and the device augmentation are re-exported here; they load on first use so that `import countr_amd` (the
+"""CounTR on the MI355X.  The raw-frame entry points, the device augmentation and the evaluation report are re-exported here; they load on first use so that `import countr_amd` (the
 build, the CPU tools) stays free of torch."""
 
 
@@ -15,4 +15,7 @@ def __getattr__(name):
     if name == "PretrainAug":
         from . import pretrain_aug
         return pretrain_aug.PretrainAug
+    if name in ("ReportWriter", "ReportItem", "compose_host", "exemplar_strip_host"):
+        from . import report
+        return getattr(report, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

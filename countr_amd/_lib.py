@@ -73,8 +73,26 @@ class PretrainImage(C.Structure):
                 ("flip", C.c_int), ("row", C.c_int)]
 
 
+class ReportPatch(C.Structure):
+    """countr_report_patch: a host-rasterised label / text raster of the report blob and where it lies in the image (csrc/report.hip)."""
+    _fields_ = [("off", C.c_int64), ("px", C.c_int), ("py", C.c_int), ("pw", C.c_int), ("ph", C.c_int)]
+
+
+class ReportImage(C.Structure):
+    """countr_report_image: one image of a report group."""
+    _fields_ = [("sam", C.c_void_p), ("maps", C.c_void_p * 9), ("gt", C.c_void_p), ("out_off", C.c_int64),
+                ("w", C.c_int), ("layout", C.c_int), ("grid", C.c_int), ("rect_off", C.c_int), ("rect_cnt", C.c_int),
+                ("labels", ReportPatch), ("text", ReportPatch)]
+
+
+class ReportStrip(C.Structure):
+    """countr_report_strip: the exemplars of one image of a report group."""
+    _fields_ = [("ex", C.c_void_p), ("out_off", C.c_int64), ("S", C.c_int)]
+
+
 AUG_MAX_IMAGES = 32
 PRETRAIN_MAX_IMAGES = 16
+REPORT_MAX_IMAGES = 16
 _libs = {}
 
 
@@ -190,6 +208,9 @@ _SIGS = {
     "countr_carpk_prep_u8": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "countr_carpk_count_blocks": [_i, _i],
     "countr_carpk_count": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "countr_report_panels": [_vp, _i, _i, _vp, _i64, _i64, _i, _vp, _i64, _vp],
+    "countr_report_strip_shape": [_i, _i, _i, _vp],
+    "countr_report_quantize": [_vp, _i, _i, _i, _vp, _i64, _vp],
     "countr_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp],
 }
 _RESTYPES = {"countr_xattn_bwd_workspace_floats": C.c_int64, "countr_groupnorm_bwd_image_sums_offset": C.c_int64}

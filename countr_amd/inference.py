@@ -289,9 +289,12 @@ def _normalise(pred, dm, pos, normalization):
 
 
 @torch.no_grad()
-def count_image(model, samples, boxes, shot_num, pos=None, normalization=True, max_s_cnt=1, max_batch=32):
-    """Full per-image test path: returns (pred_cnt, density_map).  pos: exemplar rectangles [(y1, x1, y2, x2), ...]."""
+def count_image(model, samples, boxes, shot_num, pos=None, normalization=True, max_s_cnt=1, max_batch=32, return_crops=False):
+    """Full per-image test path: returns (pred_cnt, density_map).  pos: exemplar rectangles [(y1, x1, y2, x2), ...].
+    return_crops=True: (pred_cnt, density_map, crops) -- crops = the nine maps of the 3x3 path in the reference's list order (the report's
+    misc.make_grid tiles them; density_map is the last of them), or None when the image did not take that path."""
     _, _, h, w = samples.shape
+    dms = None
     if pos is not None and _small_exemplars(pos) >= max_s_cnt:
         # 3x3 split: each crop is upscaled back to (h, w) and counted on its own (FSC_test_cross(few-shot).py:273-320); the nine
         # upscaled crops are nine independent images for the stitcher, so all their windows share forwards
@@ -306,20 +309,22 @@ def count_image(model, samples, boxes, shot_num, pos=None, normalization=True, m
     else:
         dm = density_map(model, samples, boxes, shot_num, max_batch)
         pred = (dm.sum() / 60).item()
-    return _normalise(pred, dm, pos, normalization), dm
+    pred = _normalise(pred, dm, pos, normalization)
+    return (pred, dm, dms) if return_crops else (pred, dm)
 
 
 @torch.no_grad()
-def count_images(model, items, normalization=True, max_s_cnt=1, max_batch=32):
+def count_images(model, items, normalization=True, max_s_cnt=1, max_batch=32, return_crops=False):
     """Test path over MANY images with windows batched across images: items = [(samples [1,3,384,w], boxes [1,S,3,64,64] or
     empty, pos or None), ...] -> [(pred_cnt, density_map), ...] in input order.  Images are grouped by shot count (one forward
-    has one shot_num, models_mae_cross.py:201); images that take the 3x3 split path already fill batches on their own."""
+    has one shot_num, models_mae_cross.py:201); images that take the 3x3 split path already fill batches on their own.
+    return_crops=True: (pred_cnt, density_map, crops) per image, crops as count_image returns them."""
     res = [None] * len(items)
     groups = {}
     for idx, (samples, boxes, pos) in enumerate(items):
         S = boxes.shape[1] if boxes.nelement() > 0 else 0
         if pos is not None and _small_exemplars(pos) >= max_s_cnt:
-            res[idx] = count_image(model, samples, boxes, S, pos, normalization, max_s_cnt, max_batch)
+            res[idx] = count_image(model, samples, boxes, S, pos, normalization, max_s_cnt, max_batch, return_crops)
         else:
             groups.setdefault(S, []).append(idx)
     for S, idxs in groups.items():
@@ -335,5 +340,6 @@ def count_images(model, items, normalization=True, max_s_cnt=1, max_batch=32):
         stream = density_maps_stream(model, (([items[i][0] for i in sel], [items[i][1] for i in sel]) for sel in chunks), S, max_batch)
         for sel, dms in zip(chunks, stream):
             for i, dm in zip(sel, dms):
-                res[i] = (_normalise((dm.sum() / 60).item(), dm, items[i][2], normalization), dm)
+                pred = _normalise((dm.sum() / 60).item(), dm, items[i][2], normalization)
+                res[i] = (pred, dm, None) if return_crops else (pred, dm)
     return res

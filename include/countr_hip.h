@@ -542,6 +542,55 @@ int countr_carpk_prep_u8(const void* const* frames, const int* shapes, int n, co
 int countr_carpk_count_blocks(int H, int W);
 int countr_carpk_count(const float* maps, int n, int H, int W, const int* rects, float* out, float* workspace, void* stream);
 
+/* ---- the evaluation report of FSC_test_cross(few-shot).py:379-425 (csrc/report.hip; additive exports, the ABI version stays 9).
+ * countr_report_panels: the `full_*.png` picture of n (1..COUNTR_REPORT_MAX_IMAGES) images of one height h, widths free per image, in ONE
+ *   launch: image i's panel uint8 [h, P w, 3] (HWC, what PIL encodes) at out + imgs[i].out_off, P = imgs[i].layout.  Per pixel, in fp32,
+ *   every product and sum rounded on its own, in the script's operation order (s = the sample's channel, p = pred, g = gt):
+ *     pred_img = (p, p, 0), gt_img = (g, 0, 0), fp = pred_img where gt_img - pred_img < -0.01, else 0
+ *     tp_img  = s 0.6 + (pred_img - fp)[[1, 0, 2]]                (not clamped)
+ *     mix2    = s 0.6 + |clamp01(pred_img) - clamp01(gt_img)|
+ *     sam_box = clamp01(s + box + labels)                          (box, labels: 0..255 as the script adds them, NOT scaled)
+ *     den_pr  = clamp01(s 0.6 + text + pred_img)
+ *   layout 3 (gt_cnt != 0): [mix2 | sam_box | tp_img]; layout 2 (gt_cnt == 0): [sam_box without labels | den_pr].
+ *   Every value is quantised as torchvision's save_image does: x 255 + 0.5, clamped to [0, 255], truncated.
+ *   box: 255 on the outline of every rectangle of the image (cv2.rectangle, thickness 1: y in {y1, y2}, x1 <= x <= x2 or x in {x1, x2},
+ *   y1 <= y <= y2, clipped to the image; corners in either order), rectangles rects[rect_off .. rect_off + rect_cnt) of the blob.
+ *   pred: the stitched map, or (grid != 0) the nine maps of the 3 x 3 path tiled row-major in list order and resized [3 h, 3 w] -> [h, w]
+ *   with bilinear, align_corners=False, no antialias: the source coordinate is 3 d + 1 with weight 1 on one tap, so
+ *   pred[y, x] = maps[3 (Y / h) + X / w][Y % h, X % w] at Y = 3 y + 1, X = 3 x + 1, exactly.
+ *   labels / text: a uint8 [ph, pw, 3] raster of the blob whose top-left pixel lies at (px, py) of the image; it may hang over any edge
+ *   (only the pixels inside the image are read), pw = 0: none.  layout 3 reads `labels`, layout 2 reads `text`.
+ *   blob: ONE device buffer the caller uploads per group: int32 rectangles {y1, x1, y2, x2} at byte rects_off, patch rasters at their
+ *   `off`.  imgs is a HOST array read at call time; every offset is checked against blob_bytes / out_bytes, panels must not overlap, and
+ *   nothing is launched when a check fails.  16-byte loads and 4-byte stores when w % 4 == 0 and the image's buffers are aligned, one pixel
+ *   at a time otherwise.  Nothing is allocated.
+ * countr_report_quantize: the `boxes_*.png` picture of n (1..16) exemplar sets: strips[i].ex fp32 [S, 3, eh, ew] -> uint8 [GH, GW, 3] at
+ *   out + strips[i].out_off = save_image's grid (torchvision make_grid: 8 per row, padding 2, pad value 0; S = 1 is the exemplar itself,
+ *   no padding), quantised as above.  countr_report_strip_shape gives {GH, GW}.  ONE launch. */
+#define COUNTR_REPORT_MAX_IMAGES 16
+typedef struct countr_report_patch {
+  int64_t off;           /* first byte of the raster in the blob */
+  int px, py, pw, ph;    /* position of its top-left pixel in the image, and its size (pw = 0 or ph = 0: no raster) */
+} countr_report_patch;
+typedef struct countr_report_image {
+  const float* sam;      /* the sample, fp32 [3, h, w] */
+  const float* maps[9];  /* maps[0]: the stitched map fp32 [h, w]; grid != 0: the nine maps of the 3 x 3 path */
+  const float* gt;       /* the ground-truth map, fp32 [h, w] */
+  int64_t out_off;       /* first byte of the panel in out */
+  int w, layout, grid;   /* width, 3 or 2 panels, 3 x 3 path */
+  int rect_off, rect_cnt;
+  countr_report_patch labels, text;
+} countr_report_image;
+typedef struct countr_report_strip {
+  const float* ex;       /* fp32 [S, 3, eh, ew] */
+  int64_t out_off;
+  int S;
+} countr_report_strip;
+int countr_report_panels(const countr_report_image* imgs, int n, int h, const void* blob, int64_t blob_bytes, int64_t rects_off,
+                         int nrects, void* out, int64_t out_bytes, void* stream);
+int countr_report_strip_shape(int S, int eh, int ew, int* shape);
+int countr_report_quantize(const countr_report_strip* strips, int n, int eh, int ew, void* out, int64_t out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
