@@ -3,9 +3,12 @@ build, the CPU tools) stays free of torch."""
 
 
 def __getattr__(name):
-    if name in ("count_frames", "FramePrep"):
+    if name in ("count_frames", "locate_frames", "FramePrep"):
         from . import frames
         return getattr(frames, name)
+    if name in ("PeakFinder", "peaks_host", "Peaks"):
+        from . import peaks
+        return getattr(peaks, name)
     if name in ("count_carpk", "CarpkPrep"):
         from . import carpk
         return getattr(carpk, name)

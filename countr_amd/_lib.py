@@ -90,9 +90,15 @@ class ReportStrip(C.Structure):
     _fields_ = [("ex", C.c_void_p), ("out_off", C.c_int64), ("S", C.c_int)]
 
 
+class PeakMap(C.Structure):
+    """countr_peak_map: one density map of a countr_density_peaks call (csrc/peaks.hip)."""
+    _fields_ = [("map", C.c_void_p), ("h", C.c_int), ("w", C.c_int)]
+
+
 AUG_MAX_IMAGES = 32
 PRETRAIN_MAX_IMAGES = 16
 REPORT_MAX_IMAGES = 16
+PEAKS_MAX_MAPS = 16
 _libs = {}
 
 
@@ -211,6 +217,8 @@ _SIGS = {
     "countr_report_panels": [_vp, _i, _i, _vp, _i64, _i64, _i, _vp, _i64, _vp],
     "countr_report_strip_shape": [_i, _i, _i, _vp],
     "countr_report_quantize": [_vp, _i, _i, _i, _vp, _i64, _vp],
+    "countr_peaks_workspace": [_i, _i, _i, _i],
+    "countr_density_peaks": [_vp, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp],
     "countr_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp],
 }
 _RESTYPES = {"countr_xattn_bwd_workspace_floats": C.c_int64, "countr_groupnorm_bwd_image_sums_offset": C.c_int64}

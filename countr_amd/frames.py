@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, inference
+from . import _lib, inference, peaks
 
 NEW_H = 384
 BOX = 64                    # exemplar crops are 64 x 64 (demo.py:67)
@@ -255,3 +255,105 @@ def count_frames(model, frames, boxes=None, normalization=True, max_s_cnt=1, max
     counted as inference.count_images counts them -- one forward per <= max_batch windows, the encoder pipelined across groups."""
     device = next(model.parameters()).device
     return count_items(model, prepare_items(device, frames, boxes), normalization, max_s_cnt, max_batch)
+
+
+def frame_points(cy, cx, W, H, new_w):
+    """Centroids (cy, cx) of the resized [384, new_w] map -> (x, y) in pixel-centre coordinates of the ORIGINAL W x H frame, in float64:
+    x = (cx + 0.5) W / new_w - 0.5, y = (cy + 0.5) H / 384 - 0.5."""
+    cy, cx = np.asarray(cy, np.float64), np.asarray(cx, np.float64)
+    return (cx + 0.5) * W / new_w - 0.5, (cy + 0.5) * H / NEW_H - 0.5
+
+
+def crop_points(cy, cx, k, h, w):
+    """Centroids of crop k of the 3 x 3 split (the crop was upscaled from h // 3 x w // 3 back to h x w) -> (cy, cx) of the [h, w] image
+    the crops were cut from: cy_img = top + (cy + 0.5) (h // 3) / h - 0.5 with split_rects(h, w)[k] = (top, left, ., .), cx likewise."""
+    top, left = split_rects(h, w)[k][:2]
+    cy, cx = np.asarray(cy, np.float64), np.asarray(cx, np.float64)
+    return top + (cy + 0.5) * (h // 3) / h - 0.5, left + (cx + 0.5) * (w // 3) / w - 0.5
+
+
+def _keep_count(P, count, keep):
+    if keep == "all":
+        return P
+    if keep != "count":
+        raise ValueError('keep is "all" or "count"')
+    return min(P, max(0, int(np.floor(count + 0.5))))
+
+
+def locate_maps(results, sizes, crops=None, *, radius=4, threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all"):
+    """The points of counted frames: results [(count, density map [384, new_W] on the device), ...], sizes [(W, H), ...] of the original
+    frames, crops per frame None or the nine maps of the 3 x 3 path -> [(points float32 [P, 2] as (x, y), score [P], total), ...].
+    Every map of the call (the nine crop maps of a split frame included) goes through ONE PeakFinder.find."""
+    crops = crops or [None] * len(results)
+    maps, first = [], []
+    for (_c, dm), cr in zip(results, crops):
+        first.append(len(maps))
+        maps.extend(cr if cr is not None else [dm])
+    if not maps:
+        return []
+    maps = [m if (m.dtype == torch.float32 and m.is_contiguous()) else m.float().contiguous() for m in maps]
+    found = peaks.peak_finder(maps[0].device).find(maps, radius, threshold, rel_threshold, max_points)
+    out = []
+    for (count, dm), (W, H), cr, f0 in zip(results, sizes, crops, first):
+        h, w = dm.shape
+        if cr is None:
+            pk = found[f0]
+            cy, cx, score, total = pk.centroid[:, 0], pk.centroid[:, 1], pk.score, pk.total
+        else:
+            nine = found[f0:f0 + 9]
+            parts = [crop_points(pk.centroid[:, 0], pk.centroid[:, 1], k, h, w) for k, pk in enumerate(nine)]
+            cy, cx = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+            score = np.concatenate([pk.score for pk in nine])
+            crop = np.concatenate([np.full(len(pk.score), k) for k, pk in enumerate(nine)])
+            idx = np.concatenate([pk.yx[:, 0].astype(np.int64) * w + pk.yx[:, 1] for pk in nine])
+            order = np.lexsort((idx, crop, -score))                    # (score descending, crop, idx)
+            cy, cx, score = cy[order], cx[order], score[order]
+            total = sum(pk.total for pk in nine)
+        x, y = frame_points(cy, cx, W, H, w)
+        P = _keep_count(len(score), count, keep)
+        out.append((np.stack([x, y], 1).astype(np.float32)[:P], np.asarray(score, np.float32)[:P], total))
+    return out
+
+
+@torch.no_grad()
+def _count_items_crops(model, items, normalization=True, max_s_cnt=1, max_batch=32):
+    """count_items, which also hands back the nine maps of a frame that took the 3 x 3 path: [(count, density map, crops or None), ...]."""
+    res = [None] * len(items)
+    rest = []
+    for idx, (im, ex, rects) in enumerate(items):
+        if rects is not None and inference._small_exemplars(rects) >= max_s_cnt:
+            dms = inference.density_maps(model, split_crops(im), [ex] * 9, ex.shape[1], max_batch)
+            pred = sum((d.sum() / 60).item() for d in dms)
+            res[idx] = (inference._normalise(pred, dms[-1], rects, normalization), dms[-1], dms)
+        else:
+            rest.append(idx)
+    if rest:
+        for idx, (c, dm) in zip(rest, inference.count_images(model, [items[i] for i in rest], normalization, max_s_cnt, max_batch)):
+            res[idx] = (c, dm, None)
+    return res
+
+
+@torch.no_grad()
+def locate_items(model, items, sizes, *, radius=4, threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all", normalization=True,
+                 max_s_cnt=1, max_batch=32):
+    """count_items + locate_maps over device-prepared items: [(count, density map, points, score, total peaks), ...]."""
+    res = _count_items_crops(model, items, normalization, max_s_cnt, max_batch)
+    pts = locate_maps([(c, dm) for c, dm, _cr in res], sizes, [cr for _c, _dm, cr in res], radius=radius, threshold=threshold,
+                      rel_threshold=rel_threshold, max_points=max_points, keep=keep)
+    return [(c, dm, p, s, t) for (c, dm, _cr), (p, s, t) in zip(res, pts)]
+
+
+@torch.no_grad()
+def locate_frames(model, frames, boxes=None, *, radius=4, threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all", normalization=True,
+                  max_s_cnt=1, max_batch=32):
+    """count_frames that also says WHERE: [(count, density map, points float32 [P, 2] as (x, y), score [P]), ...].  count and density map
+    are count_frames' bit for bit.  points are the sub-pixel centroids of the map's peaks (countr_amd/peaks.py states the rule) in
+    pixel-centre coordinates of the original frame (frame_points), ordered by score; keep="count" keeps the first
+    min(P, floor(count + 0.5)) of them.  A frame that takes the 3 x 3 split gets the peaks of its nine crop maps, mapped back through
+    crop_points and re-ordered by (score descending, crop, raster index); its returned map stays the last crop's.  The defaults
+    radius=4 and rel_threshold=0.1 are unmeasured: no localisation accuracy figure exists for them."""
+    device = next(model.parameters()).device
+    items = prepare_items(device, frames, boxes)
+    sizes = [(int(f.shape[1]), int(f.shape[0])) for f in frames]
+    return [r[:4] for r in locate_items(model, items, sizes, radius=radius, threshold=threshold, rel_threshold=rel_threshold,
+                                        max_points=max_points, keep=keep, normalization=normalization, max_s_cnt=max_s_cnt, max_batch=max_batch)]

@@ -9,7 +9,9 @@ applies to every input image; --boxes_json names a JSON file {image file name: [
 the images it lists.  An image without boxes is counted zero-shot.  The frame is handed to the device as decoded uint8 pixels:
 the resize to height 384, the 64 x 64 exemplar crops and, for exemplars under 10 pixels, the 3 x 3 crop-and-upscale all run there
 (countr_amd.frames).  The visualisation is image + exemplar outlines + density / 2, clamped to [0, 1], at the resized size.
-`--model_path ""` runs the randomly initialised model (dry runs / tests)."""
+`--model_path ""` runs the randomly initialised model (dry runs / tests).  `--points` also locates the objects (countr_amd.frames.locate_items):
+points_<stem>.json = {"count", "total_peaks", "points": [[x, y, score], ...]} in pixel-centre coordinates of the input image is written
+(with --no_viz too), and viz_<name>.jpg is resized back to the input size and gets a small dot per point."""
 import json
 import time
 from argparse import ArgumentParser
@@ -22,6 +24,7 @@ from PIL import Image
 
 import models_mae_cross
 from countr_amd import frames
+from demo_zero import add_points_args, draw_points, write_points
 
 
 def parse_boxes(text):
@@ -37,8 +40,9 @@ def parse_boxes(text):
     return boxes
 
 
-def save_visualisation(sample, density_map, rects, path):
-    """sample [3, h, w] in [0, 1], density_map [h, w]: outlines are drawn at 10 (white after the clamp), the density is halved."""
+def save_visualisation(sample, density_map, rects, path, points=None, size=None):
+    """sample [3, h, w] in [0, 1], density_map [h, w]: outlines are drawn at 10 (white after the clamp), the density is halved.
+    points: [(x, y), ...] of the input image of size (W, H): the picture is resized to that size and dotted."""
     _, h, w = sample.shape
     box_map = torch.zeros(h, w, device=sample.device)
     for y1, x1, y2, x2 in rects or []:
@@ -48,7 +52,10 @@ def save_visualisation(sample, density_map, rects, path):
         box_map[ya, xa:xb + 1] = 10
         box_map[yb, xa:xb + 1] = 10
     fig = torch.clamp(sample + box_map.unsqueeze(0) + density_map.unsqueeze(0) / 2, 0, 1)
-    Image.fromarray((fig.permute(1, 2, 0).cpu().numpy() * 255.0 + 0.5).astype(np.uint8)).save(path)
+    im = Image.fromarray((fig.permute(1, 2, 0).cpu().numpy() * 255.0 + 0.5).astype(np.uint8))
+    if points is not None:
+        im = draw_points(im.resize(size, Image.BILINEAR), points)
+    im.save(path)
 
 
 def main():
@@ -61,6 +68,7 @@ def main():
     p.add_argument("--group_images", type=int, default=8, help="images prepared and counted per call")
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     p.add_argument("--no_viz", action="store_true", help="counts only, no viz_*.jpg")
+    add_points_args(p)
     args = p.parse_args()
     args.output_path.mkdir(exist_ok=True, parents=True)
     device = torch.device("cuda")
@@ -88,13 +96,20 @@ def main():
         boxes = [[tuple(b) for b in named[pth.name]] if pth.name in named else common for pth in paths]
         t0 = time.perf_counter()
         items = frames.prepare_items(device, raw, boxes)
-        results = frames.count_items(model, items)
+        sizes = [(r.shape[1], r.shape[0]) for r in raw]
+        if args.points:
+            results = frames.locate_items(model, items, sizes, radius=args.points_radius, rel_threshold=args.points_rel_threshold,
+                                          keep=args.points_keep)
+        else:
+            results = [r + (None, None, None) for r in frames.count_items(model, items)]
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / len(paths)
-        for pth, (sample, _ex, rects), (pred_cnt, dm) in zip(paths, items, results):
+        for pth, (sample, _ex, rects), (pred_cnt, dm, pts, score, total), size in zip(paths, items, results, sizes):
             done += 1
+            if pts is not None:
+                write_points(args.output_path / ("points_%s.json" % pth.stem), pred_cnt, total, pts, score)
             if not args.no_viz:
-                save_visualisation(sample[0], dm.float(), rects, args.output_path / ("viz_%s.jpg" % pth.stem))
+                save_visualisation(sample[0], dm.float(), rects, args.output_path / ("viz_%s.jpg" % pth.stem), pts, size)
             if len(inputs) > 1:
                 print("[%3d/%d] %s:\tcount = %5.2f  -  time = %5.2f" % (done, len(inputs), pth.name, pred_cnt, dt))
             else:

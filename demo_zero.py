@@ -10,7 +10,11 @@ counted with shot_num = 0 and an empty exemplar tensor (:41-74).  The reference 
 resized back to the input size) is written with PIL, since torchvision is not part of this build.
 `--model_path ""` runs the randomly initialised model (dry runs / tests).  `--device_prep` moves the resize to the device: the frames
 are decoded by PIL, handed over as uint8 pixels and resized by countr_frame_resize_u8 (same bits as the host resize, so same counts);
-the printed time then includes the preparation.  demo.py is the few-shot counterpart (exemplar boxes)."""
+the printed time then includes the preparation.  `--points` also locates the objects (countr_amd.frames.locate_maps: the peaks of the
+density map, found on the device): viz_<name>.jpg gets a small dot per point and points_<stem>.json = {"count", "total_peaks", "points":
+[[x, y, score], ...]} (pixel-centre coordinates of the input image) is written, with --no_viz too.  demo.py is the few-shot counterpart
+(exemplar boxes)."""
+import json
 import time
 from argparse import ArgumentParser
 from itertools import chain
@@ -38,8 +42,29 @@ def load_image(img_path):
     return t, torch.Tensor([]), W, H
 
 
-def save_visualisation(sample, density_map, pred_cnt, path, old_w, old_h):
-    """demo_zero.py:77-90."""
+def draw_points(image, points, radius=2):
+    """A small dot per (x, y) point (pixel-centre coordinates of `image`)."""
+    draw = ImageDraw.Draw(image)
+    for x, y in points:
+        draw.ellipse((x + 0.5 - radius, y + 0.5 - radius, x + 0.5 + radius, y + 0.5 + radius), fill=(0, 255, 0))
+    return image
+
+
+def write_points(path, pred_cnt, total, points, score):
+    with open(path, "w") as f:
+        json.dump({"count": pred_cnt, "total_peaks": int(total),
+                   "points": [[float(x), float(y), float(s)] for (x, y), s in zip(points, score)]}, f)
+
+
+def add_points_args(p):
+    p.add_argument("--points", action="store_true", help="locate the objects: dots in viz_*.jpg and points_<stem>.json")
+    p.add_argument("--points_radius", type=int, default=4, help="half width of the peak window, 1..8 (the default is unmeasured)")
+    p.add_argument("--points_rel_threshold", type=float, default=0.1, help="a peak is at least this share of the map's maximum (the default is unmeasured)")
+    p.add_argument("--points_keep", default="all", choices=["all", "count"], help="count: keep the round(count) highest peaks")
+
+
+def save_visualisation(sample, density_map, pred_cnt, path, old_w, old_h, points=None):
+    """demo_zero.py:77-90; points: [(x, y), ...] of the input image, dotted after the resize back to its size."""
     _, h, w = sample.shape
     pred_fig = torch.stack((density_map, torch.zeros_like(density_map), torch.zeros_like(density_map)))
     count_im = Image.new(mode="RGB", size=(w, h), color=(0, 0, 0))
@@ -47,7 +72,10 @@ def save_visualisation(sample, density_map, pred_cnt, path, old_w, old_h):
     count_im = torch.from_numpy(np.array(count_im).transpose((2, 0, 1)).copy()).to(sample.device)   # 0 / 255, as in the reference
     fig = torch.clamp(sample / 2 + pred_fig / 2 + count_im, 0, 1)
     arr = (fig.permute(1, 2, 0).cpu().numpy() * 255.0 + 0.5).astype(np.uint8)
-    Image.fromarray(arr).resize((old_w, old_h), Image.BILINEAR).save(path)
+    im = Image.fromarray(arr).resize((old_w, old_h), Image.BILINEAR)
+    if points is not None:
+        draw_points(im, points)
+    im.save(path)
 
 
 def main():
@@ -60,6 +88,7 @@ def main():
     p.add_argument("--no_viz", action="store_true", help="counts only, no viz_*.jpg")
     p.add_argument("--device_prep", action="store_true",
                    help="hand the decoded uint8 frames to the device and resize them there (countr_amd.frames) instead of with PIL on the host")
+    add_points_args(p)
     args = p.parse_args()
     args.output_path.mkdir(exist_ok=True, parents=True)
     device = torch.device("cuda")
@@ -90,12 +119,19 @@ def main():
             t0 = time.perf_counter()
             items = [(s.unsqueeze(0).to(device, non_blocking=True), b.unsqueeze(0).to(device), None) for s, b, _w, _h in loaded]
         results = inference.count_images(model, items, normalization=False)
+        located = [None] * len(paths)
+        if args.points:
+            located = frames.locate_maps(results, [(w, h) for _s, _b, w, h in loaded], radius=args.points_radius,
+                                         rel_threshold=args.points_rel_threshold, keep=args.points_keep)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / len(paths)
-        for pth, (sample, _b, old_w, old_h), (pred_cnt, dm) in zip(paths, loaded, results):
+        for pth, (sample, _b, old_w, old_h), (pred_cnt, dm), loc in zip(paths, loaded, results, located):
             done += 1
+            if loc is not None:
+                write_points(args.output_path / ("points_%s.json" % pth.stem), pred_cnt, loc[2], loc[0], loc[1])
             if not args.no_viz:
-                save_visualisation(sample.to(device), dm.float(), pred_cnt, args.output_path / ("viz_%s.jpg" % pth.stem), old_w, old_h)
+                save_visualisation(sample.to(device), dm.float(), pred_cnt, args.output_path / ("viz_%s.jpg" % pth.stem), old_w, old_h,
+                                   points=loc[0] if loc is not None else None)
             if len(inputs) > 1:
                 print("[%3d/%d] %s:\tcount = %5.2f  -  time = %5.2f" % (done, len(inputs), pth.name, pred_cnt, dt))
             else:

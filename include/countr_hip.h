@@ -591,6 +591,38 @@ int countr_report_panels(const countr_report_image* imgs, int n, int h, const vo
 int countr_report_strip_shape(int S, int eh, int ew, int* shape);
 int countr_report_quantize(const countr_report_strip* strips, int n, int eh, int ew, void* out, int64_t out_bytes, void* stream);
 
+/* ---- object locations from density maps (csrc/peaks.hip; additive exports, the ABI version stays 9).
+ * countr_density_peaks: the peaks of n (1..16) maps, maps[i].map fp32 [h, w] on the device, contiguous, any h, w >= 1 with h w <= 2^28,
+ *   sizes free per map, no alignment requirement beyond the float's (16-byte loads in the maximum pass when a map's base is 16-byte
+ *   aligned, element loads otherwise).  maps is a HOST array read at call time.  radius is 1..8, cap 1..8192, threshold >= 0 and
+ *   0 <= rel_threshold <= 1; anything else is an error and nothing is launched.
+ *   The rule, which is the specification:
+ *     Let m be the maximum of the map.  A NaN never wins.
+ *     Let idx(p) = y*w + x.
+ *     Let win(p) be the (2r+1)^2 window around p, clipped to the map.
+ *     Pixel p with value v is a peak iff all three hold:
+ *       v > threshold
+ *       v >= rel_threshold * m, where the product is one fp32 multiply
+ *       for every q != p in win(p): v > d(q), or v == d(q) and idx(p) < idx(q)
+ *     Consequences: a plateau yields exactly one peak, its first pixel in raster order, unless something higher is in reach; an all-zero
+ *     map yields none; a NaN is never a peak (and neither is a pixel with a NaN inside its window).
+ *   Per peak, with w(q) = max(d(q), 0) over win(p), accumulated in fp32 (64 lanes, then a fixed butterfly):
+ *     score = v, mass = sum(w) / 60, cy = y + sum(w (qy - y)) / sum(w), cx likewise (offsets relative to the peak: magnitudes <= 8).
+ *   Output: totals[i] = the true number of peaks of map i, even beyond cap; recs[i][k][6] = {y, x, score, cy, cx, mass} (fp32) for
+ *   k < min(totals[i], cap): when totals[i] > cap the kept peaks are the first cap in raster order; the kept peaks are ordered by
+ *   (score descending, idx ascending).  Entries behind the kept ones are left untouched.
+ *   Four launches whatever n is (block maxima; tile detection with an r-wide halo in LDS, one 64-bit ballot mask per 64-pixel row segment;
+ *   popcount scan + raster-order records; rank by counting).  No atomic decides an order or a sum: two runs give the same bytes.
+ *   Nothing is allocated and the host never waits: all scratch lives in workspace (8-byte aligned, >= countr_peaks_workspace(n, max_h,
+ *   max_w, cap) bytes for maps no taller than max_h and no wider than max_w; HOST only, < 0 on bad arguments). */
+typedef struct countr_peak_map {
+  const float* map;      /* fp32 [h, w], contiguous */
+  int h, w;
+} countr_peak_map;
+int countr_peaks_workspace(int n, int max_h, int max_w, int cap);
+int countr_density_peaks(const countr_peak_map* maps, int n, int radius, float threshold, float rel_threshold, int cap, int* totals,
+                         float* recs, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
