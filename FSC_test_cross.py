@@ -6,6 +6,9 @@ loaded as TestData does (countr_amd/data/fsc147.py::test_item, pinned against th
 `--external`: the split's own exemplar crops, cut to --box_bound, serve every image -- :96-129).
 Without a dataset (none is available offline) `--synthetic N` evaluates N synthetic wide images through the same
 sliding-window / stitching / normalisation code (countr_amd/inference.py).
+`--localize` scores WHERE the objects are: the peaks of the density maps (frames.locate_maps) are matched one to one to the annotated dots
+(countr_amd/match.py states the rule; csrc/match.hip computes it) and precision / recall / F1 are printed per image and over the run, at
+the distances of --localize_dist in pixels of the 384-high evaluated image.  Off by default; without it the output is unchanged.
 `--report` writes the reference's evaluation report into --output_dir (:379-453: full_<stem>__<count>.png and boxes_<stem>.png per image,
 results.csv, log.txt, test_stat.png), composed on the device (countr_amd/report.py); without it nothing is written."""
 import argparse
@@ -53,7 +56,28 @@ def get_args_parser():
     p.add_argument("--group_images", default=8, type=int, help="images whose sliding windows share forward batches (up to 32 windows each)")
     p.add_argument("--report", action="store_true", help="write the reference's evaluation report (pictures, results.csv, log.txt, test_stat.png) into --output_dir")
     p.add_argument("--report_workers", default=4, type=int, help="threads that encode the report's PNGs (at most 8)")
+    p.add_argument("--localize", action="store_true", help="match the density maps' peaks to the annotated dots: precision / recall per image and over the run")
+    p.add_argument("--localize_dist", default="4,8,16", type=str, help="comma-separated matching distances, in pixels of the 384-high evaluated image")
+    p.add_argument("--localize_box_scale", default=0.0, type=float, help="> 0: a further per-image distance, this factor x the mean shorter side of the image's exemplar rectangles")
+    p.add_argument("--points_radius", default=4, type=int, help="peak window radius (locate_frames' radius)")
+    p.add_argument("--points_rel_threshold", default=0.1, type=float, help="peaks below this fraction of the map maximum are dropped")
+    p.add_argument("--points_keep", default="all", choices=["all", "count"], help='"count": keep the first floor(count + 0.5) peaks by score')
     return p
+
+
+def localize_distances(text):
+    """--localize_dist -> the distances, each finite and > 0."""
+    dists = [float(t) for t in str(text).split(",") if t.strip()]
+    if not dists or not all(np.isfinite(d) and d > 0 for d in dists):
+        raise ValueError("--localize_dist: comma-separated distances > 0")
+    return dists
+
+
+def box_distance(pos, scale):
+    """--localize_box_scale: scale x the mean shorter side of the exemplar rectangles (y1, x1, y2, x2), inclusive; None without any."""
+    if scale <= 0 or not pos:
+        return None
+    return scale * float(np.mean([min(y2 - y1, x2 - x1) + 1 for y1, x1, y2, x2 in pos]))
 
 
 def main(args):
@@ -74,14 +98,17 @@ def main(args):
             boxes = torch.from_numpy(rs.uniform(0, 1, size=(k, 3, 64, 64)).astype(np.float32)) if k else torch.zeros(0)
             pos = [(10 * j, 10 * j, 10 * j + 40, 10 * j + 40) for j in range(k)]
             gt_cnt = int(rs.randint(5, 200))
-            gt_map = None
-            if args.report:       # a generator of its own: the images and counts above are those of a run without --report
-                from scipy import ndimage
+            gt_map = pts = None
+            if args.report or args.localize:       # a generator of its own: the images and counts above are those of a run without the flags
                 ds = np.random.RandomState(args.seed + 1000003 * (i + 1))
+                rows, cols = ds.randint(0, 384, gt_cnt), ds.randint(0, w, gt_cnt)      # (rows first: the two flags describe the same objects)
+                pts = np.stack([cols, rows], 1).astype(np.float32)
+            if args.report:
+                from scipy import ndimage
                 dots = np.zeros((384, w), dtype=np.float32)
-                dots[ds.randint(0, 384, gt_cnt), ds.randint(0, w, gt_cnt)] = 1
+                dots[rows, cols] = 1
                 gt_map = torch.from_numpy(ndimage.gaussian_filter(dots, sigma=(1, 1), order=0)) * 60
-            items.append(("synthetic_%d" % i, img, boxes, pos, gt_cnt, gt_map))
+            items.append(("synthetic_%d" % i, img, boxes, pos, gt_cnt, gt_map, pts))
     else:
         from countr_amd.data import fsc147
         annotations = json.load(open(os.path.join(args.data_path, args.anno_file)))
@@ -92,7 +119,8 @@ def main(args):
             ext = fsc147.external_exemplars(annotations, split, im_dir, args.box_bound)
         for im_id in split:
             img, dots, boxes, pos, gt_map = fsc147.test_item(annotations, im_dir, im_id, args.box_bound, ext)
-            items.append((im_id, img, boxes, [tuple(r) for r in pos], dots.shape[0], gt_map if args.report else None))
+            items.append((im_id, img, boxes, [tuple(r) for r in pos], dots.shape[0], gt_map if args.report else None,
+                          fsc147.test_dots(annotations, im_dir, im_id) if args.localize else None))
     from countr_amd.parallel import shard_batch
     lo, hi = shard_batch(len(items), misc.get_rank(), misc.get_world_size())   # replicas only: images sharded, no collective
     mae = rmse = nae = 0.0
@@ -103,29 +131,74 @@ def main(args):
     if args.report:      # every rank writes the pictures of its own images; rank 0 writes the summary files (of its shard, as the reference's does)
         from countr_amd.report import ReportItem, ReportWriter
         writer = ReportWriter(args.output_dir, workers=args.report_workers, external=args.external, summary=misc.is_main_process())
+    dists, located = (localize_distances(args.localize_dist), []) if args.localize else (None, None)
     t0 = time.time()
     preds = []
     for g0 in range(0, len(mine), args.group_images):
         grp = mine[g0:g0 + args.group_images]
-        its = [(img.unsqueeze(0).to(device), boxes.unsqueeze(0).to(device), pos) for _name, img, boxes, pos, _gt, _map in grp]
-        if writer is None:
+        its = [(img.unsqueeze(0).to(device), boxes.unsqueeze(0).to(device), pos) for _name, img, boxes, pos, _gt, _map, _pts in grp]
+        if writer is None and not args.localize:
             preds += [p for p, _dm in inference.count_images(model, its, normalization=bool(args.normalization), max_s_cnt=args.max_s_cnt)]
             continue
         res = inference.count_images(model, its, normalization=bool(args.normalization), max_s_cnt=args.max_s_cnt, return_crops=True)
         preds += [r[0] for r in res]
-        for c0 in range(0, len(grp), 16):      # (a report launch takes 16 images); the encodes overlap the next group's forward
-            writer.add_group([ReportItem(name, s, b, pos, gt_cnt, gt_map) for (name, _i, _b, pos, gt_cnt, gt_map), (s, b, _p)
+        if args.localize:
+            located += localize_group(args, dists, grp, res)
+        for c0 in range(0, len(grp), 16) if writer is not None else ():      # (a report launch takes 16 images); the encodes overlap the next group's forward
+            writer.add_group([ReportItem(name, s, b, pos, gt_cnt, gt_map) for (name, _i, _b, pos, gt_cnt, gt_map, _pts), (s, b, _p)
                               in zip(grp[c0:c0 + 16], its[c0:c0 + 16])], res[c0:c0 + 16])
     torch.cuda.synchronize()
     t_inf = time.time() - t0
-    for (name, _img, _boxes, _pos, gt_cnt, _map), pred in zip(mine, preds):
+    for (name, _img, _boxes, _pos, gt_cnt, _map, _pts), pred in zip(mine, preds):
         err = abs(pred - gt_cnt)
         mae += err; rmse += err ** 2; nae += err / gt_cnt if gt_cnt > 0 else 0
         print("%s: pred_cnt: %5.3f, gt_cnt: %5.3f, error: %5.3f" % (name, pred, gt_cnt, err))
     n = max(hi - lo, 1)
     print(json.dumps({"MAE": mae / n, "RMSE": (rmse / n) ** 0.5, "NAE": nae / n, "images": hi - lo, "mean_infer_time_s": t_inf / n}))
+    columns = None
+    if args.localize:
+        columns = print_localization(args, dists, [it[0] for it in mine], located)
     if writer is not None:
-        writer.close(timing={"Mean infer time": t_inf / n, "Mean overall time": (time.time() - t0) / n})
+        writer.close(timing={"Mean infer time": t_inf / n, "Mean overall time": (time.time() - t0) / n}, columns=columns)
+
+
+def localize_group(args, dists, grp, res):
+    """The points of one group's maps (the nine crop maps of the 3 x 3 path included) against the group's dots: ONE matcher run per image
+    at its largest distance; the smaller distances are read off the same matching (the prefix property of the rule).
+    -> per image (P, G, rows of localization_metrics, labels)."""
+    from countr_amd import frames, match
+    # sizes = the evaluated image's own: frame_points is then the identity, and points and dots share one coordinate system
+    pts = frames.locate_maps([(r[0], r[1]) for r in res], [(int(r[1].shape[1]), frames.NEW_H) for r in res], [r[2] for r in res],
+                             radius=args.points_radius, rel_threshold=args.points_rel_threshold, keep=args.points_keep)
+    use, sets = [], []
+    for (_name, _img, _boxes, pos, _gt, _map, dots), (xy, _score, _total) in zip(grp, pts):
+        box = box_distance(pos, args.localize_box_scale)
+        use.append(dists + ([box] if box is not None else []))
+        sets.append((xy, dots, max(use[-1])))
+    out = []
+    for (xy, dots, _md), d, (_m, d2, _cnt) in zip(sets, use, match.point_matcher(res[0][1].device).match(sets)):
+        labels = ["%g" % v for v in dists] + (["box"] if len(d) > len(dists) else [])
+        out.append((len(xy), len(dots), match.localization_metrics(d2, len(xy), len(dots), d), labels))
+    return out
+
+
+def print_localization(args, dists, names, located):
+    """One line per image, then the run's (this rank's shard's) {"localization": ...} line -> the results.csv columns of --report."""
+    from countr_amd import match
+    totals = match.LocalizationTotals()
+    every = ["%g" % v for v in dists] + (["box"] if args.localize_box_scale > 0 else [])
+    header = ["points", "dots"] + ["%s_%s" % (k, lab) for lab in every for k in ("tp", "precision", "recall")]
+    cells = {}
+    for name, (P, G, rows, labels) in zip(names, located):
+        by = dict(zip(labels, rows))
+        for lab, row in by.items():
+            totals.add(lab, row, P, G)
+        print("%s: localization: %s" % (name, json.dumps({"points": P, "dots": G, "dist": by})))
+        cells[name] = [P, G] + [v for lab in every for v in (
+            (by[lab]["tp"], "%.4f" % by[lab]["precision"], "%.4f" % by[lab]["recall"]) if lab in by else ("", "", ""))]
+    print(json.dumps({"localization": {"images": len(located), "radius": args.points_radius, "rel_threshold": args.points_rel_threshold,
+                                       "keep": args.points_keep, "dist": totals.summary()}}))
+    return header, cells
 
 
 if __name__ == "__main__":

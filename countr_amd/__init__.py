@@ -9,6 +9,9 @@ def __getattr__(name):
     if name in ("PeakFinder", "peaks_host", "Peaks"):
         from . import peaks
         return getattr(peaks, name)
+    if name in ("match_host", "PointMatcher", "localization_metrics", "LocalizationTotals"):
+        from . import match
+        return getattr(match, name)
     if name in ("count_carpk", "CarpkPrep"):
         from . import carpk
         return getattr(carpk, name)

@@ -95,10 +95,16 @@ class PeakMap(C.Structure):
     _fields_ = [("map", C.c_void_p), ("h", C.c_int), ("w", C.c_int)]
 
 
+class MatchSet(C.Structure):
+    """countr_match_set: the points of one set of a countr_match_points call (csrc/match.hip)."""
+    _fields_ = [("pred", C.c_void_p), ("gt", C.c_void_p), ("P", C.c_int), ("G", C.c_int), ("max_dist", C.c_float), ("offset", C.c_int)]
+
+
 AUG_MAX_IMAGES = 32
 PRETRAIN_MAX_IMAGES = 16
 REPORT_MAX_IMAGES = 16
 PEAKS_MAX_MAPS = 16
+MATCH_MAX_SETS = 16
 _libs = {}
 
 
@@ -219,6 +225,8 @@ _SIGS = {
     "countr_report_quantize": [_vp, _i, _i, _i, _vp, _i64, _vp],
     "countr_peaks_workspace": [_i, _i, _i, _i],
     "countr_density_peaks": [_vp, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp],
+    "countr_match_workspace": [_i, _i, _i],
+    "countr_match_points": [_vp, _i, _vp, _vp, _vp, _vp, _vp],
     "countr_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp],
 }
 _RESTYPES = {"countr_xattn_bwd_workspace_floats": C.c_int64, "countr_groupnorm_bwd_image_sums_offset": C.c_int64}

@@ -605,6 +605,18 @@ def test_item(annotations, im_dir, im_id, box_bound=-1, external_boxes=None):
     return img_t, dots, boxes, pos, torch.from_numpy(gt) * 60
 
 
+def test_dots(annotations, im_dir, im_id):
+    """The image's annotated dots in pixel-centre coordinates of the evaluated [384, W'] image: float32 [n, 2] as (x * sw, y * sh),
+    unrounded, with _test_resize's scales (test_item's gt map truncates the same products to a pixel).  Reads the image's size only."""
+    from PIL import Image
+    with Image.open(os.path.join(im_dir, im_id)) as image:
+        W, H = image.size
+    new_h, new_w = 384, 16 * int((W / H * 384) / 16)
+    sw, sh = float(new_w) / W, float(new_h) / H
+    dots = np.asarray(annotations[im_id]["points"], dtype=np.float64).reshape(-1, 2)
+    return (dots * np.array([sw, sh])).astype(np.float32)
+
+
 def _paths(args):
     j = lambda p: p if os.path.isabs(p) else os.path.join(args.data_path, p)
     return j(args.anno_file), j(args.data_split_file), j(args.im_dir)

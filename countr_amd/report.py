@@ -388,10 +388,11 @@ class ReportWriter:
         return {"MAE": sum(errs) / n, "RMSE": (sum(e ** 2 for e in errs) / n) ** 0.5,
                 "NAE": sum(e / g if g > 0 else 0 for e, (_n, _p, g) in zip(errs, self.rows)) / n}
 
-    def close(self, timing=None):
+    def close(self, timing=None, columns=None):
         """Drains the pool; with summary=True writes results.csv (time, name, prediction = round(pred)), appends one JSON line of
         MAE / RMSE / NAE and the `timing` keys to log.txt (FSC_test_cross(few-shot).py:429-445) and draws test_stat.png (:447-450).
-        Returns the logged dictionary."""
+        columns = (header names, {image name: values}) appends further columns to results.csv (--localize; an image without values
+        gets empty cells); without it the file is the reference's.  Returns the logged dictionary."""
         if self.closed:
             return None
         self.closed = True
@@ -404,9 +405,10 @@ class ReportWriter:
             return log_stats
         with open(os.path.join(self.output_dir, "results.csv"), "w", newline="") as f:
             wr = csv.writer(f, lineterminator="\n")
-            wr.writerow(["time", "name", "prediction"])
+            more, cells = columns if columns is not None else ([], {})
+            wr.writerow(["time", "name", "prediction"] + list(more))
             for k, (name, pred, _gt) in enumerate(self.rows):
-                wr.writerow([k + 1, name, round(pred)])
+                wr.writerow([k + 1, name, round(pred)] + list(cells.get(name, [""] * len(more))))
         with open(os.path.join(self.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
             f.write(json.dumps(log_stats) + "\n")
         try:

@@ -623,6 +623,39 @@ int countr_peaks_workspace(int n, int max_h, int max_w, int cap);
 int countr_density_peaks(const countr_peak_map* maps, int n, int radius, float threshold, float rel_threshold, int cap, int* totals,
                          float* recs, void* workspace, void* stream);
 
+/* ---- predicted points against annotated dots (csrc/match.hip; additive exports, the ABI version stays 9).
+ * countr_match_points: the one-to-one matching of n (1..16) sets.  sets is a HOST array read at call time; set s holds pred fp32 [P, 2]
+ *   and gt fp32 [G, 2] on the device, both as (x, y) pairs, 8-byte aligned, P and G 0..8192 each (a pointer may be null when its count
+ *   is 0), max_dist finite and > 0, and offset >= 0, the first element of the set's slice in match / match_d2.  Anything else is an
+ *   error and nothing is launched.
+ *   The rule, which is the specification:
+ *     d2(i, j) = fl(fl(dx*dx) + fl(dy*dy)) with dx = fl(px_i - gx_j), dy = fl(py_i - gy_j): fp32, nothing contracted.
+ *     Pair (i, j) is eligible iff d2(i, j) <= fl(max_dist * max_dist) (one fp32 multiply).  A point with a non-finite coordinate
+ *     therefore has no eligible pair.
+ *     The eligible pairs are totally ordered by the key (d2, i, j).
+ *     The matching is the greedy one: go through the pairs in ascending key order and match (i, j) when both are still free.
+ *   Two properties follow.  (1) The matching is the fixed point of rounds in which every pair that is the smallest remaining key of both
+ *   its pred and its gt is matched -- this is how the kernel computes it, exactly.  (2) The matching under a smaller max_dist is the
+ *   subset of this one whose d2 is within the smaller bound, so one call at the largest distance gives the matches of every smaller one.
+ *   Letting each pred propose to its best gt and each gt take its best proposer is NOT this rule: a gt's best is taken over all its
+ *   remaining eligible pairs.
+ *   Output: match[offset + i] = the gt index of pred i or -1, match_d2[offset + i] = the pair's d2 or +inf, for i < P; counts[s] = the
+ *   number of matched pairs of set s.  Entries outside the slices are left untouched.
+ *   Two launches whatever the sets hold (every point's best partner over all CUs; then a block per set that runs the rounds until one
+ *   matches nothing -- no round count is assumed).  Minima, atomic AND on bit masks and one integer atomic add: nothing depends on an
+ *   order, two runs give the same bytes.  Nothing is allocated and the host never waits: all scratch lives in workspace (16-byte
+ *   aligned, >= countr_match_workspace(n, max_p, max_g) bytes for sets of at most max_p preds and max_g gts; HOST only, < 0 on bad
+ *   arguments). */
+typedef struct countr_match_set {
+  const float* pred;     /* fp32 [P, 2] as (x, y) */
+  const float* gt;       /* fp32 [G, 2] as (x, y) */
+  int P, G;
+  float max_dist;
+  int offset;            /* of the set's slice in match / match_d2, in elements */
+} countr_match_set;
+int countr_match_workspace(int n, int max_p, int max_g);
+int countr_match_points(const countr_match_set* sets, int n, int* match, float* match_d2, int* counts, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
