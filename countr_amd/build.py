@@ -55,7 +55,7 @@ def build(force=False, verbose=True):
             obj = os.path.join(bdir, os.path.basename(src) + ".o")
             objs.append(obj)
             total += 1
-            cmd = ([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-amdgpu-mfma-vgpr-form=1"] + extra
+            cmd = ([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-mllvm", "-amdgpu-mfma-vgpr-form=1"] + extra
                    + EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj])
             want = _digest([src] + hdrs, " ".join(cmd[1:-3]))
             rec = obj + ".sha256"

@@ -15,7 +15,7 @@ from . import _lib, inference
 from .data import carpk as D
 from .frames import FramePrep, _Slot, _is_u8, _stream
 
-MAX_FRAMES = 16             # csrc/carpk.hip: MAX_FRAMES (and MAX_RECTS = 2 per frame)
+MAX_FRAMES = _lib.CARPK_MAX_FRAMES         # (and two rectangles per frame)
 GROUP = 8                   # frames per forward: 8 x 4 windows = one batch of 32
 
 

@@ -12,7 +12,7 @@
 
 namespace {
 
-constexpr int MAX_FRAMES = 16, MAX_RECTS = 32;
+constexpr int MAX_FRAMES = COUNTR_CARPK_MAX_FRAMES, MAX_RECTS = 2 * MAX_FRAMES;
 constexpr int BOX = 64;                          // exemplar crops are 64 x 64 (FSC_test_CARPK.py:171)
 constexpr int MAX_BLOCKS = 4096;
 constexpr int CELL = 16;                         // the count rule's Conv2d(1, 1, 16, stride 16)

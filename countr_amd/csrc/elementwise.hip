@@ -827,6 +827,7 @@ extern "C" int countr_upsample2x_bwd(const void* dout, void* din, int B, int H, 
 // Several device-to-device copies in ONE launch (the per-step staging of a batch: images, exemplar crops, ground-truth map, loss mask --
 // four ~5-us copy launches in front of every step otherwise).  16-byte aligned pointers and sizes.  A NULL source zero-fills its
 // destination (a gradient bucket this rank has no gradient for while another rank has: per-rank shot_num, trainer.py).
+namespace {
 struct CopyTable { int n; const uint4* src[8]; uint4* dst[8]; long long n16[8]; int first[8]; };
 __global__ __launch_bounds__(256) void copy_multi_kernel(const CopyTable t) {
   int e = 0;
@@ -844,6 +845,8 @@ __global__ __launch_bounds__(256) void copy_multi_kernel(const CopyTable t) {
     for (int u = 0; u < 4; ++u) if (i + (long long)u * nb * 256 < n) d[i + (long long)u * nb * 256] = v[u];
   }
 }
+
+}  // namespace
 
 extern "C" int countr_copy_multi(int n, const void* const* src, void* const* dst, const int64_t* bytes, void* stream) {
   if (n < 1 || n > 8 || !src || !dst || !bytes) { countr_set_error("countr_copy_multi: 1..8 copies"); return -1; }
@@ -870,6 +873,7 @@ extern "C" int countr_copy_multi(int n, const void* const* src, void* const* dst
 // of 256-byte records in pinned host memory that the device reads directly: record index = *counter % slots, where counter is a
 // device int64 every execution increments -- eager launches and replays alike, so the host mirrors it by counting executions and
 // fills record (executions % slots) before each one.
+namespace {
 struct PrologueRec {               // 256 bytes, host-written (countr_amd/trainer.py::_Prologue)
   unsigned long long src[6], dst[6];
   long long n16[6];
@@ -942,6 +946,8 @@ __global__ __launch_bounds__(256) void step_prologue_kernel(const PrologueRec* _
   }
 }
 
+}  // namespace
+
 extern "C" int countr_step_prologue_record_bytes(void) { return (int)sizeof(PrologueRec); }
 extern "C" int countr_step_prologue_copy_blocks(void) { return PRO_COPY_BLOCKS; }
 extern "C" int countr_step_prologue(const void* ring, int slots, int64_t* counter, float* hyper_dev, float* mask, int mask_n, void* stream) {
@@ -1002,6 +1008,7 @@ extern "C" int countr_conv_shadows(int n, const float* const* src, void* const* 
 // behind AdamW, which has just written the 16-bit shadow W itself: reading THAT instead of the fp32 master halves the bytes read, and the
 // tiles move as 16-byte chunks both ways (64 x 64 elements through LDS: 128-byte runs in, 128-byte runs out).  The bits are those of
 // countr_conv_shadows' taps = 1 form (a cast of the same fp32 value, transposed).
+namespace {
 constexpr int TR_MAX = 96, TR_PITCH = 72;      // LDS row pitch in elements: 144 bytes, 16-byte aligned rows, odd multiple of 16 bytes
 struct TransposeTable {
   const uint16_t* src[TR_MAX];
@@ -1038,6 +1045,8 @@ __global__ __launch_bounds__(256) void transpose16_kernel(const TransposeTable t
     }
   }
 }
+
+}  // namespace
 
 extern "C" int countr_transpose16(int n, const void* const* src, void* const* dst, const int* rows, const int* cols, void* stream) {
   if (n < 1 || n > TR_MAX || !src || !dst || !rows || !cols) { countr_set_error("countr_transpose16: 1..96 matrices"); return -1; }

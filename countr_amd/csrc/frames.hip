@@ -16,7 +16,7 @@
 
 namespace {
 
-constexpr int MAX_FRAMES = 16, MAX_RECTS = 16;
+constexpr int MAX_FRAMES = COUNTR_FRAMES_MAX, MAX_RECTS = COUNTR_FRAMES_MAX;
 constexpr int MAX_BLOCKS = 2048;
 
 struct FrameArgs {

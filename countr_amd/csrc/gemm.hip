@@ -275,6 +275,7 @@ extern "C" int countr_gemm(const countr_gemm_args* a, int dtype, int modeA, int 
 // Finisher of a split-K FORWARD-type GEMM: out[m][n] = sum_z partial[z][m][n] (+ bias[n]) in the output dtype.  For launches with few
 // tiles and a long K (decode_head0 forward: 72 tiles x 72 k-tiles, exemplar conv4 dgrad: 24 x 72) the k loop is cut over the idle CUs
 // and this pass costs less than the serial loop it replaces.
+namespace {
 template <typename TO>
 __global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restrict__ partial, TO* __restrict__ out,
                                                             const float* __restrict__ bias, int splitk, int64_t MN4, int N4) {
@@ -289,6 +290,8 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restr
   }
   st4<TO>(out + i * 4, s);
 }
+
+}  // namespace
 
 extern "C" int countr_splitk_finish(const float* partial, void* out, const float* bias, int splitk, int M, int N, int out_bf16,
                                     void* stream) {

@@ -3,6 +3,8 @@
 #include "common.hpp"
 #include "../../include/countr_hip.h"
 
+namespace {
+
 // dst[r,:] = (idx[r] >= 0 ? src[idx[r],:] : default_row[:]) + add[r % add_mod,:]     (4 columns per thread)
 template <typename TS, typename TD>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const TS* __restrict__ src, const int* __restrict__ idx, TD* __restrict__ dst,
@@ -106,6 +108,8 @@ __global__ __launch_bounds__(256) void mae_indices_kernel(const long long* __res
     mask[b * N + s] = 1.f;
   }
 }
+
+}  // namespace
 
 extern "C" int countr_mae_indices(const long long* ids_shuffle, long long* ids_restore, int* keep_pos, int* keep_src, int* restore_src,
                                   int* mask_src, float* mask, int B, int N, int K, void* stream) {

@@ -22,7 +22,7 @@
 
 namespace {
 
-constexpr int MAX_SETS = 16, MAX_PTS = 8192;
+constexpr int MAX_SETS = COUNTR_MATCH_MAX_SETS, MAX_PTS = COUNTR_MATCH_MAX_POINTS;
 constexpr int NONE = 0xFFFF;                     // "no eligible free partner" (an index is < 8192)
 constexpr int INIT_BLOCKS = 128;                 // blocks per set of the first launch (4 waves each)
 constexpr int ROUND_THREADS = 1024, ROUND_WAVES = ROUND_THREADS / 64;

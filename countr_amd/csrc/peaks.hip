@@ -18,8 +18,8 @@
 
 namespace {
 
-constexpr int MAX_MAPS = 16;
-constexpr int MAX_R = 8, MAX_CAP = 8192;
+constexpr int MAX_MAPS = COUNTR_PEAKS_MAX_MAPS;
+constexpr int MAX_R = COUNTR_PEAKS_MAX_RADIUS, MAX_CAP = COUNTR_PEAKS_MAX_POINTS;
 constexpr int TILE_H = 32, TILE_W = 64;          // TILE_W = the wave: a tile row's ballot is its mask
 constexpr int PARTS = 32;                        // block maxima per map (one half-wave folds them)
 constexpr int WRITE_BLOCKS = 32;                 // blocks per map of the scan + write launch

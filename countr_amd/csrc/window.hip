@@ -11,7 +11,7 @@
 namespace {
 
 constexpr int WIN = 384;
-constexpr int MAX_WINDOWS = 64, MAX_STARTS = 16;
+constexpr int MAX_WINDOWS = 64, MAX_STARTS = COUNTR_WINDOW_MAX_STARTS;
 
 struct GatherArgs {
   const float* frame[MAX_WINDOWS];   // image of window j: fp32 [3, H, W_j]

@@ -273,13 +273,13 @@ class DeviceAug:
                 sub = (_lib.AugImage * len(chain))(*[table[i] for i in chain])
                 for g0 in range(0, len(chain), G):
                     n = min(G, len(chain) - g0)
-                    part = C.byref(sub, g0 * C.sizeof(_lib.AugImage))
+                    part = C.byref(sub[g0])
                     _lib.check(self.L.countr_aug_jitter(part, n, self.noise_seed, self._partials.data_ptr(), st), "countr_aug_jitter")
                     _lib.check(self.L.countr_aug_blur(part, n, st), "countr_aug_blur")
                     self.launches += 3
             for g0 in range(0, B, G):
                 n = min(G, B - g0)
-                part = C.byref(table, g0 * C.sizeof(_lib.AugImage))
+                part = C.byref(table[g0])
                 _lib.check(self.L.countr_aug_window(part, n, imgs[g0:].data_ptr(), st), "countr_aug_window")
                 _lib.check(self.L.countr_aug_exemplars(part, n, boxes[g0:].data_ptr(), st), "countr_aug_exemplars")
                 _lib.check(self.L.countr_aug_density(part, n, base + c_off, max(ncells, 1), gt[g0:].data_ptr(), st), "countr_aug_density")

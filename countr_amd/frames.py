@@ -14,7 +14,7 @@ from . import _lib, inference, peaks
 
 NEW_H = 384
 BOX = 64                    # exemplar crops are 64 x 64 (demo.py:67)
-MAX_BATCHED = 16            # csrc/frames.hip: MAX_FRAMES / MAX_RECTS
+MAX_BATCHED = _lib.FRAMES_MAX              # frames / rectangles of one call
 
 
 def new_width(W, H):

@@ -10,6 +10,8 @@ the engine as ONE batch -- the stitching itself is a few elementwise ops on [384
 import torch
 import torch.nn.functional as F
 
+from . import _lib
+
 
 def window_starts(width):
     """Start columns produced by the reference loop (FSC_test_cross(few-shot).py:326-349)."""
@@ -62,7 +64,7 @@ def blend_windows_batched(outputs, starts, width, height=384):
     return dm
 
 
-MAX_BLEND_WINDOWS = 16     # csrc/window.hip: MAX_STARTS
+MAX_BLEND_WINDOWS = _lib.WINDOW_MAX_STARTS
 
 
 def _native_plan(model, images, max_batch):
@@ -84,7 +86,6 @@ def _native_plan(model, images, max_batch):
 def _gather_windows(L, images, plan, h, dst, nb, st):
     """The windows of `plan` cut straight into the batch buffer dst [nb, 3, h, 384] (countr_window_gather); padding rows zeroed."""
     import ctypes as C
-    from . import _lib
     nw = len(plan)
     frames = (C.c_void_p * nw)(*[images[i].data_ptr() for i, _s in plan])
     widths = (C.c_int * nw)(*[images[i].shape[-1] for i, _s in plan])
@@ -103,7 +104,6 @@ def _native_maps(model, images, boxes, shot_num, max_batch, want_sums, have=None
     batch size, their windows are gathered now and their frozen-encoder forward runs beside this call's decoder / density head
     (flags["ahead"] = the engine's ownership token if it did); `have` = the token of the call that ran THIS call's encoder forward."""
     import ctypes as C
-    from . import _lib
     plan = _native_plan(model, images, max_batch)
     if plan is None:
         return None

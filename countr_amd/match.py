@@ -16,8 +16,9 @@ import ctypes as C
 
 import numpy as np
 
-MAX_SETS = 16               # csrc/match.hip: MAX_SETS
-MAX_POINTS = 8192
+from . import _lib
+
+MAX_SETS, MAX_POINTS = _lib.MATCH_MAX_SETS, _lib.MATCH_MAX_POINTS
 
 
 def _points(a, what):
@@ -137,7 +138,6 @@ class PointMatcher:
 
     def __init__(self, device="cuda"):
         import torch
-        from . import _lib
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.CountrError("PointMatcher needs a GPU device: the HIP path has no CPU fallback")
@@ -168,7 +168,6 @@ class PointMatcher:
         """sets: [(pred [P, 2], gt [G, 2], max_dist), ...] on the host -> [(match int32 [P], d2 float32 [P], matched), ...] as numpy
         arrays, on the current stream."""
         import torch
-        from . import _lib
         n = len(sets)
         if n == 0:
             return []

@@ -14,8 +14,9 @@ from collections import namedtuple
 
 import numpy as np
 
-MAX_MAPS = 16               # csrc/peaks.hip: MAX_MAPS
-MAX_RADIUS, MAX_CAP = 8, 8192
+from . import _lib
+
+MAX_MAPS, MAX_RADIUS, MAX_CAP = _lib.PEAKS_MAX_MAPS, _lib.PEAKS_MAX_RADIUS, _lib.PEAKS_MAX_POINTS
 REC = 6                     # {y, x, score, cy, cx, mass}
 
 # total: the true number of peaks (beyond max_points too); the arrays hold the P = min(total, max_points) kept ones in score order
@@ -79,7 +80,6 @@ class PeakFinder:
 
     def __init__(self, device="cuda"):
         import torch
-        from . import _lib
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.CountrError("PeakFinder needs a GPU device: the HIP path has no CPU fallback")
@@ -109,7 +109,6 @@ class PeakFinder:
         """maps: fp32 [h, w] device tensors (contiguous; sizes free per map) -> [Peaks(total, yx int32 [P, 2], score [P], centroid
         float32 [P, 2] as (cy, cx), mass [P]), ...] as numpy arrays, on the current stream."""
         import torch
-        from . import _lib
         _check(radius, threshold, rel_threshold, max_points)
         cap, n = int(max_points), len(maps)
         if n == 0:

@@ -24,7 +24,9 @@ import torch
 import torch.nn.functional as F
 from PIL import Image, ImageDraw
 
-MAX_GROUP = 16              # csrc/report.hip: COUNTR_REPORT_MAX_IMAGES
+from . import _lib
+
+MAX_GROUP = _lib.REPORT_MAX_IMAGES
 MAX_WORKERS = 8
 GRID_ROW, GRID_PAD = 8, 2   # torchvision.utils.make_grid's defaults, which save_image passes on
 
@@ -260,7 +262,6 @@ class ReportWriter:
                 self._host_pending.append(self.pool.submit(_encode, self.boxes_path(it.name), exemplar_strip_host(it.boxes)))
 
     def _device_group(self, items, cnts, preds):
-        from . import _lib
         device = items[0].sample.device
         L = _lib.lib()
         if self._descs is None:

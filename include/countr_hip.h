@@ -25,6 +25,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+#pragma GCC visibility push(default) /* the library is built with -fvisibility=hidden: what this header declares is what it exports */
 
 #define COUNTR_F32 0
 #define COUNTR_BF16 1
@@ -48,7 +49,8 @@ int countr_init(int device);            /* selects device, checks it is gfx950-c
                                            thread-safe.  A bias-less countr_gemm / countr_conv launch on a device without it fails
                                            with a negative code and a message naming countr_init (it does not allocate lazily:
                                            no allocation inside a launch) */
-int countr_version(void);               /* ABI version, currently 9 (9: countr_gemm_args grew at its end (gn_rows) + countr_groupnorm_relu_fwd_rows -- rebuild callers; 8: countr_transpose16 added, no layout change; 7: countr_masked_mse_amp / countr_patch_mse_amp / countr_adamw_step_amp added, no layout change; 6: countr_softmax_fwd_ld added, no layout change; 5: countr_step_prologue added, no layout change; countr_gemm_args grew at its end -- round 3: ln_* fields, rowsum_slabs; round 4: prefetch hint (3) -- so a caller built against an older version must be rebuilt; 4: countr_gemm_group / countr_gemm_group_tiles added, no layout change) */
+#define COUNTR_ABI_VERSION 9
+int countr_version(void);               /* COUNTR_ABI_VERSION (9: countr_gemm_args grew at its end (gn_rows) + countr_groupnorm_relu_fwd_rows -- rebuild callers; 8: countr_transpose16 added, no layout change; 7: countr_masked_mse_amp / countr_patch_mse_amp / countr_adamw_step_amp added, no layout change; 6: countr_softmax_fwd_ld added, no layout change; 5: countr_step_prologue added, no layout change; countr_gemm_args grew at its end -- round 3: ln_* fields, rowsum_slabs; round 4: prefetch hint (3) -- so a caller built against an older version must be rebuilt; 4: countr_gemm_group / countr_gemm_group_tiles added, no layout change) */
 const char* countr_last_error(void);    /* thread-local message of the last failing call        */
 
 /*
@@ -373,6 +375,7 @@ int countr_patch_mse(const float* pred, const float* imgs, void* dpred, float* l
  *   width W with the window starts starts[nwin] (HOST array, increasing, <= 16) -> dm fp32 [n, H, W]; sums (optional) fp32 [n] = sum
  *   of each stitched map (the predicted count x 60), deterministic two-pass sum through workspace fp32 [n * countr_window_blend_blocks(H, W)].
  * Both equal the reference's tensor slicing / blending bit for bit (x / 2 is exact in fp32). */
+#define COUNTR_WINDOW_MAX_STARTS 16 /* window starts of a countr_window_blend call */
 int countr_window_gather(const void* const* frames, const int* widths, const int* starts, int nw, int H, float* wins, void* stream);
 int countr_window_blend(const float* outs, int n, int nwin, const int* starts, int H, int W, float* dm, float* sums, float* workspace, void* stream);
 int countr_window_blend_blocks(int H, int W);
@@ -396,6 +399,7 @@ int countr_window_blend_blocks(int H, int W);
  *   align_corners=False, no antialias -- F.interpolate(crop, size=(oh, ow), mode="bilinear") with torch's fp32 source coordinates:
  *   the 64 x 64 exemplar crops (demo.py:60-68) and the 3x3 crop-and-upscale for tiny exemplars (:84-99).  A rectangle that is empty
  *   after clipping is an error, not a launch. */
+#define COUNTR_FRAMES_MAX 16 /* frames of a countr_frame_resize_u8 call, rectangles of a countr_crop_resize_f32 call */
 int countr_pil_bilinear_tables(int in_size, int out_size, int* bounds, int* weights);
 int countr_frame_resize_u8(const void* const* frames, void* const* outs, int n, int H, int W, int out_h, int out_w,
                            const int* hbounds, const int* hweights, const int* vbounds, const int* vweights, void* tmp, void* stream);
@@ -537,6 +541,7 @@ int countr_pretrain_aug(const countr_pretrain_image* imgs, int n, const int* tab
  *     rectangles the script's line :238 really cuts is the caller's business: countr_amd/data/carpk.py::script_rects); pred = total - n_over + (e_cnt <= 0.5 ? 2 : 0).
  *   Two launches (partials, fold) through workspace fp32 [n * countr_carpk_count_blocks(H, W) * 4]; every sum has a fixed order, no
  *   atomics: two runs give the same bits. */
+#define COUNTR_CARPK_MAX_FRAMES 16 /* frames / maps of a call; countr_carpk_prep_u8 takes two rectangles per frame */
 int countr_carpk_prep_u8(const void* const* frames, const int* shapes, int n, const int* rects, int nrects, int out_h, int out_w,
                          int out_cols, float* img, float* ex, void* stream);
 int countr_carpk_count_blocks(int H, int W);
@@ -615,6 +620,9 @@ int countr_report_quantize(const countr_report_strip* strips, int n, int eh, int
  *   popcount scan + raster-order records; rank by counting).  No atomic decides an order or a sum: two runs give the same bytes.
  *   Nothing is allocated and the host never waits: all scratch lives in workspace (8-byte aligned, >= countr_peaks_workspace(n, max_h,
  *   max_w, cap) bytes for maps no taller than max_h and no wider than max_w; HOST only, < 0 on bad arguments). */
+#define COUNTR_PEAKS_MAX_MAPS 16
+#define COUNTR_PEAKS_MAX_RADIUS 8
+#define COUNTR_PEAKS_MAX_POINTS 8192 /* the largest cap */
 typedef struct countr_peak_map {
   const float* map;      /* fp32 [h, w], contiguous */
   int h, w;
@@ -646,6 +654,8 @@ int countr_density_peaks(const countr_peak_map* maps, int n, int radius, float t
  *   order, two runs give the same bytes.  Nothing is allocated and the host never waits: all scratch lives in workspace (16-byte
  *   aligned, >= countr_match_workspace(n, max_p, max_g) bytes for sets of at most max_p preds and max_g gts; HOST only, < 0 on bad
  *   arguments). */
+#define COUNTR_MATCH_MAX_SETS 16
+#define COUNTR_MATCH_MAX_POINTS 8192 /* of P and of G */
 typedef struct countr_match_set {
   const float* pred;     /* fp32 [P, 2] as (x, y) */
   const float* gt;       /* fp32 [G, 2] as (x, y) */
@@ -656,6 +666,7 @@ typedef struct countr_match_set {
 int countr_match_workspace(int n, int max_p, int max_g);
 int countr_match_points(const countr_match_set* sets, int n, int* match, float* match_d2, int* counts, void* workspace, void* stream);
 
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

@@ -1,15 +1,12 @@
 """CPU: the matching rule's host statement (countr_amd/match.py: match_host), its two properties (locally dominant rounds, prefix),
 the metrics and their totals, the ABI listing and argument checks of the two new exports, and the evaluation CLI's new flags."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
 from countr_amd import _lib, match
 from countr_amd.match import LocalizationTotals, localization_metrics, match_host, match_rounds_host
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF = np.float32(np.inf)
 
 
@@ -141,29 +138,11 @@ def test_totals_micro_and_macro():
     assert z.summary()["4"] == {"images": 1, "tp": 0, "pred": 0, "gt": 0, "precision": 0.0, "recall": 0.0, "f1": 0.0, "macro_f1": 0.0}
 
 
-def test_header_prototypes_equal_the_binding_table():
-    hdr = open(os.path.join(ROOT, "include", "countr_hip.h")).read()
-    names = ("countr_match_workspace", "countr_match_points")
-    for name in names:
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m, name
-        want = []
-        for arg in m.group(1).split(","):
-            arg = " ".join(arg.split())
-            want.append(C.c_void_p if "*" in arg else {"int": C.c_int, "float": C.c_float}[arg.rsplit(" ", 1)[0]])
-        assert _lib._SIGS[name] == want, name
-        assert name in _lib.exported_symbols()
-    src = open(os.path.join(ROOT, "countr_amd", "csrc", "match.hip")).read()
-    for name in names:
-        assert re.search(r'extern "C" int %s\(' % name, src)
-    # the struct: two pointers, P, G, max_dist, offset -- as the header lays it out
-    body = re.search(r"typedef struct countr_match_set \{(.*?)\} countr_match_set;", hdr, re.S).group(1)
-    fields = re.findall(r"(\w+)\s*(?:,\s*(\w+)\s*)?;", re.sub(r"/\*.*?\*/", "", body))
-    assert [n for pair in fields for n in pair if n] == [f[0] for f in _lib.MatchSet._fields_]
+def test_match_set_layout_version_and_limits():
     assert C.sizeof(_lib.MatchSet) == 32
     for variant in ("", "f16"):
         L = _lib.lib(variant)
-        assert L.countr_version() == 9 == _lib.ABI_VERSION and all(hasattr(L, n) for n in names)
+        assert L.countr_version() == 9 == _lib.ABI_VERSION and all(hasattr(L, n) for n in ("countr_match_workspace", "countr_match_points"))
     assert match.MAX_SETS == _lib.MATCH_MAX_SETS == 16
 
 
