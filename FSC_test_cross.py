@@ -9,6 +9,11 @@ sliding-window / stitching / normalisation code (countr_amd/inference.py).
 `--localize` scores WHERE the objects are: the peaks of the density maps (frames.locate_maps) are matched one to one to the annotated dots
 (countr_amd/match.py states the rule; csrc/match.hip computes it) and precision / recall / F1 are printed per image and over the run, at
 the distances of --localize_dist in pixels of the 384-high evaluated image.  Off by default; without it the output is unchanged.
+`--game L` (0..3) adds the grid average mean absolute error, a localisation-aware figure that needs no peak finder and so none of its
+settings: GAME(l) = the mean over images of the sum over the 2^l x 2^l cells of |predicted count in the cell - dots in the cell|; GAME(0)
+is the MAE.  The per-cell predictions are sums of the density maps the run already has (the nine crop maps of the 3 x 3 path included) over
+the level-L grid, on the device (countr_amd.frames.region_maps, one RegionSummer.sum per group of images), scaled so that they add up to
+the printed count; the levels below L are sums of those level-L cell values computed in fp64 on the host.
 `--report` writes the reference's evaluation report into --output_dir (:379-453: full_<stem>__<count>.png and boxes_<stem>.png per image,
 results.csv, log.txt, test_stat.png), composed on the device (countr_amd/report.py); without it nothing is written."""
 import argparse
@@ -59,6 +64,9 @@ def get_args_parser():
     p.add_argument("--localize", action="store_true", help="match the density maps' peaks to the annotated dots: precision / recall per image and over the run")
     p.add_argument("--localize_dist", default="4,8,16", type=str, help="comma-separated matching distances, in pixels of the 384-high evaluated image")
     p.add_argument("--localize_box_scale", default=0.0, type=float, help="> 0: a further per-image distance, this factor x the mean shorter side of the image's exemplar rectangles")
+    p.add_argument("--game", default=-1, type=int, choices=[-1, 0, 1, 2, 3],
+                   help="L: print GAME(0..L) per image and over the run; the density maps are summed over the 2^L x 2^L grid on the device, and "
+                        "the levels below L are sums of level-L cell values computed in fp64 on the host (-1: off)")
     p.add_argument("--points_radius", default=4, type=int, help="peak window radius (locate_frames' radius)")
     p.add_argument("--points_rel_threshold", default=0.1, type=float, help="peaks below this fraction of the map maximum are dropped")
     p.add_argument("--points_keep", default="all", choices=["all", "count"], help='"count": keep the first floor(count + 0.5) peaks by score')
@@ -99,7 +107,7 @@ def main(args):
             pos = [(10 * j, 10 * j, 10 * j + 40, 10 * j + 40) for j in range(k)]
             gt_cnt = int(rs.randint(5, 200))
             gt_map = pts = None
-            if args.report or args.localize:       # a generator of its own: the images and counts above are those of a run without the flags
+            if args.report or args.localize or args.game >= 0:       # a generator of its own: the images and counts above are those of a run without the flags
                 ds = np.random.RandomState(args.seed + 1000003 * (i + 1))
                 rows, cols = ds.randint(0, 384, gt_cnt), ds.randint(0, w, gt_cnt)      # (rows first: the two flags describe the same objects)
                 pts = np.stack([cols, rows], 1).astype(np.float32)
@@ -120,7 +128,7 @@ def main(args):
         for im_id in split:
             img, dots, boxes, pos, gt_map = fsc147.test_item(annotations, im_dir, im_id, args.box_bound, ext)
             items.append((im_id, img, boxes, [tuple(r) for r in pos], dots.shape[0], gt_map if args.report else None,
-                          fsc147.test_dots(annotations, im_dir, im_id) if args.localize else None))
+                          fsc147.test_dots(annotations, im_dir, im_id) if args.localize or args.game >= 0 else None))
     from countr_amd.parallel import shard_batch
     lo, hi = shard_batch(len(items), misc.get_rank(), misc.get_world_size())   # replicas only: images sharded, no collective
     mae = rmse = nae = 0.0
@@ -132,18 +140,21 @@ def main(args):
         from countr_amd.report import ReportItem, ReportWriter
         writer = ReportWriter(args.output_dir, workers=args.report_workers, external=args.external, summary=misc.is_main_process())
     dists, located = (localize_distances(args.localize_dist), []) if args.localize else (None, None)
+    games = []
     t0 = time.time()
     preds = []
     for g0 in range(0, len(mine), args.group_images):
         grp = mine[g0:g0 + args.group_images]
         its = [(img.unsqueeze(0).to(device), boxes.unsqueeze(0).to(device), pos) for _name, img, boxes, pos, _gt, _map, _pts in grp]
-        if writer is None and not args.localize:
+        if writer is None and not args.localize and args.game < 0:
             preds += [p for p, _dm in inference.count_images(model, its, normalization=bool(args.normalization), max_s_cnt=args.max_s_cnt)]
             continue
         res = inference.count_images(model, its, normalization=bool(args.normalization), max_s_cnt=args.max_s_cnt, return_crops=True)
         preds += [r[0] for r in res]
         if args.localize:
             located += localize_group(args, dists, grp, res)
+        if args.game >= 0:
+            games += game_group(args.game, grp, res)
         for c0 in range(0, len(grp), 16) if writer is not None else ():      # (a report launch takes 16 images); the encodes overlap the next group's forward
             writer.add_group([ReportItem(name, s, b, pos, gt_cnt, gt_map) for (name, _i, _b, pos, gt_cnt, gt_map, _pts), (s, b, _p)
                               in zip(grp[c0:c0 + 16], its[c0:c0 + 16])], res[c0:c0 + 16])
@@ -158,6 +169,9 @@ def main(args):
     columns = None
     if args.localize:
         columns = print_localization(args, dists, [it[0] for it in mine], located)
+    if args.game >= 0:
+        header, cells = print_game(args.game, [it[0] for it in mine], games)
+        columns = (header, cells) if columns is None else (columns[0] + header, {k: v + cells[k] for k, v in columns[1].items()})
     if writer is not None:
         writer.close(timing={"Mean infer time": t_inf / n, "Mean overall time": (time.time() - t0) / n}, columns=columns)
 
@@ -180,6 +194,30 @@ def localize_group(args, dists, grp, res):
         labels = ["%g" % v for v in dists] + (["box"] if len(d) > len(dists) else [])
         out.append((len(xy), len(dots), match.localization_metrics(d2, len(xy), len(dots), d), labels))
     return out
+
+
+def game_group(L, grp, res):
+    """GAME(0..L) of one group's images: ONE RegionSummer.sum over the group's maps (the nine crop maps of the 3 x 3 path add into their
+    image's cells) on the level-L grid of each 384-high image; the dots are binned by the grid's own half-open rule on the host.
+    -> per image [GAME(0), ..., GAME(L)]."""
+    from countr_amd import frames, regions
+    sizes = [(int(r[1].shape[1]), frames.NEW_H) for r in res]      # the evaluated image's own size: the placement is the identity
+    grids = [regions.game_grid(h, w, L) for w, h in sizes]
+    cells = frames.region_maps([(r[0], r[1]) for r in res], sizes, [r[2] for r in res], [[g] for g in grids])
+    n = 1 << L
+    return [regions.game_levels(counts.reshape(n, n), regions.grid_dot_counts(it[6], g)) for it, g, (counts, _area) in zip(grp, grids, cells)]
+
+
+def print_game(L, names, games):
+    """One line per image, then the run's (this rank's shard's) {"GAME": ...} line -> the results.csv columns of --report."""
+    header = ["game_%d" % l for l in range(L + 1)]
+    cells = {}
+    for name, g in zip(names, games):
+        print("%s: game: %s" % (name, json.dumps({str(l): v for l, v in enumerate(g)})))
+        cells[name] = ["%.4f" % v for v in g]
+    n = max(len(games), 1)
+    print(json.dumps({"GAME": {str(l): sum(g[l] for g in games) / n for l in range(L + 1)}, "images": len(games)}))
+    return header, cells
 
 
 def print_localization(args, dists, names, located):

@@ -3,12 +3,15 @@ build, the CPU tools) stays free of torch."""
 
 
 def __getattr__(name):
-    if name in ("count_frames", "locate_frames", "FramePrep"):
+    if name in ("count_frames", "locate_frames", "count_regions", "FramePrep"):
         from . import frames
         return getattr(frames, name)
     if name in ("PeakFinder", "peaks_host", "Peaks"):
         from . import peaks
         return getattr(peaks, name)
+    if name in ("RegionSummer", "regions_host"):
+        from . import regions
+        return getattr(regions, name)
     if name in ("match_host", "PointMatcher", "localization_metrics", "LocalizationTotals"):
         from . import match
         return getattr(match, name)

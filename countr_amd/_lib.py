@@ -128,3 +128,42 @@ def check(rc, what=""):
 def exported_symbols():
     """Names declared in include/countr_hip.h, which are the names the library exports."""
     return sorted(PROTOS)
+
+
+# ---- the extension library: exports that came after the ABI of countr_hip.h was closed.  include/countr_hip_ext.h is its one statement,
+# in the same dialect; nothing of it enters CONSTS / STRUCTS / PROTOS or this module's COUNTR_* globals.
+EXT_LIB_PATH = os.environ.get("COUNTR_LIB_EXT", os.path.join(_HERE, "libcountr_hip_ext.so"))
+EXT_HEADER = os.path.join(_HERE, "..", "include", "countr_hip_ext.h")
+EXT_CONSTS, EXT_STRUCTS, EXT_PROTOS = parse_header(open(EXT_HEADER).read())
+RegionMap, Region = EXT_STRUCTS["countr_region_map"], EXT_STRUCTS["countr_region"]
+_ext = None
+
+
+def ext_lib():
+    """Load (once) and return the ctypes handle of libcountr_hip_ext.so, bound from its header; raises CountrError if it is not built or
+    was built from another version of the header."""
+    global _ext
+    if _ext is None:
+        if not os.path.exists(EXT_LIB_PATH):
+            raise CountrError(
+                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
+                "the HIP path has no CPU fallback" % os.path.basename(EXT_LIB_PATH))
+        L = C.CDLL(EXT_LIB_PATH)
+        for name, (restype, argtypes) in EXT_PROTOS.items():
+            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
+            fn.restype, fn.argtypes = restype, argtypes
+        if L.countr_ext_version() != EXT_CONSTS["COUNTR_EXT_ABI_VERSION"]:
+            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
+                              % (os.path.basename(EXT_LIB_PATH), L.countr_ext_version(), EXT_CONSTS["COUNTR_EXT_ABI_VERSION"]))
+        _ext = L
+    return _ext
+
+
+def ext_check(rc, what=""):
+    if rc != 0:
+        raise CountrError("%s failed (rc=%d): %s" % (what or "countr_ext call", rc, (ext_lib().countr_ext_last_error() or b"").decode()))
+
+
+def ext_exported_symbols():
+    """Names declared in include/countr_hip_ext.h, which are the names the extension library exports."""
+    return sorted(EXT_PROTOS)

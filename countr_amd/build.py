@@ -1,4 +1,4 @@
-"""Build libcountr_hip.so (all HIP kernels + the C ABI) in-tree for gfx950.
+"""Build libcountr_hip.so (all HIP kernels + the C ABI) and the extension library libcountr_hip_ext.so in-tree for gfx950.
 
 hipcc cross-compiles without a GPU, so this runs in the build container and on the GPU box.
 The .so is git-ignored but travels with the repo snapshot to the GPU box.
@@ -34,30 +34,45 @@ def _digest(paths, extra=""):
 # (precision="bf16") and IEEE fp16 in libcountr_hip_f16.so (precision="fp16", -DCOUNTR_HALF_FP16=1: csrc/common.hpp)
 LIB_F16 = os.path.join(HERE, "libcountr_hip_f16.so")
 VARIANTS = (("", LIB, []), ("f16", LIB_F16, ["-DCOUNTR_HALF_FP16=1"]))
+# the extension library (include/countr_hip_ext.h): exports that came after the ABI of countr_hip.h was closed.  Its sources live in
+# csrc_ext/, outside the csrc/*.hip glob, and are built once: nothing in them has a 16-bit operand
+CSRC_EXT = os.path.join(HERE, "csrc_ext")
+LIB_EXT = os.path.join(HERE, "libcountr_hip_ext.so")
+EXT_HEADER = os.path.join(HERE, "..", "include", "countr_hip_ext.h")
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"]
+
+
+def ext_sources():
+    return sorted(glob.glob(os.path.join(CSRC_EXT, "*.hip")))
 
 
 def build(force=False, verbose=True):
-    """Compile every csrc/*.hip for gfx950 and link libcountr_hip.so + libcountr_hip_f16.so.  An object is reused only if the record
+    """Compile every csrc/*.hip for gfx950 and link libcountr_hip.so + libcountr_hip_f16.so, and every csrc_ext/*.hip into
+    libcountr_hip_ext.so.  An object is reused only if the record
     written when it was compiled (build/<variant>/<src>.o.sha256: content hash of the source, of every shared header and of the flags)
     still matches -- content, not mtime, so a snapshot copy or a checkout cannot make a stale object look fresh.  COUNTR_BUILD_FORCE=1
     (or force=True / --force) recompiles everything.  Prints how many objects were compiled."""
     force = force or os.environ.get("COUNTR_BUILD_FORCE", "0") == "1"
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    hdrs = glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(HERE, "..", "include", "*.h"))
+    shared = glob.glob(os.path.join(CSRC, "*.hpp"))
+    hdrs = shared + [os.path.join(HERE, "..", "include", "countr_hip.h")]
     procs, reused, total = [], 0, 0
     links = []
     jobs = int(os.environ.get("COUNTR_BUILD_JOBS", "0")) or max(2, (os.cpu_count() or 4))
-    for tag, lib, extra in VARIANTS:
+    for tag, lib, extra in VARIANTS + (("ext", LIB_EXT, None),):
         bdir = os.path.join(HERE, "build", tag) if tag else os.path.join(HERE, "build")
         os.makedirs(bdir, exist_ok=True)
         objs, fresh = [], False
-        for src in sources():
+        for src in sources() if extra is not None else ext_sources():
             obj = os.path.join(bdir, os.path.basename(src) + ".o")
             objs.append(obj)
             total += 1
-            cmd = ([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-mllvm", "-amdgpu-mfma-vgpr-form=1"] + extra
-                   + EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj])
-            want = _digest([src] + hdrs, " ".join(cmd[1:-3]))
+            if extra is None:
+                cmd = [hipcc] + FLAGS + ["-c", src, "-o", obj]
+            else:
+                cmd = ([hipcc] + FLAGS + ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] + extra
+                       + EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj])
+            want = _digest([src] + (hdrs if extra is not None else shared + [EXT_HEADER]), " ".join(cmd[1:-3]))
             rec = obj + ".sha256"
             if not force and os.path.exists(obj) and os.path.exists(rec) and open(rec).read().strip() == want:
                 reused += 1
@@ -86,8 +101,9 @@ def build(force=False, verbose=True):
             subprocess.check_call(cmd)
             open(lrec, "w").write(lwant + "\n")
     if verbose:
-        print("build_mode: %s -- %d of %d objects compiled (2 libraries x %d sources), %d reused after a content-hash check (source + headers + flags)"
-              % ("full" if reused == 0 else "incremental", len(procs), total, total // 2, reused), flush=True)
+        print("build_mode: %s -- %d of %d objects compiled (2 libraries x %d sources + %d of the extension library), %d reused after a "
+              "content-hash check (source + headers + flags)"
+              % ("full" if reused == 0 else "incremental", len(procs), total, len(sources()), len(ext_sources()), reused), flush=True)
     return LIB
 
 

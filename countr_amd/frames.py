@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, inference, peaks
+from . import _lib, inference, peaks, regions as regions_
 
 NEW_H = 384
 BOX = 64                    # exemplar crops are 64 x 64 (demo.py:67)
@@ -316,7 +316,7 @@ def locate_maps(results, sizes, crops=None, *, radius=4, threshold=0.0, rel_thre
 
 
 @torch.no_grad()
-def _count_items_crops(model, items, normalization=True, max_s_cnt=1, max_batch=32):
+def count_items_crops(model, items, normalization=True, max_s_cnt=1, max_batch=32):
     """count_items, which also hands back the nine maps of a frame that took the 3 x 3 path: [(count, density map, crops or None), ...]."""
     res = [None] * len(items)
     rest = []
@@ -335,25 +335,122 @@ def _count_items_crops(model, items, normalization=True, max_s_cnt=1, max_batch=
 
 @torch.no_grad()
 def locate_items(model, items, sizes, *, radius=4, threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all", normalization=True,
-                 max_s_cnt=1, max_batch=32):
-    """count_items + locate_maps over device-prepared items: [(count, density map, points, score, total peaks), ...]."""
-    res = _count_items_crops(model, items, normalization, max_s_cnt, max_batch)
+                 max_s_cnt=1, max_batch=32, crops=False):
+    """count_items + locate_maps over device-prepared items: [(count, density map, points, score, total peaks), ...]; with crops=True
+    each tuple ends with the nine maps of the 3 x 3 path, or None."""
+    res = count_items_crops(model, items, normalization, max_s_cnt, max_batch)
     pts = locate_maps([(c, dm) for c, dm, _cr in res], sizes, [cr for _c, _dm, cr in res], radius=radius, threshold=threshold,
                       rel_threshold=rel_threshold, max_points=max_points, keep=keep)
-    return [(c, dm, p, s, t) for (c, dm, _cr), (p, s, t) in zip(res, pts)]
+    return [(c, dm, p, s, t) + ((cr,) if crops else ()) for (c, dm, cr), (p, s, t) in zip(res, pts)]
 
 
 @torch.no_grad()
 def locate_frames(model, frames, boxes=None, *, radius=4, threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all", normalization=True,
-                  max_s_cnt=1, max_batch=32):
+                  max_s_cnt=1, max_batch=32, regions=None):
     """count_frames that also says WHERE: [(count, density map, points float32 [P, 2] as (x, y), score [P]), ...].  count and density map
     are count_frames' bit for bit.  points are the sub-pixel centroids of the map's peaks (countr_amd/peaks.py states the rule) in
     pixel-centre coordinates of the original frame (frame_points), ordered by score; keep="count" keeps the first
     min(P, floor(count + 0.5)) of them.  A frame that takes the 3 x 3 split gets the peaks of its nine crop maps, mapped back through
     crop_points and re-ordered by (score descending, crop, raster index); its returned map stays the last crop's.  The defaults
-    radius=4 and rel_threshold=0.1 are unmeasured: no localisation accuracy figure exists for them."""
+    radius=4 and rel_threshold=0.1 are unmeasured: no localisation accuracy figure exists for them.
+    With regions (count_regions' argument) each tuple gains region_counts float32 [R] and point_region int32 [P]: the first region that
+    contains each point by the regions' own rule (countr_amd/regions.py), -1 = none."""
     device = next(model.parameters()).device
     items = prepare_items(device, frames, boxes)
     sizes = [(int(f.shape[1]), int(f.shape[0])) for f in frames]
-    return [r[:4] for r in locate_items(model, items, sizes, radius=radius, threshold=threshold, rel_threshold=rel_threshold,
-                                        max_points=max_points, keep=keep, normalization=normalization, max_s_cnt=max_s_cnt, max_batch=max_batch)]
+    res = locate_items(model, items, sizes, radius=radius, threshold=threshold, rel_threshold=rel_threshold, max_points=max_points, keep=keep,
+                       normalization=normalization, max_s_cnt=max_s_cnt, max_batch=max_batch, crops=regions is not None)
+    if regions is None:
+        return [r[:4] for r in res]
+    per = frame_regions(regions, sizes)
+    sums = region_maps([(r[0], r[1]) for r in res], sizes, [r[5] for r in res], per)
+    return [r[:4] + (counts, regions_.point_regions(r[2], rs)) for r, rs, (counts, _area) in zip(res, per, sums)]
+
+
+def map_placement(W, H, new_w):
+    """The placement (ax, bx, ay, by) of a frame's [384, new_w] map in pixel-centre coordinates of the original W x H frame, in float64:
+    frame_points as one multiply and one add per axis -- x = (W / new_w) cx + frame_points(0, 0)'s x."""
+    x0, y0 = frame_points(0.0, 0.0, W, H, new_w)
+    return (np.float64(W) / new_w, np.float64(x0), np.float64(H) / NEW_H, np.float64(y0))
+
+
+def crop_placement(k, h, w, placement):
+    """The placement of crop k's [h, w] map (3 x 3 split of an [h, w] image whose own placement is given): crop_points composed with it.
+    Crop pixel cx lies at image column (w // 3) / w * cx + crop_points(0, 0)'s column, and an image column c at ax * c + bx."""
+    ax, bx, ay, by = placement
+    cy0, cx0 = crop_points(0.0, 0.0, k, h, w)
+    return (ax * (np.float64(w // 3) / w), ax * np.float64(cx0) + bx, ay * (np.float64(h // 3) / h), ay * np.float64(cy0) + by)
+
+
+def _is_grid(r):
+    return isinstance(r, (tuple, list)) and len(r) == 3 and isinstance(r[0], str)
+
+
+def _is_region(r):
+    if _is_grid(r):
+        return True
+    try:
+        v = np.asarray(r, np.float64)
+    except (TypeError, ValueError):
+        return False
+    return v.ndim == 2 and v.shape[1] == 2
+
+
+def frame_regions(regions, sizes):
+    """count_regions' `regions` -> one list of regions.region() per frame.  regions: one list for every frame, or one list per frame; a
+    region is a polygon [(x, y), ...] in pixels of the original frame, or ("grid", gy, gx) = the uniform grid over the frame (explicit
+    boundaries ("grid", ys, xs) pass through)."""
+    regions = list(regions)
+    per = [regions] * len(sizes) if all(_is_region(r) for r in regions) else regions
+    if len(per) != len(sizes):
+        raise ValueError("regions: one list for every frame, or one list per frame")
+    out = []
+    for rs, (W, H) in zip(per, sizes):
+        out.append([regions_.frame_grid(W, H, int(r[1]), int(r[2])) if _is_grid(r) and np.ndim(r[1]) == 0 else regions_.region(r) for r in rs])
+    return out
+
+
+def region_maps(results, sizes, crops, regions):
+    """The regional counts of counted frames: results [(count, density map [384, new_W] on the device), ...], sizes [(W, H), ...] of the
+    original frames, crops per frame None or the nine maps of the 3 x 3 path, regions as count_regions takes them (frame_regions) ->
+    [(region_counts float32 [R], region_area int32 [R]), ...].  Every map of the call goes through ONE RegionSummer.sum; a split
+    frame's nine crop maps add into the frame's regions.  region_counts[r] = scale * mass[r] / 60 with scale = count / (total / 60)
+    when total > 0, else 1: the scale carries the test-time normalisation and nothing else, so regions that partition the frame sum
+    to count up to the reduction's rounding."""
+    crops = crops or [None] * len(results)
+    regions = frame_regions(regions, sizes)
+    maps, places, set_of_map = [], [], []
+    for f, ((_c, dm), (W, H), cr) in enumerate(zip(results, sizes, crops)):
+        h, w = dm.shape
+        pl = map_placement(W, H, w)
+        for k, m in enumerate(cr if cr is not None else [dm]):
+            maps.append(m)
+            places.append(pl if cr is None else crop_placement(k, h, w, pl))
+            set_of_map.append(f)
+    if not maps:
+        return []
+    maps = [m if (m.dtype == torch.float32 and m.is_contiguous()) else m.float().contiguous() for m in maps]
+    sums = regions_.region_summer(maps[0].device).sum(maps, places, set_of_map, regions)
+    out = []
+    for (count, _dm), (mass, area, total) in zip(results, sums):
+        pred = np.float64(total) / 60
+        scale = np.float64(count) / pred if total > 0 else np.float64(1.0)
+        out.append(((scale * mass.astype(np.float64) / 60).astype(np.float32), area))
+    return out
+
+
+@torch.no_grad()
+def count_regions(model, frames, regions, boxes=None, *, normalization=True, max_s_cnt=1, max_batch=32):
+    """count_frames that also answers "how many in this part of the frame": [(count, density map, region_counts float32 [R], region_area
+    int32 [R]), ...].  regions: one list for every frame or one list per frame; a region is a polygon [(x, y), ...] in pixel-centre
+    coordinates of the original frame (pixel i has centre i) or ("grid", gy, gx), the uniform grid over the frame, which owns gy * gx
+    results, row-major.  count and the map are count_frames' bit for bit.  The counts are sums of the density map over the regions
+    (countr_amd/regions.py states the rule; csrc_ext/regions.hip computes it), scaled as region_maps says; region_area is the number of
+    map pixels whose centre lies in the region.  A frame that takes the 3 x 3 split is summed over its nine crop maps."""
+    device = next(model.parameters()).device
+    items = prepare_items(device, frames, boxes)
+    sizes = [(int(f.shape[1]), int(f.shape[0])) for f in frames]
+    per = frame_regions(regions, sizes)
+    res = count_items_crops(model, items, normalization, max_s_cnt, max_batch)
+    sums = region_maps([(c, dm) for c, dm, _cr in res], sizes, [cr for _c, _dm, cr in res], per)
+    return [(c, dm, counts, area) for (c, dm, _cr), (counts, area) in zip(res, sums)]

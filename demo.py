@@ -11,7 +11,10 @@ the resize to height 384, the 64 x 64 exemplar crops and, for exemplars under 10
 (countr_amd.frames).  The visualisation is image + exemplar outlines + density / 2, clamped to [0, 1], at the resized size.
 `--model_path ""` runs the randomly initialised model (dry runs / tests).  `--points` also locates the objects (countr_amd.frames.locate_items):
 points_<stem>.json = {"count", "total_peaks", "points": [[x, y, score], ...]} in pixel-centre coordinates of the input image is written
-(with --no_viz too), and viz_<name>.jpg is resized back to the input size and gets a small dot per point."""
+(with --no_viz too), and viz_<name>.jpg is resized back to the input size and gets a small dot per point.  `--regions_json FILE` counts
+per region, as demo_zero.py does: {"name": [[x, y], ...], ...} in pixels of the original image -> one printed line per region,
+regions_<stem>.json and the outlines in viz_<name>.jpg (then at the input size too); a frame that takes the 3 x 3 path is summed over
+its nine crop maps.  It works together with --points."""
 import json
 import time
 from argparse import ArgumentParser
@@ -24,7 +27,7 @@ from PIL import Image
 
 import models_mae_cross
 from countr_amd import frames
-from demo_zero import add_points_args, draw_points, write_points
+from demo_zero import add_points_args, add_regions_args, draw_points, draw_regions, load_regions, report_regions, write_points
 
 
 def parse_boxes(text):
@@ -40,9 +43,10 @@ def parse_boxes(text):
     return boxes
 
 
-def save_visualisation(sample, density_map, rects, path, points=None, size=None):
+def save_visualisation(sample, density_map, rects, path, points=None, size=None, regions=None):
     """sample [3, h, w] in [0, 1], density_map [h, w]: outlines are drawn at 10 (white after the clamp), the density is halved.
-    points: [(x, y), ...] of the input image of size (W, H): the picture is resized to that size and dotted."""
+    points: [(x, y), ...] and regions: polygons of the input image of size (W, H): the picture is resized to that size, then outlined
+    and dotted."""
     _, h, w = sample.shape
     box_map = torch.zeros(h, w, device=sample.device)
     for y1, x1, y2, x2 in rects or []:
@@ -53,8 +57,12 @@ def save_visualisation(sample, density_map, rects, path, points=None, size=None)
         box_map[yb, xa:xb + 1] = 10
     fig = torch.clamp(sample + box_map.unsqueeze(0) + density_map.unsqueeze(0) / 2, 0, 1)
     im = Image.fromarray((fig.permute(1, 2, 0).cpu().numpy() * 255.0 + 0.5).astype(np.uint8))
+    if points is not None or regions is not None:
+        im = im.resize(size, Image.BILINEAR)
+    if regions is not None:
+        draw_regions(im, regions)
     if points is not None:
-        im = draw_points(im.resize(size, Image.BILINEAR), points)
+        draw_points(im, points)
     im.save(path)
 
 
@@ -69,9 +77,11 @@ def main():
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     p.add_argument("--no_viz", action="store_true", help="counts only, no viz_*.jpg")
     add_points_args(p)
+    add_regions_args(p)
     args = p.parse_args()
     args.output_path.mkdir(exist_ok=True, parents=True)
     device = torch.device("cuda")
+    region_names, polygons = load_regions(args.regions_json)
 
     if not args.model_path:
         torch.manual_seed(0)          # dry runs without a checkpoint: the same random model every time
@@ -97,23 +107,30 @@ def main():
         t0 = time.perf_counter()
         items = frames.prepare_items(device, raw, boxes)
         sizes = [(r.shape[1], r.shape[0]) for r in raw]
+        summed = [None] * len(paths)
         if args.points:
             results = frames.locate_items(model, items, sizes, radius=args.points_radius, rel_threshold=args.points_rel_threshold,
-                                          keep=args.points_keep)
+                                          keep=args.points_keep, crops=True)
+        elif polygons is not None:
+            results = [(c, dm, None, None, None, cr) for c, dm, cr in frames.count_items_crops(model, items)]
         else:
-            results = [r + (None, None, None) for r in frames.count_items(model, items)]
+            results = [r + (None, None, None, None) for r in frames.count_items(model, items)]
+        if polygons is not None:      # the nine crop maps of a frame that took the 3 x 3 path add into the frame's regions
+            summed = frames.region_maps([r[:2] for r in results], sizes, [r[5] for r in results], frames.frame_regions(polygons, sizes))
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / len(paths)
-        for pth, (sample, _ex, rects), (pred_cnt, dm, pts, score, total), size in zip(paths, items, results, sizes):
+        for pth, (sample, _ex, rects), (pred_cnt, dm, pts, score, total, _crops), size, reg in zip(paths, items, results, sizes, summed):
             done += 1
             if pts is not None:
                 write_points(args.output_path / ("points_%s.json" % pth.stem), pred_cnt, total, pts, score)
             if not args.no_viz:
-                save_visualisation(sample[0], dm.float(), rects, args.output_path / ("viz_%s.jpg" % pth.stem), pts, size)
+                save_visualisation(sample[0], dm.float(), rects, args.output_path / ("viz_%s.jpg" % pth.stem), pts, size, regions=polygons)
             if len(inputs) > 1:
                 print("[%3d/%d] %s:\tcount = %5.2f  -  time = %5.2f" % (done, len(inputs), pth.name, pred_cnt, dt))
             else:
                 print("Count:", pred_cnt, "- Time:", dt)
+            if reg is not None:
+                report_regions(args.output_path / ("regions_%s.json" % pth.stem), pred_cnt, region_names, reg[0], reg[1])
 
 
 if __name__ == "__main__":

@@ -12,8 +12,11 @@ resized back to the input size) is written with PIL, since torchvision is not pa
 are decoded by PIL, handed over as uint8 pixels and resized by countr_frame_resize_u8 (same bits as the host resize, so same counts);
 the printed time then includes the preparation.  `--points` also locates the objects (countr_amd.frames.locate_maps: the peaks of the
 density map, found on the device): viz_<name>.jpg gets a small dot per point and points_<stem>.json = {"count", "total_peaks", "points":
-[[x, y, score], ...]} (pixel-centre coordinates of the input image) is written, with --no_viz too.  demo.py is the few-shot counterpart
-(exemplar boxes)."""
+[[x, y, score], ...]} (pixel-centre coordinates of the input image) is written, with --no_viz too.  `--regions_json FILE` counts per
+region: FILE is {"name": [[x, y], ...], ...}, polygons in pixels of the original image (pixel-centre coordinates: pixel i has centre
+i); the density map is summed over each polygon on the device (countr_amd.frames.region_maps), one line per region is printed,
+regions_<stem>.json = {"count", "regions": {name: {"count", "area"}}} is written (area = map pixels inside) and viz_<name>.jpg gets the
+outlines.  It works together with --points.  demo.py is the few-shot counterpart (exemplar boxes)."""
 import json
 import time
 from argparse import ArgumentParser
@@ -63,8 +66,40 @@ def add_points_args(p):
     p.add_argument("--points_keep", default="all", choices=["all", "count"], help="count: keep the round(count) highest peaks")
 
 
-def save_visualisation(sample, density_map, pred_cnt, path, old_w, old_h, points=None):
-    """demo_zero.py:77-90; points: [(x, y), ...] of the input image, dotted after the resize back to its size."""
+def add_regions_args(p):
+    p.add_argument("--regions_json", type=Path, default=None,
+                   help='count per region: JSON {"name": [[x, y], ...], ...}, polygons in pixels of the original image')
+
+
+def load_regions(path):
+    """--regions_json -> (names, polygons) or (None, None) without the flag."""
+    if path is None:
+        return None, None
+    named = json.load(open(path))
+    if not isinstance(named, dict) or not named:
+        raise ValueError('--regions_json: a JSON object {"name": [[x, y], ...], ...}')
+    return list(named), [[(float(x), float(y)) for x, y in poly] for poly in named.values()]
+
+
+def draw_regions(image, polygons):
+    """The outline of each polygon (pixel-centre coordinates of `image`)."""
+    draw = ImageDraw.Draw(image)
+    for poly in polygons:
+        pts = [(x + 0.5, y + 0.5) for x, y in poly]
+        draw.line(pts + pts[:1], fill=(255, 255, 0), width=1)
+    return image
+
+
+def report_regions(path, pred_cnt, names, counts, area):
+    """One printed line per region and regions_<stem>.json."""
+    for name, c, a in zip(names, counts, area):
+        print("  region %s: count = %5.2f, area = %d" % (name, c, a))
+    with open(path, "w") as f:
+        json.dump({"count": pred_cnt, "regions": {name: {"count": float(c), "area": int(a)} for name, c, a in zip(names, counts, area)}}, f)
+
+
+def save_visualisation(sample, density_map, pred_cnt, path, old_w, old_h, points=None, regions=None):
+    """demo_zero.py:77-90; points: [(x, y), ...] and regions: polygons of the input image, drawn after the resize back to its size."""
     _, h, w = sample.shape
     pred_fig = torch.stack((density_map, torch.zeros_like(density_map), torch.zeros_like(density_map)))
     count_im = Image.new(mode="RGB", size=(w, h), color=(0, 0, 0))
@@ -73,6 +108,8 @@ def save_visualisation(sample, density_map, pred_cnt, path, old_w, old_h, points
     fig = torch.clamp(sample / 2 + pred_fig / 2 + count_im, 0, 1)
     arr = (fig.permute(1, 2, 0).cpu().numpy() * 255.0 + 0.5).astype(np.uint8)
     im = Image.fromarray(arr).resize((old_w, old_h), Image.BILINEAR)
+    if regions is not None:
+        draw_regions(im, regions)
     if points is not None:
         draw_points(im, points)
     im.save(path)
@@ -89,9 +126,11 @@ def main():
     p.add_argument("--device_prep", action="store_true",
                    help="hand the decoded uint8 frames to the device and resize them there (countr_amd.frames) instead of with PIL on the host")
     add_points_args(p)
+    add_regions_args(p)
     args = p.parse_args()
     args.output_path.mkdir(exist_ok=True, parents=True)
     device = torch.device("cuda")
+    region_names, polygons = load_regions(args.regions_json)
 
     if not args.model_path:
         torch.manual_seed(0)          # dry runs without a checkpoint: the same random model every time
@@ -123,19 +162,25 @@ def main():
         if args.points:
             located = frames.locate_maps(results, [(w, h) for _s, _b, w, h in loaded], radius=args.points_radius,
                                          rel_threshold=args.points_rel_threshold, keep=args.points_keep)
+        summed = [None] * len(paths)
+        if polygons is not None:
+            sizes = [(w, h) for _s, _b, w, h in loaded]
+            summed = frames.region_maps(results, sizes, None, frames.frame_regions(polygons, sizes))
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / len(paths)
-        for pth, (sample, _b, old_w, old_h), (pred_cnt, dm), loc in zip(paths, loaded, results, located):
+        for pth, (sample, _b, old_w, old_h), (pred_cnt, dm), loc, reg in zip(paths, loaded, results, located, summed):
             done += 1
             if loc is not None:
                 write_points(args.output_path / ("points_%s.json" % pth.stem), pred_cnt, loc[2], loc[0], loc[1])
             if not args.no_viz:
                 save_visualisation(sample.to(device), dm.float(), pred_cnt, args.output_path / ("viz_%s.jpg" % pth.stem), old_w, old_h,
-                                   points=loc[0] if loc is not None else None)
+                                   points=loc[0] if loc is not None else None, regions=polygons)
             if len(inputs) > 1:
                 print("[%3d/%d] %s:\tcount = %5.2f  -  time = %5.2f" % (done, len(inputs), pth.name, pred_cnt, dt))
             else:
                 print("Count:", pred_cnt, "- Time:", dt)
+            if reg is not None:
+                report_regions(args.output_path / ("regions_%s.json" % pth.stem), pred_cnt, region_names, reg[0], reg[1])
 
 
 if __name__ == "__main__":
