@@ -3,7 +3,7 @@ build, the CPU tools) stays free of torch."""
 
 
 def __getattr__(name):
-    if name in ("count_frames", "locate_frames", "count_regions", "FramePrep"):
+    if name in ("count_frames", "locate_frames", "count_regions", "count_classes", "ClassCounts", "FramePrep"):
         from . import frames
         return getattr(frames, name)
     if name in ("PeakFinder", "peaks_host", "Peaks"):
@@ -12,6 +12,9 @@ def __getattr__(name):
     if name in ("RegionSummer", "regions_host"):
         from . import regions
         return getattr(regions, name)
+    if name in ("ClassFolder", "classes_host"):
+        from . import classes
+        return getattr(classes, name)
     if name in ("match_host", "PointMatcher", "localization_metrics", "LocalizationTotals"):
         from . import match
         return getattr(match, name)

@@ -167,3 +167,42 @@ def ext_check(rc, what=""):
 def ext_exported_symbols():
     """Names declared in include/countr_hip_ext.h, which are the names the extension library exports."""
     return sorted(EXT_PROTOS)
+
+
+# ---- the classes library: the fold of a frame's class maps into a label map.  include/countr_hip_classes.h is its one statement, in
+# the same dialect; nothing of it enters the bindings above or this module's COUNTR_* globals.
+CLASSES_LIB_PATH = os.environ.get("COUNTR_LIB_CLASSES", os.path.join(_HERE, "libcountr_hip_classes.so"))
+CLASSES_HEADER = os.path.join(_HERE, "..", "include", "countr_hip_classes.h")
+CLASSES_CONSTS, CLASSES_STRUCTS, CLASSES_PROTOS = parse_header(open(CLASSES_HEADER).read())
+ClassSet = CLASSES_STRUCTS["countr_class_set"]
+_classes = None
+
+
+def classes_lib():
+    """Load (once) and return the ctypes handle of libcountr_hip_classes.so, bound from its header; raises CountrError if it is not built
+    or was built from another version of the header."""
+    global _classes
+    if _classes is None:
+        if not os.path.exists(CLASSES_LIB_PATH):
+            raise CountrError(
+                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
+                "the HIP path has no CPU fallback" % os.path.basename(CLASSES_LIB_PATH))
+        L = C.CDLL(CLASSES_LIB_PATH)
+        for name, (restype, argtypes) in CLASSES_PROTOS.items():
+            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
+            fn.restype, fn.argtypes = restype, argtypes
+        if L.countr_classes_version() != CLASSES_CONSTS["COUNTR_CLASSES_ABI_VERSION"]:
+            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
+                              % (os.path.basename(CLASSES_LIB_PATH), L.countr_classes_version(), CLASSES_CONSTS["COUNTR_CLASSES_ABI_VERSION"]))
+        _classes = L
+    return _classes
+
+
+def classes_check(rc, what=""):
+    if rc != 0:
+        raise CountrError("%s failed (rc=%d): %s" % (what or "countr_classes call", rc, (classes_lib().countr_classes_last_error() or b"").decode()))
+
+
+def classes_exported_symbols():
+    """Names declared in include/countr_hip_classes.h, which are the names the classes library exports."""
+    return sorted(CLASSES_PROTOS)

@@ -1,4 +1,5 @@
-"""Build libcountr_hip.so (all HIP kernels + the C ABI) and the extension library libcountr_hip_ext.so in-tree for gfx950.
+"""Build libcountr_hip.so (all HIP kernels + the C ABI) and the extension libraries libcountr_hip_ext.so and libcountr_hip_classes.so
+in-tree for gfx950.
 
 hipcc cross-compiles without a GPU, so this runs in the build container and on the GPU box.
 The .so is git-ignored but travels with the repo snapshot to the GPU box.
@@ -39,6 +40,10 @@ VARIANTS = (("", LIB, []), ("f16", LIB_F16, ["-DCOUNTR_HALF_FP16=1"]))
 CSRC_EXT = os.path.join(HERE, "csrc_ext")
 LIB_EXT = os.path.join(HERE, "libcountr_hip_ext.so")
 EXT_HEADER = os.path.join(HERE, "..", "include", "countr_hip_ext.h")
+# the classes library (include/countr_hip_classes.h), built like the extension library, from csrc_classes/
+CSRC_CLASSES = os.path.join(HERE, "csrc_classes")
+LIB_CLASSES = os.path.join(HERE, "libcountr_hip_classes.so")
+CLASSES_HEADER = os.path.join(HERE, "..", "include", "countr_hip_classes.h")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"]
 
 
@@ -46,9 +51,17 @@ def ext_sources():
     return sorted(glob.glob(os.path.join(CSRC_EXT, "*.hip")))
 
 
+def classes_sources():
+    return sorted(glob.glob(os.path.join(CSRC_CLASSES, "*.hip")))
+
+
+# the libraries built once, without a 16-bit twin: tag -> (library, sources, its header)
+SINGLE = {"ext": (LIB_EXT, ext_sources, EXT_HEADER), "classes": (LIB_CLASSES, classes_sources, CLASSES_HEADER)}
+
+
 def build(force=False, verbose=True):
     """Compile every csrc/*.hip for gfx950 and link libcountr_hip.so + libcountr_hip_f16.so, and every csrc_ext/*.hip into
-    libcountr_hip_ext.so.  An object is reused only if the record
+    libcountr_hip_ext.so, every csrc_classes/*.hip into libcountr_hip_classes.so.  An object is reused only if the record
     written when it was compiled (build/<variant>/<src>.o.sha256: content hash of the source, of every shared header and of the flags)
     still matches -- content, not mtime, so a snapshot copy or a checkout cannot make a stale object look fresh.  COUNTR_BUILD_FORCE=1
     (or force=True / --force) recompiles everything.  Prints how many objects were compiled."""
@@ -59,11 +72,11 @@ def build(force=False, verbose=True):
     procs, reused, total = [], 0, 0
     links = []
     jobs = int(os.environ.get("COUNTR_BUILD_JOBS", "0")) or max(2, (os.cpu_count() or 4))
-    for tag, lib, extra in VARIANTS + (("ext", LIB_EXT, None),):
+    for tag, lib, extra in VARIANTS + tuple((t, lib_, None) for t, (lib_, _s, _h) in SINGLE.items()):
         bdir = os.path.join(HERE, "build", tag) if tag else os.path.join(HERE, "build")
         os.makedirs(bdir, exist_ok=True)
         objs, fresh = [], False
-        for src in sources() if extra is not None else ext_sources():
+        for src in sources() if extra is not None else SINGLE[tag][1]():
             obj = os.path.join(bdir, os.path.basename(src) + ".o")
             objs.append(obj)
             total += 1
@@ -72,7 +85,7 @@ def build(force=False, verbose=True):
             else:
                 cmd = ([hipcc] + FLAGS + ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] + extra
                        + EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj])
-            want = _digest([src] + (hdrs if extra is not None else shared + [EXT_HEADER]), " ".join(cmd[1:-3]))
+            want = _digest([src] + (hdrs if extra is not None else shared + [SINGLE[tag][2]]), " ".join(cmd[1:-3]))
             rec = obj + ".sha256"
             if not force and os.path.exists(obj) and os.path.exists(rec) and open(rec).read().strip() == want:
                 reused += 1
@@ -101,9 +114,9 @@ def build(force=False, verbose=True):
             subprocess.check_call(cmd)
             open(lrec, "w").write(lwant + "\n")
     if verbose:
-        print("build_mode: %s -- %d of %d objects compiled (2 libraries x %d sources + %d of the extension library), %d reused after a "
+        print("build_mode: %s -- %d of %d objects compiled (2 libraries x %d sources + %d of the extension library + %d of the classes library), %d reused after a "
               "content-hash check (source + headers + flags)"
-              % ("full" if reused == 0 else "incremental", len(procs), total, len(sources()), len(ext_sources()), reused), flush=True)
+              % ("full" if reused == 0 else "incremental", len(procs), total, len(sources()), len(ext_sources()), len(classes_sources()), reused), flush=True)
     return LIB
 
 

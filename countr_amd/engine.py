@@ -1460,6 +1460,38 @@ class Engine:
             self.pipe_join()
         return p.buf["out"]
 
+    def forward_loaded_tail(self, B, shot_num):
+        """The class-dependent tail of forward_loaded: a forward of plan (B, shot_num) has run on the windows now in p.buf["img"], and
+        p.buf["boxes"] holds ANOTHER set of exemplars for the same windows.  Runs only what reads the exemplars -- the exemplar CNN and
+        the blocks' wk | wv products (p.ex_range), then everything from the first cross-attention on (p.first_xattn) -- over the latent,
+        dx0 and the first block's x1 / q the earlier forward left: an inference plan writes them once and never again (_dec_block_fwd).
+        Same launches on the same data as a full forward_loaded of these exemplars: bit-identical maps.  Zero-shot plans have nothing
+        class-dependent: the output is returned as it stands.  (The warm-up hints inside the launches may name a panel whose consumer
+        no longer follows; they are reads.)"""
+        p = self.plan(B, int(shot_num), False)
+        if p.ex_range is not None:
+            if "tail" not in p.sched:
+                ex, xi = p.ex_range, p.first_xattn
+                if xi is None or not (p.enc_ops <= ex[0] <= ex[1] <= xi):
+                    raise _lib.CountrError("forward_loaded_tail: plan (%d, %d) has no class-independent prefix" % (B, int(shot_num)))
+                p.sched["tail"] = p.fwd[ex[0]:ex[1]] + p.fwd[xi:]
+            self.run(p.sched["tail"])
+        return p.buf["out"]
+
+    def forward_loaded_from(self, B, shot_num, src_shot_num):
+        """forward_loaded of plan (B, shot_num) without its encoder: the latent of the windows is copied from plan (B, src_shot_num),
+        whose forward has run on them (the encoder never sees the exemplars), and the decoder side runs as the pipelined forward runs it
+        once its latent is in place (decoder_ops_with_exemplar_lane).  p.buf["boxes"] of plan (B, shot_num) holds the exemplars.
+        Bit-identical to a full forward_loaded(B, shot_num) on the same windows."""
+        p = self.plan(B, int(shot_num), False)       # (first: building it may grow the shared scratch and drop the other plans)
+        src = self.plans.get((B, int(src_shot_num), False))
+        if src is None:
+            raise _lib.CountrError("forward_loaded_from: no forward of plan (%d, %d) has run on the present buffers" % (B, int(src_shot_num)))
+        if src is not p:
+            p.buf["latent"].view(-1).copy_(src.buf["latent"].view(-1), non_blocking=True)
+        self.run(self.decoder_ops_with_exemplar_lane(p))
+        return p.buf["out"]
+
     def backward(self, B, shot_num, dout):
         """Decoder-side backward for the last train-mode forward of plan (B, shot_num); fills self.G."""
         p = self.plan(B, int(shot_num), True)

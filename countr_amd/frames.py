@@ -5,12 +5,13 @@ The preparation the reference leaves to PIL / torchvision on the host -- resize 
 exemplars (:84-99) -- runs as HIP kernels on the stream the forward runs on (csrc/frames.hip: countr_frame_resize_u8,
 countr_crop_resize_f32).  The prepared image equals PIL's BILINEAR resize + ToTensor bit for bit, and everything behind it is
 inference.count_images / density_maps unchanged, so the results equal the host-prepared path's.  There is no host fallback."""
+import collections
 import ctypes as C
 
 import numpy as np
 import torch
 
-from . import _lib, inference, peaks, regions as regions_
+from . import _lib, classes as classes_, inference, peaks, regions as regions_
 
 NEW_H = 384
 BOX = 64                    # exemplar crops are 64 x 64 (demo.py:67)
@@ -255,6 +256,87 @@ def count_frames(model, frames, boxes=None, normalization=True, max_s_cnt=1, max
     counted as inference.count_images counts them -- one forward per <= max_batch windows, the encoder pipelined across groups."""
     device = next(model.parameters()).device
     return count_items(model, prepare_items(device, frames, boxes), normalization, max_s_cnt, max_batch)
+
+
+ClassCounts = collections.namedtuple("ClassCounts", "names counts maps labels won total area")
+
+
+@torch.no_grad()
+def count_classes(model, frames, classes, *, normalization=True, max_s_cnt=1, max_batch=32, fold=True, floor=0.0):
+    """Several object classes per frame from one encoder pass.  frames: as for count_frames; classes: a dict name -> boxes, boxes being
+    what count_frames takes (None = zero-shot, or one list of (x1, y1, x2, y2) per frame); insertion order is the class index.  Returns
+    per frame a ClassCounts(names, counts, maps, labels, won, total, area): counts[c] and maps[c] are what count_frames(model, frames,
+    classes[names[c]]) returns for that frame, bit for bit -- the 3 x 3 split for tiny exemplars, the test-time normalisation and the
+    grouping by shot count included.
+    Sharing.  The frames are prepared once.  Every class forms its forward batches as count_frames forms them
+    (inference.class_batches); batches of different classes over the same windows and of the same batch size run ONE encoder forward
+    (inference.density_maps_shared): the encoder and the first decoder block's self-attention half never see the exemplars.  A class
+    whose frames take another path (one frame on the 3 x 3 split, say) has other batches and runs its own encoder for them.
+    The fold (fold=True, at most 16 classes; countr_amd/classes.py states the rule, csrc_classes/classes.hip computes it): labels is a
+    uint8 device tensor [384, new_W] naming per pixel the class with the largest scale[c] * maps[c] (255: none above floor), with
+    scale[c] = counts[c] / sum(maps[c]) (1 / 60 where the sum is 0), so that total[c] ~ counts[c]; won[c] is the part of total[c] on
+    the pixels class c owns and area[c] their number (numpy arrays).  A frame on which ANY class took the 3 x 3 split has, for that
+    class, nine maps of another geometry: it gets labels = won = total = area = None.  With fold=False the four fields are None and any
+    number of classes is allowed."""
+    names = list(classes)
+    if fold and len(names) > classes_.MAX_CLASSES:
+        raise ValueError("count_classes: the fold takes at most %d classes, got %d (fold=False takes any number)"
+                         % (classes_.MAX_CLASSES, len(names)))
+    device = next(model.parameters()).device
+    images = frame_prep(device).prepare(frames)
+    F_ = len(images)
+    widths = [int(im.shape[-1]) for im in images]
+    ex, rects, split, groups = [], [], [], collections.OrderedDict()
+    for c, name in enumerate(names):
+        boxes = classes[name]
+        ex.append([]); rects.append([]); split.append([])
+        for f, im in enumerate(images):
+            bx = boxes[f] if boxes is not None else None
+            if bx is not None and len(bx) > 0:
+                e, r = exemplars(im, bx, int(frames[f].shape[1]), int(frames[f].shape[0]))
+            else:
+                e, r = torch.zeros(1, 0, device=im.device), None
+            ex[c].append(e); rects[c].append(r)
+            split[c].append(r is not None and inference._small_exemplars(r) >= max_s_cnt)
+        shots = [int(e.shape[1]) if e.nelement() > 0 else 0 for e in ex[c]]
+        for S, variants, _windows, bucket in inference.class_batches(widths, shots, split[c], max_batch):
+            groups.setdefault((bucket, tuple(variants)), []).append((c, S))
+    crops, dm = {}, {}                      # frame -> its nine upscaled crops; (class, variant) -> map
+    for (_bucket, variants), members in groups.items():
+        for f, k in variants:
+            if k >= 0 and f not in crops:
+                crops[f] = split_crops(images[f])
+        ims = [images[f] if k < 0 else crops[f][k] for f, k in variants]
+        jobs = [([ex[c][f] for f, _k in variants], S) for c, S in members]
+        for (c, _S), maps in zip(members, inference.density_maps_shared(model, ims, jobs, max_batch)):
+            for v, m in zip(variants, maps):
+                dm[(c, v)] = m
+    counts = [[None] * len(names) for _ in range(F_)]
+    maps = [[None] * len(names) for _ in range(F_)]
+    sums = {}
+    for f in range(F_):
+        for c in range(len(names)):
+            if split[c][f]:
+                nine = [dm[(c, (f, k))] for k in range(9)]
+                pred, m = sum((d.sum() / 60).item() for d in nine), nine[-1]      # (the reference normalises with the LAST crop's map)
+            else:
+                m = dm[(c, (f, -1))]
+                sums[(f, c)] = tot = m.sum()
+                pred = (tot / 60).item()
+            counts[f][c] = inference._normalise(pred, m, rects[c][f], normalization)
+            maps[f][c] = m
+    folded = {}
+    if fold and names:
+        plain = [f for f in range(F_) if not any(split[c][f] for c in range(len(names)))]
+        if plain:
+            tot = torch.stack([sums[(f, c)] for f in plain for c in range(len(names))]).tolist()       # one transfer for every sum
+            sets = []
+            for i, f in enumerate(plain):
+                t = tot[i * len(names):(i + 1) * len(names)]
+                sets.append((maps[f], [counts[f][c] / t[c] if t[c] != 0 else 1.0 / 60 for c in range(len(names))]))
+            for f, r in zip(plain, classes_.class_folder(device).fold(sets, floor)):
+                folded[f] = r
+    return [ClassCounts(tuple(names), tuple(counts[f]), tuple(maps[f]), *folded.get(f, (None, None, None, None))) for f in range(F_)]
 
 
 def frame_points(cy, cx, W, H, new_w):

@@ -95,6 +95,42 @@ def _gather_windows(L, images, plan, h, dst, nb, st):
         dst[nw:].zero_()                       # padding rows only need defined values
 
 
+def _blend_outputs(L, out, images, want_sums, st):
+    """The forward's per-window densities out [>= windows, h, 384], in the order of _native_plan(images), stitched per image
+    (countr_window_blend: one launch per run of consecutive images of one width) -> maps, or (maps, sums)."""
+    import ctypes as C
+    h = images[0].shape[-2]
+    dev = images[0].device
+    res, sums = [None] * len(images), [None] * len(images)
+    row = 0
+    i = 0
+    while i < len(images):                      # runs of consecutive images of one width: one blend launch each
+        w = images[i].shape[-1]
+        j = i
+        while j + 1 < len(images) and images[j + 1].shape[-1] == w:
+            j += 1
+        n = j - i + 1
+        stw = window_starts(w)
+        if not stw:
+            for k in range(i, j + 1):
+                res[k] = torch.zeros(h, w, device=dev)          # narrower than a window: the reference's loop never runs
+                sums[k] = torch.zeros((), device=dev)
+        else:
+            dm = torch.empty(n, h, w, device=dev, dtype=torch.float32)
+            sm = torch.empty(n, device=dev, dtype=torch.float32) if want_sums else None
+            ws = torch.empty(n * int(L.countr_window_blend_blocks(h, w)), device=dev, dtype=torch.float32) if want_sums else None
+            arr = (C.c_int * len(stw))(*stw)
+            _lib.check(L.countr_window_blend(out[row:].data_ptr(), n, len(stw), arr, h, w, dm.data_ptr(), sm.data_ptr() if want_sums else None,
+                                             ws.data_ptr() if want_sums else None, st), "countr_window_blend")
+            for k in range(n):
+                res[i + k] = dm[k]
+                if want_sums:
+                    sums[i + k] = sm[k]
+            row += n * len(stw)
+        i = j + 1
+    return (res, sums) if want_sums else res
+
+
 @torch.no_grad()
 def _native_maps(model, images, boxes, shot_num, max_batch, want_sums, have=None, ahead=None, flags=None):
     """density_maps through the two window kernels of the C ABI (countr_window_gather / countr_window_blend: windows cut straight into
@@ -137,34 +173,7 @@ def _native_maps(model, images, boxes, shot_num, max_batch, want_sums, have=None
         out = eng.forward_loaded_pipelined(nb, shot_num, have, plan_next is not None)
     else:
         out = eng.forward_loaded(nb, shot_num)      # [nb, h, 384], valid until the next forward of this plan
-    res, sums = [None] * len(images), [None] * len(images)
-    row = 0
-    i = 0
-    while i < len(images):                      # runs of consecutive images of one width: one blend launch each
-        w = images[i].shape[-1]
-        j = i
-        while j + 1 < len(images) and images[j + 1].shape[-1] == w:
-            j += 1
-        n = j - i + 1
-        stw = window_starts(w)
-        if not stw:
-            for k in range(i, j + 1):
-                res[k] = torch.zeros(h, w, device=dev)          # narrower than a window: the reference's loop never runs
-                sums[k] = torch.zeros((), device=dev)
-        else:
-            dm = torch.empty(n, h, w, device=dev, dtype=torch.float32)
-            sm = torch.empty(n, device=dev, dtype=torch.float32) if want_sums else None
-            ws = torch.empty(n * int(L.countr_window_blend_blocks(h, w)), device=dev, dtype=torch.float32) if want_sums else None
-            arr = (C.c_int * len(stw))(*stw)
-            _lib.check(L.countr_window_blend(out[row:].data_ptr(), n, len(stw), arr, h, w, dm.data_ptr(), sm.data_ptr() if want_sums else None,
-                                             ws.data_ptr() if want_sums else None, st), "countr_window_blend")
-            for k in range(n):
-                res[i + k] = dm[k]
-                if want_sums:
-                    sums[i + k] = sm[k]
-            row += n * len(stw)
-        i = j + 1
-    return (res, sums) if want_sums else res
+    return _blend_outputs(L, out, images, want_sums, st)
 
 
 @torch.no_grad()
@@ -313,6 +322,99 @@ def count_image(model, samples, boxes, shot_num, pos=None, normalization=True, m
     return (pred, dm, dms) if return_crops else (pred, dm)
 
 
+def image_chunks(widths, max_batch=32):
+    """Positions of consecutive images (given by their widths) grouped into forward batches: as many images as fill one batch of
+    max_batch windows, an image with more windows than that on its own -> [[0, 1, ...], ...]."""
+    g0, chunks = 0, []
+    while g0 < len(widths):                             # as many images as fill one forward batch
+        g1, nwin = g0, 0
+        while g1 < len(widths) and (g1 == g0 or nwin + len(window_starts(widths[g1])) <= max_batch):
+            nwin += len(window_starts(widths[g1]))
+            g1 += 1
+        chunks.append(list(range(g0, g1)))
+        g0 = g1
+    return chunks
+
+
+def class_batches(widths, shots, split, max_batch=32):
+    """The forward batches count_items / count_images form for the frames of ONE exemplar set (a class), from sizes alone: widths [F] of
+    the prepared frames, shots [F] exemplars per frame, split [F] whether the frame takes the 3 x 3 split -> [(shot count, variants,
+    windows, bucket), ...].  A variant is an image that is cut into windows: (frame, -1) = the prepared frame, (frame, k) = crop k of
+    its split, upscaled to the frame's size.  windows = [(variant, start column), ...] in forward order, bucket = the forward batch
+    size.  A split frame is a batch of its own; the others are grouped by shot count and chunked by image_chunks.  Two batches run the
+    same encoder forward iff their windows and buckets are equal: the kernels choose split-K by batch size, so a row is reproducible
+    only inside the same forward batch.  bucket is None where the batch does not fit one native forward (no windows, or more than
+    max_batch of them): density_maps then runs it as before."""
+    out, groups = [], {}
+
+    def batch(S, variants):
+        windows = [(v, s0) for v in variants for s0 in window_starts(widths[v[0]])]
+        fits = (0 < len(windows) <= min(max_batch, 64)
+                and all(len(window_starts(widths[f])) <= MAX_BLEND_WINDOWS for f, _k in variants))
+        out.append((S, variants, windows, _bucket(len(windows), max_batch) if fits else None))
+
+    for f in range(len(widths)):
+        if split[f]:
+            batch(shots[f], [(f, k) for k in range(9)])
+        else:
+            groups.setdefault(shots[f], []).append(f)
+    for S, idxs in groups.items():
+        for sel in image_chunks([widths[f] for f in idxs], max_batch):
+            batch(S, [(idxs[k], -1) for k in sel])
+    return out
+
+
+@torch.no_grad()
+def density_maps_shared(model, images, jobs, max_batch=32):
+    """density_maps of the SAME images for several exemplar sets with one encoder forward: jobs = [(boxes, shot_num), ...], boxes as
+    density_maps takes them -> one list of maps per job, each bit-identical to density_maps(model, images, boxes, shot_num, max_batch).
+    Where the images fit one native forward the windows are gathered once; the first job runs the ordinary forward, every further job
+    of its shot count only the class-dependent tail (engine.forward_loaded_tail), and the first job of another shot count the decoder
+    side on a copy of the latent (engine.forward_loaded_from).  A job's exemplars enter its plan by one indexed copy.  Images that do
+    not fit run through density_maps job by job."""
+    import ctypes as C
+    plan = _native_plan(model, images, max_batch)
+    if plan is None:
+        return [density_maps(model, images, bx, int(S), max_batch) for bx, S in jobs]
+    h = images[0].shape[-2]
+    dev = images[0].device
+    eng = model._engine()
+    L = eng.L
+    eng.check_ln_fold(images[plan[0][0]][:, :, :, plan[0][1]:plan[0][1] + 384])     # (first use of a weight set only: may rebuild the plans)
+    nw = len(plan)
+    nb = _bucket(nw, max_batch)
+    shots = list(dict.fromkeys(int(S) for _bx, S in jobs))
+    for _ in range(2):          # every plan exists before the first forward: building one may grow the shared scratch and drop the others
+        for S in shots:
+            eng.plan(nb, S, False)
+    if any((nb, S, False) not in eng.plans for S in shots):
+        raise _lib.CountrError("density_maps_shared: the engine could not hold the plans of %d shot counts at once" % len(shots))
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _gather_windows(L, images, plan, h, eng.plan(nb, shots[0], False).buf["img"], nb, st)
+    rows = torch.tensor([i for i, _s in plan], device=dev) if any(shots) else None          # window -> its image
+    res = [None] * len(jobs)
+    for S in shots:
+        p = eng.plan(nb, S, False)
+        first = True
+        for j, (boxes, Sj) in enumerate(jobs):
+            if int(Sj) != S:
+                continue
+            if S > 0:
+                bx = p.buf["boxes"].view(nb, S, 3, 64, 64)
+                torch.index_select(torch.cat([b[:, :S] for b in boxes], 0), 0, rows, out=bx[:nw])
+                if nb > nw:
+                    bx[nw:].zero_()
+            if not first:
+                out = eng.forward_loaded_tail(nb, S)
+            elif S == shots[0]:
+                out = eng.forward_loaded(nb, S)     # [nb, h, 384], valid until the next forward of this plan
+            else:
+                out = eng.forward_loaded_from(nb, S, shots[0])
+            first = False
+            res[j] = _blend_outputs(L, out, images, False, st)
+    return res
+
+
 @torch.no_grad()
 def count_images(model, items, normalization=True, max_s_cnt=1, max_batch=32, return_crops=False):
     """Test path over MANY images with windows batched across images: items = [(samples [1,3,384,w], boxes [1,S,3,64,64] or
@@ -328,14 +430,7 @@ def count_images(model, items, normalization=True, max_s_cnt=1, max_batch=32, re
         else:
             groups.setdefault(S, []).append(idx)
     for S, idxs in groups.items():
-        g0, chunks = 0, []
-        while g0 < len(idxs):                           # as many images as fill one forward batch
-            g1, nwin = g0, 0
-            while g1 < len(idxs) and (g1 == g0 or nwin + len(window_starts(items[idxs[g1]][0].shape[-1])) <= max_batch):
-                nwin += len(window_starts(items[idxs[g1]][0].shape[-1]))
-                g1 += 1
-            chunks.append(idxs[g0:g1])
-            g0 = g1
+        chunks = [[idxs[k] for k in sel] for sel in image_chunks([items[i][0].shape[-1] for i in idxs], max_batch)]
         # consecutive forwards of one shot count: the next chunk's encoder forward runs beside this chunk's decoder / head
         stream = density_maps_stream(model, (([items[i][0] for i in sel], [items[i][1] for i in sel]) for sel in chunks), S, max_batch)
         for sel, dms in zip(chunks, stream):

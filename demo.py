@@ -14,7 +14,11 @@ points_<stem>.json = {"count", "total_peaks", "points": [[x, y, score], ...]} in
 (with --no_viz too), and viz_<name>.jpg is resized back to the input size and gets a small dot per point.  `--regions_json FILE` counts
 per region, as demo_zero.py does: {"name": [[x, y], ...], ...} in pixels of the original image -> one printed line per region,
 regions_<stem>.json and the outlines in viz_<name>.jpg (then at the input size too); a frame that takes the 3 x 3 path is summed over
-its nine crop maps.  It works together with --points."""
+its nine crop maps.  It works together with --points.  `--classes_json FILE` counts several classes per image from one encoder pass
+(countr_amd.frames.count_classes): {"name": [[x1, y1, x2, y2], ...], ...} exemplar boxes per class in pixels of the input image, applied
+to every input image -> one printed line per class (count and won count), classes_<stem>.json = {"classes": {name: {"count", "won",
+"area"}}} and viz_<name>.jpg tinted by the dominant class (won and area are null, and nothing is tinted, for an image on which a class
+took the 3 x 3 path).  It replaces --boxes, --points and --regions_json for that run."""
 import json
 import time
 from argparse import ArgumentParser
@@ -66,6 +70,50 @@ def save_visualisation(sample, density_map, rects, path, points=None, size=None,
     im.save(path)
 
 
+# the tint of class 0, 1, 2, ... in viz_<name>.jpg (repeats after sixteen)
+PALETTE = [(230, 25, 75), (60, 180, 75), (0, 130, 200), (255, 225, 25), (245, 130, 48), (145, 30, 180), (70, 240, 240), (240, 50, 230),
+           (210, 245, 60), (250, 190, 212), (0, 128, 128), (220, 190, 255), (170, 110, 40), (128, 0, 0), (170, 255, 195), (0, 0, 128)]
+
+
+def save_class_visualisation(sample, labels, path):
+    """sample [3, h, w] in [0, 1] on the device, labels uint8 [h, w] (255 = no class) or None: the picture with every labelled pixel
+    mixed half and half with its class's colour, composed on the host."""
+    fig = (sample.permute(1, 2, 0).cpu().numpy() * 255.0 + 0.5).astype(np.uint8)
+    if labels is not None:
+        lab = labels.cpu().numpy()
+        tint = np.asarray(PALETTE, np.float32)[lab % len(PALETTE)]
+        own = (lab != 255)[:, :, None]
+        fig = np.where(own, (fig.astype(np.float32) + tint) / 2 + 0.5, fig).astype(np.uint8)
+    Image.fromarray(fig).save(path)
+
+
+def run_classes(args, model, device, inputs, named):
+    """--classes_json: every group of images through frames.count_classes."""
+    names = list(named)
+    done = 0
+    step = max(args.group_images, 1)
+    for g0 in range(0, len(inputs), step):
+        paths = inputs[g0:g0 + step]
+        raw = [np.asarray(Image.open(pth).convert("RGB"), dtype=np.uint8) for pth in paths]
+        t0 = time.perf_counter()
+        res = frames.count_classes(model, raw, {n: [[tuple(b) for b in named[n]]] * len(raw) for n in names})
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / len(paths)
+        samples = frames.frame_prep(device).prepare(raw) if not args.no_viz else [None] * len(raw)
+        for pth, r, sample in zip(paths, res, samples):
+            done += 1
+            print("[%3d/%d] %s:\ttime = %5.2f" % (done, len(inputs), pth.name, dt))
+            out = {}
+            for c, n in enumerate(names):
+                won = float(r.won[c]) if r.won is not None else None
+                out[n] = {"count": float(r.counts[c]), "won": won, "area": int(r.area[c]) if r.area is not None else None}
+                print("  class %s: count = %5.2f  won = %s" % (n, r.counts[c], "%5.2f" % won if won is not None else "n/a"))
+            with open(args.output_path / ("classes_%s.json" % pth.stem), "w") as f:
+                json.dump({"classes": out}, f)
+            if not args.no_viz:
+                save_class_visualisation(sample[0], r.labels, args.output_path / ("viz_%s.jpg" % pth.stem))
+
+
 def main():
     p = ArgumentParser()
     p.add_argument("--input_path", type=Path, required=True)
@@ -76,6 +124,7 @@ def main():
     p.add_argument("--group_images", type=int, default=8, help="images prepared and counted per call")
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     p.add_argument("--no_viz", action="store_true", help="counts only, no viz_*.jpg")
+    p.add_argument("--classes_json", type=Path, default=None, help="JSON {class name: [[x1, y1, x2, y2], ...]}: several classes per image")
     add_points_args(p)
     add_regions_args(p)
     args = p.parse_args()
@@ -98,6 +147,9 @@ def main():
         inputs = sorted(chain(args.input_path.glob("*.jpg"), args.input_path.glob("*.png")))
     else:
         inputs = [args.input_path]
+    if args.classes_json:
+        run_classes(args, model, device, inputs, json.load(open(args.classes_json)))
+        return
     done = 0
     step = max(args.group_images, 1)
     for g0 in range(0, len(inputs), step):
