@@ -15,6 +15,9 @@ def __getattr__(name):
     if name in ("ClassFolder", "classes_host"):
         from . import classes
         return getattr(classes, name)
+    if name in ("TileStitcher", "tiles_host", "tile_starts"):
+        from . import tiles
+        return getattr(tiles, name)
     if name in ("match_host", "PointMatcher", "localization_metrics", "LocalizationTotals"):
         from . import match
         return getattr(match, name)

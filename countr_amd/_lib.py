@@ -206,3 +206,41 @@ def classes_check(rc, what=""):
 def classes_exported_symbols():
     """Names declared in include/countr_hip_classes.h, which are the names the classes library exports."""
     return sorted(CLASSES_PROTOS)
+
+
+# ---- the tiles library: a frame counted on a 2-D grid of 384 x 384 tiles (count_frames(zoom=k)).  include/countr_hip_tiles.h is its one
+# statement, in the same dialect; nothing of it enters the bindings above or this module's COUNTR_* globals.
+TILES_LIB_PATH = os.environ.get("COUNTR_LIB_TILES", os.path.join(_HERE, "libcountr_hip_tiles.so"))
+TILES_HEADER = os.path.join(_HERE, "..", "include", "countr_hip_tiles.h")
+TILES_CONSTS, TILES_STRUCTS, TILES_PROTOS = parse_header(open(TILES_HEADER).read())
+_tiles = None
+
+
+def tiles_lib():
+    """Load (once) and return the ctypes handle of libcountr_hip_tiles.so, bound from its header; raises CountrError if it is not built
+    or was built from another version of the header."""
+    global _tiles
+    if _tiles is None:
+        if not os.path.exists(TILES_LIB_PATH):
+            raise CountrError(
+                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
+                "the HIP path has no CPU fallback" % os.path.basename(TILES_LIB_PATH))
+        L = C.CDLL(TILES_LIB_PATH)
+        for name, (restype, argtypes) in TILES_PROTOS.items():
+            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
+            fn.restype, fn.argtypes = restype, argtypes
+        if L.countr_tiles_version() != TILES_CONSTS["COUNTR_TILES_ABI_VERSION"]:
+            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
+                              % (os.path.basename(TILES_LIB_PATH), L.countr_tiles_version(), TILES_CONSTS["COUNTR_TILES_ABI_VERSION"]))
+        _tiles = L
+    return _tiles
+
+
+def tiles_check(rc, what=""):
+    if rc != 0:
+        raise CountrError("%s failed (rc=%d): %s" % (what or "countr_tiles call", rc, (tiles_lib().countr_tiles_last_error() or b"").decode()))
+
+
+def tiles_exported_symbols():
+    """Names declared in include/countr_hip_tiles.h, which are the names the tiles library exports."""
+    return sorted(TILES_PROTOS)

@@ -1,5 +1,5 @@
-"""Build libcountr_hip.so (all HIP kernels + the C ABI) and the extension libraries libcountr_hip_ext.so and libcountr_hip_classes.so
-in-tree for gfx950.
+"""Build libcountr_hip.so (all HIP kernels + the C ABI) and the extension libraries libcountr_hip_ext.so, libcountr_hip_classes.so and
+libcountr_hip_tiles.so in-tree for gfx950.
 
 hipcc cross-compiles without a GPU, so this runs in the build container and on the GPU box.
 The .so is git-ignored but travels with the repo snapshot to the GPU box.
@@ -44,6 +44,10 @@ EXT_HEADER = os.path.join(HERE, "..", "include", "countr_hip_ext.h")
 CSRC_CLASSES = os.path.join(HERE, "csrc_classes")
 LIB_CLASSES = os.path.join(HERE, "libcountr_hip_classes.so")
 CLASSES_HEADER = os.path.join(HERE, "..", "include", "countr_hip_classes.h")
+# the tiles library (include/countr_hip_tiles.h), built the same way, from csrc_tiles/
+CSRC_TILES = os.path.join(HERE, "csrc_tiles")
+LIB_TILES = os.path.join(HERE, "libcountr_hip_tiles.so")
+TILES_HEADER = os.path.join(HERE, "..", "include", "countr_hip_tiles.h")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"]
 
 
@@ -55,13 +59,18 @@ def classes_sources():
     return sorted(glob.glob(os.path.join(CSRC_CLASSES, "*.hip")))
 
 
+def tiles_sources():
+    return sorted(glob.glob(os.path.join(CSRC_TILES, "*.hip")))
+
+
 # the libraries built once, without a 16-bit twin: tag -> (library, sources, its header)
-SINGLE = {"ext": (LIB_EXT, ext_sources, EXT_HEADER), "classes": (LIB_CLASSES, classes_sources, CLASSES_HEADER)}
+SINGLE = {"ext": (LIB_EXT, ext_sources, EXT_HEADER), "classes": (LIB_CLASSES, classes_sources, CLASSES_HEADER),
+          "tiles": (LIB_TILES, tiles_sources, TILES_HEADER)}
 
 
 def build(force=False, verbose=True):
     """Compile every csrc/*.hip for gfx950 and link libcountr_hip.so + libcountr_hip_f16.so, and every csrc_ext/*.hip into
-    libcountr_hip_ext.so, every csrc_classes/*.hip into libcountr_hip_classes.so.  An object is reused only if the record
+    libcountr_hip_ext.so, every csrc_classes/*.hip into libcountr_hip_classes.so, every csrc_tiles/*.hip into libcountr_hip_tiles.so.  An object is reused only if the record
     written when it was compiled (build/<variant>/<src>.o.sha256: content hash of the source, of every shared header and of the flags)
     still matches -- content, not mtime, so a snapshot copy or a checkout cannot make a stale object look fresh.  COUNTR_BUILD_FORCE=1
     (or force=True / --force) recompiles everything.  Prints how many objects were compiled."""
@@ -114,9 +123,9 @@ def build(force=False, verbose=True):
             subprocess.check_call(cmd)
             open(lrec, "w").write(lwant + "\n")
     if verbose:
-        print("build_mode: %s -- %d of %d objects compiled (2 libraries x %d sources + %d of the extension library + %d of the classes library), %d reused after a "
+        print("build_mode: %s -- %d of %d objects compiled (2 libraries x %d sources + %d of the extension library + %d of the classes library + %d of the tiles library), %d reused after a "
               "content-hash check (source + headers + flags)"
-              % ("full" if reused == 0 else "incremental", len(procs), total, len(sources()), len(ext_sources()), len(classes_sources()), reused), flush=True)
+              % ("full" if reused == 0 else "incremental", len(procs), total, len(sources()), len(ext_sources()), len(classes_sources()), len(tiles_sources()), reused), flush=True)
     return LIB
 
 

@@ -4,29 +4,30 @@ The preparation the reference leaves to PIL / torchvision on the host -- resize 
 (demo_zero.py:23-38, demo.py:42-49), ToTensor, the 64 x 64 exemplar crops (demo.py:60-68) and the 3 x 3 crop-and-upscale for tiny
 exemplars (:84-99) -- runs as HIP kernels on the stream the forward runs on (csrc/frames.hip: countr_frame_resize_u8,
 countr_crop_resize_f32).  The prepared image equals PIL's BILINEAR resize + ToTensor bit for bit, and everything behind it is
-inference.count_images / density_maps unchanged, so the results equal the host-prepared path's.  There is no host fallback."""
+inference.count_images / density_maps unchanged, so the results equal the host-prepared path's.  There is no host fallback.
+count_frames(zoom=k) resizes to height 384 k instead and counts on a 2-D grid of tiles (countr_amd/tiles.py, csrc_tiles/tiles.hip)."""
 import collections
 import ctypes as C
 
 import numpy as np
 import torch
 
-from . import _lib, classes as classes_, inference, peaks, regions as regions_
+from . import _lib, classes as classes_, inference, peaks, regions as regions_, tiles as tiles_
 
 NEW_H = 384
 BOX = 64                    # exemplar crops are 64 x 64 (demo.py:67)
 MAX_BATCHED = _lib.FRAMES_MAX              # frames / rectangles of one call
 
 
-def new_width(W, H):
-    """Width of the resized frame (demo_zero.py:28-31, demo.py:42-44)."""
-    return 16 * int((W / H * NEW_H) / 16)
+def new_width(W, H, new_h=NEW_H):
+    """Width of the frame resized to height new_h (demo_zero.py:28-31, demo.py:42-44 with 384 = new_h)."""
+    return 16 * int((W / H * new_h) / 16)
 
 
-def scale_boxes(boxes_xyxy, W, H):
-    """Boxes [(x1, y1, x2, y2), ...] in pixels of the ORIGINAL W x H frame -> rects [[y1, x1, y2, x2], ...] of the resized frame, with the
-    reference's scale factors and int() truncation (demo.py:45-46, 60-65).  The corners are inclusive (:66)."""
-    sw, sh = float(new_width(W, H)) / W, float(NEW_H) / H
+def scale_boxes(boxes_xyxy, W, H, new_h=NEW_H):
+    """Boxes [(x1, y1, x2, y2), ...] in pixels of the ORIGINAL W x H frame -> rects [[y1, x1, y2, x2], ...] of the frame resized to height
+    new_h, with the reference's scale factors and int() truncation (demo.py:45-46, 60-65).  The corners are inclusive (:66)."""
+    sw, sh = float(new_width(W, H, new_h)) / W, float(new_h) / H
     return [[int(y1 * sh), int(x1 * sw), int(y2 * sh), int(x2 * sw)] for x1, y1, x2, y2 in boxes_xyxy]
 
 
@@ -77,10 +78,10 @@ def crop_resize(image, rects, oh, ow):
     return out
 
 
-def exemplars(image, boxes_xyxy, W, H):
-    """Exemplar tensors of one prepared frame: image [1, 3, 384, new_W] (FramePrep.prepare), boxes in pixels of the original W x H frame
+def exemplars(image, boxes_xyxy, W, H, new_h=NEW_H):
+    """Exemplar tensors of one prepared frame: image [1, 3, new_h, new_W] (FramePrep.prepare), boxes in pixels of the original W x H frame
     -> (boxes [1, S, 3, 64, 64] on the device, rects [[y1, x1, y2, x2], ...]) as demo.py:60-71 builds them."""
-    rects = scale_boxes(boxes_xyxy, W, H)
+    rects = scale_boxes(boxes_xyxy, W, H, new_h)
     return crop_resize(image, rects, BOX, BOX).unsqueeze(0), rects
 
 
@@ -126,7 +127,7 @@ class FramePrep:
         self.L = _lib.lib()
         self._tables = {}      # (in, out) -> (bounds, weights) on the device
         self._slots = {}       # (H, W) -> [_Slot, ...]
-        self._tmp = {}         # (H, W) -> uint8 [n, H, out_w, 3]
+        self._tmp = {}         # (H, W, out height) -> uint8 [n, H, out_w, 3]
         self._last = None      # (stream, event) of the previous prepare: a call on another stream waits for it before it reuses the buffers
 
     def tables(self, in_size, out_size):
@@ -155,9 +156,10 @@ class FramePrep:
         slot.copied.record(torch.cuda.current_stream(self.device))
         return slot.dev
 
-    def prepare(self, frames):
-        """frames: uint8 [H, W, 3] each (np.ndarray, CPU tensor or device tensor) -> [[1, 3, 384, new_W] fp32 device tensors], each equal
-        to ToTensor(PIL resize((new_W, 384), BILINEAR)) bit for bit.  Frames of one shape share launches (up to 16 per launch pair)."""
+    def prepare(self, frames, new_h=NEW_H):
+        """frames: uint8 [H, W, 3] each (np.ndarray, CPU tensor or device tensor) -> [[1, 3, new_h, new_W] fp32 device tensors], each equal
+        to ToTensor(PIL resize((new_W, new_h), BILINEAR)) bit for bit.  Frames of one shape share launches (up to 16 per launch pair)."""
+        new_h = int(new_h)
         out = [None] * len(frames)
         by_shape = {}
         for i, f in enumerate(frames):
@@ -170,26 +172,26 @@ class FramePrep:
             if self._last is not None and self._last[0] != cur:
                 cur.wait_event(self._last[1])
             for (H, W), idxs in by_shape.items():
-                ow = new_width(W, H)
+                ow = new_width(W, H, new_h)
                 if ow < 16:
                     raise ValueError("FramePrep.prepare: a %d x %d frame resizes to width %d" % (W, H, ow))
                 hb, hw = self.tables(W, ow)
-                vb, vw = self.tables(H, NEW_H)
+                vb, vw = self.tables(H, new_h)
                 slots = self._slots.setdefault((H, W), [])
                 while len(slots) < len(idxs):
                     slots.append(_Slot(H, W, self.device))
                 nb = min(len(idxs), MAX_BATCHED)
-                tmp = self._tmp.get((H, W))
+                tmp = self._tmp.get((H, W, new_h))
                 if tmp is None or tmp.shape[0] < nb:
-                    tmp = self._tmp[(H, W)] = torch.empty(nb, H, ow, 3, dtype=torch.uint8, device=self.device)
+                    tmp = self._tmp[(H, W, new_h)] = torch.empty(nb, H, ow, 3, dtype=torch.uint8, device=self.device)
                 for g0 in range(0, len(idxs), MAX_BATCHED):
                     sel = idxs[g0:g0 + MAX_BATCHED]
                     srcs = [self._frame_on_device(frames[i], slots[g0 + k]) for k, i in enumerate(sel)]
                     for i in sel:
-                        out[i] = torch.empty(1, 3, NEW_H, ow, device=self.device, dtype=torch.float32)
+                        out[i] = torch.empty(1, 3, new_h, ow, device=self.device, dtype=torch.float32)
                     fp = (C.c_void_p * len(sel))(*[s.data_ptr() for s in srcs])
                     op = (C.c_void_p * len(sel))(*[out[i].data_ptr() for i in sel])
-                    _lib.check(self.L.countr_frame_resize_u8(fp, op, len(sel), H, W, NEW_H, ow, hb.data_ptr(), hw.data_ptr(), vb.data_ptr(),
+                    _lib.check(self.L.countr_frame_resize_u8(fp, op, len(sel), H, W, new_h, ow, hb.data_ptr(), hw.data_ptr(), vb.data_ptr(),
                                                              vw.data_ptr(), tmp.data_ptr(), st), "countr_frame_resize_u8")
             if self._last is None or self._last[0] != cur:
                 self._last = (cur, torch.cuda.Event())
@@ -211,17 +213,17 @@ def frame_prep(device):
     return p
 
 
-def prepare_items(device, frames, boxes=None, prep=None):
+def prepare_items(device, frames, boxes=None, prep=None, new_h=NEW_H):
     """Raw frames (+ per-frame lists of (x1, y1, x2, y2) boxes in original pixels, or None) -> the items inference.count_images takes:
-    [(image [1, 3, 384, new_W], exemplars [1, S, 3, 64, 64] or an empty [1, 0] tensor, rects or None), ...], all made on the device."""
+    [(image [1, 3, new_h, new_W], exemplars [1, S, 3, 64, 64] or an empty [1, 0] tensor, rects or None), ...], all made on the device."""
     prep = prep or frame_prep(device)
-    images = prep.prepare(frames)
+    images = prep.prepare(frames, new_h)
     items = []
     for i, im in enumerate(images):
         bx = boxes[i] if boxes is not None else None
         if bx is not None and len(bx) > 0:
             H, W = int(frames[i].shape[0]), int(frames[i].shape[1])
-            ex, rects = exemplars(im, bx, W, H)
+            ex, rects = exemplars(im, bx, W, H, new_h)
             items.append((im, ex, rects))
         else:
             items.append((im, torch.zeros(1, 0, device=im.device), None))
@@ -248,12 +250,53 @@ def count_items(model, items, normalization=True, max_s_cnt=1, max_batch=32):
     return res
 
 
+def frame_zooms(frames, boxes, zoom, zoom_max=3, max_s_cnt=1):
+    """The zoom of every frame: `zoom` itself, or under zoom="auto" tiles.auto_zoom of the frame's boxes."""
+    if zoom != "auto":
+        return [int(zoom)] * len(frames)
+    return [tiles_.auto_zoom(boxes[i] if boxes is not None else None, int(f.shape[1]), int(f.shape[0]), max_s_cnt, zoom_max)
+            for i, f in enumerate(frames)]
+
+
 @torch.no_grad()
-def count_frames(model, frames, boxes=None, normalization=True, max_s_cnt=1, max_batch=32):
+def count_frames_zoomed(model, frames, boxes, ks, normalization=True, max_s_cnt=1, max_batch=32, band_stride=128, crops=False):
+    """count_frames with a zoom per frame (ks): [(count, density map), ...], or with crops=True [(count, density map, the nine maps of the
+    3 x 3 path or None), ...].  The frames at zoom 1 run as ONE call of the existing path over just those frames.  A frame at k > 1 is
+    resized from its own pixels to height 384 k (FramePrep), its exemplars are cut from that image, and its tiles run as forwards of
+    their own (tiles.count_zoomed); it never takes the 3 x 3 split."""
+    device = next(model.parameters()).device
+    res = [None] * len(frames)
+    ones = [i for i, k in enumerate(ks) if k == 1]
+    if ones:
+        items = prepare_items(device, [frames[i] for i in ones], [boxes[i] for i in ones] if boxes is not None else None)
+        got = (count_items_crops if crops else count_items)(model, items, normalization, max_s_cnt, max_batch)
+        for i, r in zip(ones, got):
+            res[i] = r
+    for k in sorted(set(ks) - {1}):
+        sel = [i for i, kk in enumerate(ks) if kk == k]
+        items = prepare_items(device, [frames[i] for i in sel], [boxes[i] for i in sel] if boxes is not None else None, new_h=NEW_H * k)
+        for i, (im, ex, rects) in zip(sel, items):
+            r = tiles_.count_zoomed(model, im, ex, rects, normalization, max_batch, band_stride)
+            res[i] = r + (None,) if crops else r
+    return res
+
+
+@torch.no_grad()
+def count_frames(model, frames, boxes=None, normalization=True, max_s_cnt=1, max_batch=32, *, zoom=1, zoom_max=3, band_stride=128):
     """Raw frames in, [(count, density map [384, new_W]), ...] out.  frames: uint8 [H, W, 3] each, on the host or on the model's device;
     boxes: None (zero-shot) or one list of (x1, y1, x2, y2) exemplar boxes per frame, in pixels of the original frame (an empty list =
     zero-shot for that frame).  Preparation runs on the device (FramePrep, exemplars); frames are then grouped by shot count and
-    counted as inference.count_images counts them -- one forward per <= max_batch windows, the encoder pipelined across groups."""
+    counted as inference.count_images counts them -- one forward per <= max_batch windows, the encoder pipelined across groups.
+    zoom=k (2..4) counts from the frame's own pixels: the frame is resized to height 384 k instead of 384 and covered by a 2-D grid of
+    384 x 384 tiles -- columns at the reference's stride 128, rows at band_stride (128, 192, 256 or 384) -- each tile one forward row,
+    the tile maps stitched in both directions by the reference's sequential rule (countr_amd/tiles.py states it; csrc_tiles/tiles.hip
+    computes it).  Such a frame returns (count, density map [384 k, Wk]) and never takes the 3 x 3 split.  zoom="auto" gives every
+    frame the smallest k in 1..zoom_max at which fewer than max_s_cnt of its exemplars are under 10 px (zoom_max if none, 1 without
+    boxes); its frames at 1 are counted as count_frames counts just them.  zoom=1 is the path above, untouched."""
+    tiles_.check_zoom(zoom, zoom_max, band_stride)
+    if zoom != 1:
+        ks = frame_zooms(frames, boxes, zoom, zoom_max, max_s_cnt)
+        return count_frames_zoomed(model, frames, boxes, ks, normalization, max_s_cnt, max_batch, band_stride)
     device = next(model.parameters()).device
     return count_items(model, prepare_items(device, frames, boxes), normalization, max_s_cnt, max_batch)
 
@@ -339,11 +382,11 @@ def count_classes(model, frames, classes, *, normalization=True, max_s_cnt=1, ma
     return [ClassCounts(tuple(names), tuple(counts[f]), tuple(maps[f]), *folded.get(f, (None, None, None, None))) for f in range(F_)]
 
 
-def frame_points(cy, cx, W, H, new_w):
-    """Centroids (cy, cx) of the resized [384, new_w] map -> (x, y) in pixel-centre coordinates of the ORIGINAL W x H frame, in float64:
-    x = (cx + 0.5) W / new_w - 0.5, y = (cy + 0.5) H / 384 - 0.5."""
+def frame_points(cy, cx, W, H, new_w, new_h=NEW_H):
+    """Centroids (cy, cx) of the resized [new_h, new_w] map -> (x, y) in pixel-centre coordinates of the ORIGINAL W x H frame, in float64:
+    x = (cx + 0.5) W / new_w - 0.5, y = (cy + 0.5) H / new_h - 0.5."""
     cy, cx = np.asarray(cy, np.float64), np.asarray(cx, np.float64)
-    return (cx + 0.5) * W / new_w - 0.5, (cy + 0.5) * H / NEW_H - 0.5
+    return (cx + 0.5) * W / new_w - 0.5, (cy + 0.5) * H / new_h - 0.5
 
 
 def crop_points(cy, cx, k, h, w):
@@ -362,11 +405,15 @@ def _keep_count(P, count, keep):
     return min(P, max(0, int(np.floor(count + 0.5))))
 
 
-def locate_maps(results, sizes, crops=None, *, radius=4, threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all"):
+def locate_maps(results, sizes, crops=None, *, radius=4, threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all", new_h=NEW_H):
     """The points of counted frames: results [(count, density map [384, new_W] on the device), ...], sizes [(W, H), ...] of the original
     frames, crops per frame None or the nine maps of the 3 x 3 path -> [(points float32 [P, 2] as (x, y), score [P], total), ...].
-    Every map of the call (the nine crop maps of a split frame included) goes through ONE PeakFinder.find."""
+    Every map of the call (the nine crop maps of a split frame included) goes through ONE PeakFinder.find.  new_h: the height the
+    frames were resized to, one number or one per frame (384 k for a frame counted at zoom k)."""
     crops = crops or [None] * len(results)
+    heights = [int(new_h)] * len(results) if np.ndim(new_h) == 0 else [int(v) for v in new_h]
+    if len(heights) != len(results):
+        raise ValueError("locate_maps: new_h is one height, or one per frame")
     maps, first = [], []
     for (_c, dm), cr in zip(results, crops):
         first.append(len(maps))
@@ -376,7 +423,7 @@ def locate_maps(results, sizes, crops=None, *, radius=4, threshold=0.0, rel_thre
     maps = [m if (m.dtype == torch.float32 and m.is_contiguous()) else m.float().contiguous() for m in maps]
     found = peaks.peak_finder(maps[0].device).find(maps, radius, threshold, rel_threshold, max_points)
     out = []
-    for (count, dm), (W, H), cr, f0 in zip(results, sizes, crops, first):
+    for (count, dm), (W, H), cr, f0, nh in zip(results, sizes, crops, first, heights):
         h, w = dm.shape
         if cr is None:
             pk = found[f0]
@@ -391,7 +438,7 @@ def locate_maps(results, sizes, crops=None, *, radius=4, threshold=0.0, rel_thre
             order = np.lexsort((idx, crop, -score))                    # (score descending, crop, idx)
             cy, cx, score = cy[order], cx[order], score[order]
             total = sum(pk.total for pk in nine)
-        x, y = frame_points(cy, cx, W, H, w)
+        x, y = frame_points(cy, cx, W, H, w, nh)
         P = _keep_count(len(score), count, keep)
         out.append((np.stack([x, y], 1).astype(np.float32)[:P], np.asarray(score, np.float32)[:P], total))
     return out
@@ -428,7 +475,7 @@ def locate_items(model, items, sizes, *, radius=4, threshold=0.0, rel_threshold=
 
 @torch.no_grad()
 def locate_frames(model, frames, boxes=None, *, radius=4, threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all", normalization=True,
-                  max_s_cnt=1, max_batch=32, regions=None):
+                  max_s_cnt=1, max_batch=32, regions=None, zoom=1, zoom_max=3, band_stride=128):
     """count_frames that also says WHERE: [(count, density map, points float32 [P, 2] as (x, y), score [P]), ...].  count and density map
     are count_frames' bit for bit.  points are the sub-pixel centroids of the map's peaks (countr_amd/peaks.py states the rule) in
     pixel-centre coordinates of the original frame (frame_points), ordered by score; keep="count" keeps the first
@@ -436,10 +483,23 @@ def locate_frames(model, frames, boxes=None, *, radius=4, threshold=0.0, rel_thr
     crop_points and re-ordered by (score descending, crop, raster index); its returned map stays the last crop's.  The defaults
     radius=4 and rel_threshold=0.1 are unmeasured: no localisation accuracy figure exists for them.
     With regions (count_regions' argument) each tuple gains region_counts float32 [R] and point_region int32 [P]: the first region that
-    contains each point by the regions' own rule (countr_amd/regions.py), -1 = none."""
+    contains each point by the regions' own rule (countr_amd/regions.py), -1 = none.
+    zoom, zoom_max, band_stride: count_frames' arguments.  The peaks of a zoomed frame's [384 k, Wk] map go through the same PeakFinder
+    and map to the original frame through frame_points(..., new_h=384 k).  radius stays in pixels of the map that is searched: an
+    object is k times larger there, so a radius chosen at zoom 1 is k times tighter at zoom k.  regions together with a zoom other than
+    1 raises ValueError."""
+    tiles_.check_zoom(zoom, zoom_max, band_stride)
+    sizes = [(int(f.shape[1]), int(f.shape[0])) for f in frames]
+    if zoom != 1:
+        if regions is not None:
+            raise ValueError("locate_frames: regions are counted at zoom=1 only")
+        ks = frame_zooms(frames, boxes, zoom, zoom_max, max_s_cnt)
+        res = count_frames_zoomed(model, frames, boxes, ks, normalization, max_s_cnt, max_batch, band_stride, crops=True)
+        pts = locate_maps([(c, dm) for c, dm, _cr in res], sizes, [cr for _c, _dm, cr in res], radius=radius, threshold=threshold,
+                          rel_threshold=rel_threshold, max_points=max_points, keep=keep, new_h=[NEW_H * k for k in ks])
+        return [(c, dm, p, s) for (c, dm, _cr), (p, s, _t) in zip(res, pts)]
     device = next(model.parameters()).device
     items = prepare_items(device, frames, boxes)
-    sizes = [(int(f.shape[1]), int(f.shape[0])) for f in frames]
     res = locate_items(model, items, sizes, radius=radius, threshold=threshold, rel_threshold=rel_threshold, max_points=max_points, keep=keep,
                        normalization=normalization, max_s_cnt=max_s_cnt, max_batch=max_batch, crops=regions is not None)
     if regions is None:
@@ -449,11 +509,11 @@ def locate_frames(model, frames, boxes=None, *, radius=4, threshold=0.0, rel_thr
     return [r[:4] + (counts, regions_.point_regions(r[2], rs)) for r, rs, (counts, _area) in zip(res, per, sums)]
 
 
-def map_placement(W, H, new_w):
-    """The placement (ax, bx, ay, by) of a frame's [384, new_w] map in pixel-centre coordinates of the original W x H frame, in float64:
+def map_placement(W, H, new_w, new_h=NEW_H):
+    """The placement (ax, bx, ay, by) of a frame's [new_h, new_w] map in pixel-centre coordinates of the original W x H frame, in float64:
     frame_points as one multiply and one add per axis -- x = (W / new_w) cx + frame_points(0, 0)'s x."""
-    x0, y0 = frame_points(0.0, 0.0, W, H, new_w)
-    return (np.float64(W) / new_w, np.float64(x0), np.float64(H) / NEW_H, np.float64(y0))
+    x0, y0 = frame_points(0.0, 0.0, W, H, new_w, new_h)
+    return (np.float64(W) / new_w, np.float64(x0), np.float64(H) / new_h, np.float64(y0))
 
 
 def crop_placement(k, h, w, placement):

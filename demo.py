@@ -18,7 +18,10 @@ its nine crop maps.  It works together with --points.  `--classes_json FILE` cou
 (countr_amd.frames.count_classes): {"name": [[x1, y1, x2, y2], ...], ...} exemplar boxes per class in pixels of the input image, applied
 to every input image -> one printed line per class (count and won count), classes_<stem>.json = {"classes": {name: {"count", "won",
 "area"}}} and viz_<name>.jpg tinted by the dominant class (won and area are null, and nothing is tinted, for an image on which a class
-took the 3 x 3 path).  It replaces --boxes, --points and --regions_json for that run."""
+took the 3 x 3 path).  It replaces --boxes, --points and --regions_json for that run.  `--zoom {2,3,4,auto}` counts from the image's own
+pixels, as demo_zero.py does: the image is resized on the device to height 384 k, the exemplars are cut from that image, and a 2-D grid
+of tiles covers it (--band_stride, --zoom_max); "auto" takes the smallest k at which the exemplars are no longer under 10 pixels.
+viz_<name>.jpg is then drawn from the zoomed image and map.  --regions_json and --classes_json are for --zoom 1."""
 import json
 import time
 from argparse import ArgumentParser
@@ -31,7 +34,8 @@ from PIL import Image
 
 import models_mae_cross
 from countr_amd import frames
-from demo_zero import add_points_args, add_regions_args, draw_points, draw_regions, load_regions, report_regions, write_points
+from demo_zero import (add_points_args, add_regions_args, add_zoom_args, count_zoomed, draw_points, draw_regions, load_regions, parse_zoom,
+                       points_on, report_regions, write_points)
 
 
 def parse_boxes(text):
@@ -127,7 +131,11 @@ def main():
     p.add_argument("--classes_json", type=Path, default=None, help="JSON {class name: [[x1, y1, x2, y2], ...]}: several classes per image")
     add_points_args(p)
     add_regions_args(p)
+    add_zoom_args(p)
     args = p.parse_args()
+    zoom = parse_zoom(args)
+    if zoom != 1 and (args.regions_json is not None or args.classes_json is not None):
+        p.error("--regions_json and --classes_json are for --zoom 1")
     args.output_path.mkdir(exist_ok=True, parents=True)
     device = torch.device("cuda")
     region_names, polygons = load_regions(args.regions_json)
@@ -157,6 +165,23 @@ def main():
         raw = [np.asarray(Image.open(pth).convert("RGB"), dtype=np.uint8) for pth in paths]      # decoding stays on the host
         boxes = [[tuple(b) for b in named[pth.name]] if pth.name in named else common for pth in paths]
         t0 = time.perf_counter()
+        if zoom != 1:
+            got = count_zoomed(model, raw, boxes, zoom, args, True)
+            dt = (time.perf_counter() - t0) / len(paths)
+            for pth, r, bx, (pred_cnt, dm, pts, score, total, sample, k) in zip(paths, raw, boxes, got):
+                done += 1
+                if pts is not None:
+                    write_points(args.output_path / ("points_%s.json" % pth.stem), pred_cnt, total, pts, score)
+                if not args.no_viz:
+                    old_w, old_h = r.shape[1], r.shape[0]
+                    w, h = (sample.shape[2], sample.shape[1]) if k > 1 else (old_w, old_h)      # a zoomed picture stays at its size
+                    save_visualisation(sample, dm.float(), frames.scale_boxes(bx, old_w, old_h, frames.NEW_H * k), args.output_path / ("viz_%s.jpg" % pth.stem),
+                                       points_on(pts, old_w, old_h, w, h) if pts is not None else None, (w, h))
+                if len(inputs) > 1:
+                    print("[%3d/%d] %s:\tcount = %5.2f  -  time = %5.2f" % (done, len(inputs), pth.name, pred_cnt, dt))
+                else:
+                    print("Count:", pred_cnt, "- Time:", dt)
+            continue
         items = frames.prepare_items(device, raw, boxes)
         sizes = [(r.shape[1], r.shape[0]) for r in raw]
         summed = [None] * len(paths)

@@ -16,7 +16,11 @@ density map, found on the device): viz_<name>.jpg gets a small dot per point and
 region: FILE is {"name": [[x, y], ...], ...}, polygons in pixels of the original image (pixel-centre coordinates: pixel i has centre
 i); the density map is summed over each polygon on the device (countr_amd.frames.region_maps), one line per region is printed,
 regions_<stem>.json = {"count", "regions": {name: {"count", "area"}}} is written (area = map pixels inside) and viz_<name>.jpg gets the
-outlines.  It works together with --points.  demo.py is the few-shot counterpart (exemplar boxes)."""
+outlines.  It works together with --points.  `--zoom {2,3,4,auto}` counts from the image's own pixels (countr_amd.frames.count_frames
+with zoom=): the decoded image is resized on the device to height 384 k and covered by a 2-D grid of tiles (--band_stride: the row
+stride of the grid, --zoom_max: the largest k "auto" takes; without exemplar boxes "auto" is 1).  Counts, --points and their JSON
+work as before; viz_<name>.jpg is drawn from the zoomed image and map, at the zoomed size.  --regions_json is for --zoom 1.  demo.py is
+the few-shot counterpart (exemplar boxes)."""
 import json
 import time
 from argparse import ArgumentParser
@@ -64,6 +68,38 @@ def add_points_args(p):
     p.add_argument("--points_radius", type=int, default=4, help="half width of the peak window, 1..8 (the default is unmeasured)")
     p.add_argument("--points_rel_threshold", type=float, default=0.1, help="a peak is at least this share of the map's maximum (the default is unmeasured)")
     p.add_argument("--points_keep", default="all", choices=["all", "count"], help="count: keep the round(count) highest peaks")
+
+
+def add_zoom_args(p):
+    p.add_argument("--zoom", default="1", choices=["1", "2", "3", "4", "auto"],
+                   help="count at k times the model's height, on a 2-D grid of tiles over the image's own pixels")
+    p.add_argument("--zoom_max", type=int, default=3, choices=[1, 2, 3, 4], help="the largest zoom --zoom auto takes")
+    p.add_argument("--band_stride", type=int, default=128, choices=[128, 192, 256, 384], help="row stride of the tile grid")
+
+
+def parse_zoom(args):
+    return "auto" if args.zoom == "auto" else int(args.zoom)
+
+
+def count_zoomed(model, raw, boxes, zoom, args, normalization):
+    """frames.count_frames(zoom=) for the demos -> per image (count, map, points or None, score, total peaks, zoomed image [3, Hk, Wk] or
+    None with --no_viz, k).  The points are in pixel-centre coordinates of the input image."""
+    ks = frames.frame_zooms(raw, boxes, zoom, args.zoom_max)
+    res = frames.count_frames_zoomed(model, raw, boxes, ks, normalization, 1, 32, args.band_stride, crops=True)
+    located = [(None, None, None)] * len(raw)
+    if args.points:
+        located = frames.locate_maps([(c, dm) for c, dm, _cr in res], [(r.shape[1], r.shape[0]) for r in raw], [cr for _c, _dm, cr in res],
+                                     radius=args.points_radius, rel_threshold=args.points_rel_threshold, keep=args.points_keep,
+                                     new_h=[frames.NEW_H * k for k in ks])
+    torch.cuda.synchronize()
+    prep = frames.frame_prep(next(model.parameters()).device)
+    samples = [None if args.no_viz else prep.prepare([r], frames.NEW_H * k)[0][0] for r, k in zip(raw, ks)]
+    return [(c, dm, pts, score, total, sample, k) for (c, dm, _cr), (pts, score, total), sample, k in zip(res, located, samples, ks)]
+
+
+def points_on(points, old_w, old_h, w, h):
+    """Points of the input image (old_w x old_h) in pixel-centre coordinates of its picture resized to w x h."""
+    return [((x + 0.5) * w / old_w - 0.5, (y + 0.5) * h / old_h - 0.5) for x, y in points]
 
 
 def add_regions_args(p):
@@ -127,7 +163,11 @@ def main():
                    help="hand the decoded uint8 frames to the device and resize them there (countr_amd.frames) instead of with PIL on the host")
     add_points_args(p)
     add_regions_args(p)
+    add_zoom_args(p)
     args = p.parse_args()
+    zoom = parse_zoom(args)
+    if zoom != 1 and args.regions_json is not None:
+        p.error("--regions_json is for --zoom 1")
     args.output_path.mkdir(exist_ok=True, parents=True)
     device = torch.device("cuda")
     region_names, polygons = load_regions(args.regions_json)
@@ -148,6 +188,25 @@ def main():
     done = 0
     for g0 in range(0, len(inputs), max(args.group_images, 1)):
         paths = inputs[g0:g0 + max(args.group_images, 1)]
+        if zoom != 1:                 # from the image's own pixels: the decoded frames go to the device as they are
+            raw = [np.asarray(Image.open(pth).convert("RGB"), dtype=np.uint8) for pth in paths]
+            t0 = time.perf_counter()
+            got = count_zoomed(model, raw, None, zoom, args, False)
+            dt = (time.perf_counter() - t0) / len(paths)
+            for pth, r, (pred_cnt, dm, pts, score, total, sample, k) in zip(paths, raw, got):
+                done += 1
+                old_w, old_h = r.shape[1], r.shape[0]
+                if pts is not None:
+                    write_points(args.output_path / ("points_%s.json" % pth.stem), pred_cnt, total, pts, score)
+                if not args.no_viz:
+                    w, h = (sample.shape[2], sample.shape[1]) if k > 1 else (old_w, old_h)      # a zoomed picture stays at its size
+                    save_visualisation(sample, dm.float(), pred_cnt, args.output_path / ("viz_%s.jpg" % pth.stem), w, h,
+                                       points=points_on(pts, old_w, old_h, w, h) if pts is not None else None)
+                if len(inputs) > 1:
+                    print("[%3d/%d] %s:\tcount = %5.2f  -  time = %5.2f" % (done, len(inputs), pth.name, pred_cnt, dt))
+                else:
+                    print("Count:", pred_cnt, "- Time:", dt)
+            continue
         if args.device_prep:
             raw = [np.asarray(Image.open(pth).convert("RGB"), dtype=np.uint8) for pth in paths]      # decoding stays on the host
             t0 = time.perf_counter()
