@@ -69,7 +69,14 @@ __global__ __launch_bounds__(256) void patch_mse_kernel(const float* __restrict_
     if (e < F) {
       const float d = pred[(int64_t)row * F + e] - t[k];
       acc += d * d;
-      if (dpred) stf<TD>(dpred + (int64_t)row * F + e, d * gs);
+      if (dpred) {
+        // the gradient IS the fp32 product; a 16-bit dpred is its rounding, whatever the dtype of the call.  Without the barrier the fp16
+        // build folds product and conversion into one v_fma_mixlo_f16 (the exact product rounded once), which differs from the rounded
+        // fp32 gradient by an ulp wherever the fp32 value is a tie between two fp16 numbers (1-5 of 9216 elements)
+        float gv = d * gs;
+        asm volatile("" : "+v"(gv));
+        stf<TD>(dpred + (int64_t)row * F + e, gv);
+      }
     }
   }
   acc = block_sum<4>(acc, sm);

@@ -153,3 +153,55 @@ def test_layernorm_and_cast_fp16(hip16):
     w = torch.empty((rows, D), device="cuda", dtype=H16)
     _lib.check(hip16.countr_cast_permute(P(x), P(w), rows * D, 0, 0, 0, 0, _lib.BF16, st()))
     assert torch.equal(w, x.to(H16))                      # round-to-nearest-even, as torch's cast
+
+
+def test_conversions_at_the_edges_of_fp16(hip16):
+    """The conversions of csrc/common.hpp (pack2bf / f2bf / stf / st4 / st8 one way, bf2f / unpack2h / ldf / ld4 / ld8 the other) at the
+    ends of fp16's range, through countr_cast_permute mode 0 (fp32 -> fp16) and countr_gather_rows (fp32 -> fp16, fp16 -> fp32,
+    fp16 -> fp16 with an add of zeros): signed zeros, +-65504, the last fp32 below the overflow tie (-> 65504) and the tie itself
+    (65520 -> inf), 1e30, subnormals 2^-24 x {1, 2, 3, 1023}, the tie 2^-25 (-> 0), just above it (-> 2^-24), the smallest normal, NaN and
+    +-inf -- in the low AND the high half of the packed pairs.  16-bit results: the bits of torch's cast (NaN: is NaN); fp32 results:
+    .float() exactly."""
+    inf, nan = float("inf"), float("nan")
+    base = [0.0, -0.0, 65504.0, -65504.0, 65519.996, 65520.0, 1e30, 2.0 ** -24, 2 * 2.0 ** -24, 3 * 2.0 ** -24, 1023 * 2.0 ** -24, 2.0 ** -25,
+            2.0 ** -25 * (1 + 2.0 ** -10), 2.0 ** -14, nan, inf, -inf, -1e30, -(2.0 ** -25), -65520.0]
+    v = torch.tensor(base, dtype=torch.float32)
+    assert v[4].item() < 65520.0 and v[4].to(H16).item() == 65504.0 and v[5].to(H16).item() == inf and v[11].to(H16).item() == 0.0 \
+        and v[12].to(H16).item() == 2.0 ** -24                                  # what torch makes of the ties (round to nearest even)
+    v = torch.cat([v, torch.ones(1), v])                                        # odd shift: every value in both halves of a pair
+    v = torch.cat([v, torch.zeros(-v.numel() % 8)])
+    cols = v.numel()
+    assert cols % 8 == 0
+    x = v.repeat(3, 1).contiguous().cuda()                                      # three rows: gather_rows' row indexing too
+    want16 = x.to(H16)
+
+    def same16(a, b):
+        a, b = a.reshape(-1), b.reshape(-1)
+        n_a, n_b = torch.isnan(a), torch.isnan(b)
+        return bool(torch.equal(n_a, n_b)) and bool(torch.equal(a.view(torch.int16)[~n_a], b.view(torch.int16)[~n_b]))
+
+    def same32(a, b):
+        a, b = a.reshape(-1), b.reshape(-1)
+        n_a, n_b = torch.isnan(a), torch.isnan(b)
+        return bool(torch.equal(n_a, n_b)) and bool(torch.equal(a.view(torch.int32)[~n_a], b.view(torch.int32)[~n_b]))
+
+    c = torch.zeros(3, cols, device="cuda", dtype=H16)
+    _lib.check(hip16.countr_cast_permute(P(x), P(c), 3 * cols, 0, 0, 0, 0, _lib.BF16, st()), "cast")
+    torch.cuda.synchronize()
+    assert same16(c, want16)
+    idx = torch.tensor([2, 0, 1], dtype=torch.int32, device="cuda")
+    zeros = torch.zeros(3, cols, device="cuda")
+    for add in (None, zeros):
+        g16 = torch.zeros(3, cols, device="cuda", dtype=H16)
+        _lib.check(hip16.countr_gather_rows(P(x), P(idx), P(g16), None, P(add), 0, 3, cols, 0, 1, st()), "gather f32 -> f16")
+        back = torch.zeros(3, cols, device="cuda")
+        _lib.check(hip16.countr_gather_rows(P(want16), P(idx), P(back), None, P(add), 0, 3, cols, 1, 0, st()), "gather f16 -> f32")
+        h2h = torch.zeros(3, cols, device="cuda", dtype=H16)
+        _lib.check(hip16.countr_gather_rows(P(want16), P(idx), P(h2h), None, P(add), 0, 3, cols, 1, 1, st()), "gather f16 -> f16")
+        torch.cuda.synchronize()
+        if add is None:
+            assert same16(g16, want16) and same16(h2h, want16)
+            assert same32(back, want16.float())
+        else:       # x + 0.0 in fp32 turns -0 into +0 before the rounding: compare with the same sum made by torch
+            assert same16(g16, (x + zeros).to(H16)) and same16(h2h, (want16.float() + zeros).to(H16))
+            assert same32(back, want16.float() + zeros)

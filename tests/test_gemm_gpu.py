@@ -8,9 +8,11 @@ import ctypes as C
 import pytest
 import torch
 
+import halfprec as HP
 from countr_amd import _lib
 
 pytestmark = pytest.mark.gpu
+F16 = HP.FP16
 
 
 def _stream():
@@ -115,16 +117,26 @@ def test_gelu_backward_epilogue_on_the_lean_kernel(hip, shape, monkeypatch):
     """The fc2 input gradient with the transposed weight shadow ((ROW, ROW), bf16): dx = (dy @ Wt^T) * GELU'(pre) in the epilogue of
     linear.hip's three tile forms (one round of 128 x 128, 192 x 256, 256 x 128) == the generic kernel's fused form bit for bit (same
     accumulation order, same derivative), and within bf16 rounding of fp64 autograd (reference: Mlp.forward, models_crossvit.py:61-67)."""
+    _gelu_backward_epilogue_on_the_lean_kernel(hip, monkeypatch, HP.BF16, shape)
+
+
+@pytest.mark.parametrize("shape", [(800, 3072, 768), (3152, 2048, 512), (4608, 2048, 512), (1000, 1024, 256)])
+def test_gelu_backward_epilogue_on_the_lean_kernel_fp16(monkeypatch, shape):
+    """The same body on the fp16 library (libcountr_hip_f16.so), one shape per kernel selection."""
+    _gelu_backward_epilogue_on_the_lean_kernel(HP.library(F16), monkeypatch, F16, shape)
+
+
+def _gelu_backward_epilogue_on_the_lean_kernel(hip, monkeypatch, fl, shape):
     M, N, K = shape                   # dy [M, K], Wt [N, K] (= fc2.weight^T), out / pre [M, N]
-    dy = _mk((M, K), torch.bfloat16, 21)
-    Wt = _mk((N, K), torch.bfloat16, 22)
-    pre = (_mk((M, N), torch.float32, 23) * 3).to(torch.bfloat16)
+    dy = _mk((M, K), fl.dtype, 21)
+    Wt = _mk((N, K), fl.dtype, 22)
+    pre = (_mk((M, N), torch.float32, 23) * 3).to(fl.dtype)
     keep = pre.clone()
 
     def run(lean):
         monkeypatch.setenv("COUNTR_LEAN", "1" if lean else "0")
         monkeypatch.setenv("COUNTR_G256", "1" if lean else "0")
-        out = torch.full((M, N), 7.0, device="cuda", dtype=torch.bfloat16)
+        out = torch.full((M, N), 7.0, device="cuda", dtype=fl.dtype)
         a = _lib.GemmArgs()
         a.A, a.B, a.C, a.C2 = dy.data_ptr(), Wt.data_ptr(), out.data_ptr(), pre.data_ptr()
         a.lda, a.ldb, a.ldc = K, K, N
@@ -140,11 +152,11 @@ def test_gelu_backward_epilogue_on_the_lean_kernel(hip, shape, monkeypatch):
     assert torch.equal(pre, keep)
     x = pre.double().requires_grad_(True)
     torch.nn.functional.gelu(x).backward(dy.double() @ Wt.double().t())
-    assert (lean.double() - x.grad).abs().max().item() <= 2e-2 * x.grad.abs().max().item()
-    assert (lean.double() - generic.double()).abs().max().item() <= 1e-2 * x.grad.abs().max().item()
+    assert (lean.double() - x.grad).abs().max().item() <= HP.bar(fl, 2e-2) * x.grad.abs().max().item()
+    assert (lean.double() - generic.double()).abs().max().item() <= HP.bar(fl, 1e-2) * x.grad.abs().max().item()
     # ... and against the two launches it replaces (GEMM -> bf16, then countr_gelu_bwd): one bf16 rounding apart
     monkeypatch.setenv("COUNTR_LEAN", "1")
-    two = torch.empty((M, N), device="cuda", dtype=torch.bfloat16)
+    two = torch.empty((M, N), device="cuda", dtype=fl.dtype)
     a = _lib.GemmArgs()
     a.A, a.B, a.C = dy.data_ptr(), Wt.data_ptr(), two.data_ptr()
     a.lda, a.ldb, a.ldc = K, K, N
@@ -155,7 +167,7 @@ def test_gelu_backward_epilogue_on_the_lean_kernel(hip, shape, monkeypatch):
     _lib.check(hip.countr_gemm(C.byref(a), 1, 0, 0, _stream()), "gemm")
     _lib.check(hip.countr_gelu_bwd(two.data_ptr(), pre.data_ptr(), two.data_ptr(), M * N, 1, _stream()), "gelu_bwd")
     torch.cuda.synchronize()
-    assert (lean.double() - two.double()).abs().max().item() <= 1.2e-2 * x.grad.abs().max().item()
+    assert (lean.double() - two.double()).abs().max().item() <= HP.bar(fl, 1.2e-2) * x.grad.abs().max().item()
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
@@ -353,13 +365,23 @@ def test_gemm_staged_and_direct_epilogues(hip, M, N, K):
     """bf16 kernels store finished values either as whole rows staged through LDS (16-byte aligned C rows) or directly from the
     accumulator layout (any other leading dimension / base alignment): both must give the same values, honour M / N tails and
     leave the padding of a wider C untouched; same for the fp32 residual read and the training pre-activation copy (C2)."""
-    A, B = _mk((M, K), torch.bfloat16, 11), _mk((N, K), torch.bfloat16, 12)
+    _gemm_staged_and_direct_epilogues(hip, HP.BF16, M, N, K)
+
+
+@pytest.mark.parametrize("M,N,K", [(200, 136, 96), (1000, 768, 128)])
+def test_gemm_staged_and_direct_epilogues_fp16(M, N, K):
+    """The same body on the fp16 library (libcountr_hip_f16.so), one shape per kernel selection."""
+    _gemm_staged_and_direct_epilogues(HP.library(F16), F16, M, N, K)
+
+
+def _gemm_staged_and_direct_epilogues(hip, fl, M, N, K):
+    A, B = _mk((M, K), fl.dtype, 11), _mk((N, K), fl.dtype, 12)
     bias = _mk((N,), torch.float32, 13)
     res = _mk((M, N), torch.float32, 14)
     base = A.double() @ B.double().t()
     for opt in ("plain", "bias", "bias+gelu", "bias+gelu+c2", "bias+resid", "resid"):
         for obf in ((1,) if "gelu" in opt else (0,) if "resid" in opt else (0, 1)):
-            odt = torch.bfloat16 if obf else torch.float32
+            odt = fl.dtype if obf else torch.float32
             for ldc, off in ((N, 0), (N + 8, 0), (N + 4, 0), (N + 8, 4), (N + 4, 4)):
                 store = torch.full((M * ldc + 8,), 7.0, device="cuda", dtype=odt)
                 store2 = torch.full((M * ldc + 8,), 7.0, device="cuda", dtype=odt)
@@ -380,7 +402,7 @@ def test_gemm_staged_and_direct_epilogues(hip, M, N, K):
                     a.resid, a.ldres = res.data_ptr(), N; ref = ref + res.double()
                 _lib.check(hip.countr_gemm(C.byref(a), 1, 0, 0, _stream()), "gemm")
                 torch.cuda.synchronize()
-                tol = 2e-2 if obf else 2e-4
+                tol = HP.bar(fl, 2e-2) if obf else 2e-4
                 for buf, want in ((store, ref), (store2, pre if "c2" in opt else None)):
                     view = buf[off:off + M * ldc].view(M, ldc)
                     if want is None:
@@ -433,12 +455,22 @@ def test_reduce_table_matches_individual_reductions(hip):
 def test_splitk_finish_matches_unsplit_conv(hip, obf):
     """Forward-type split-K (few tiles, long K: the 24x24 / 8x8 convolutions of the bf16 engine): implicit-GEMM conv with
     splitk = 4 into fp32 partials + countr_splitk_finish (sum, bias, output dtype) against the same conv in one launch."""
+    _splitk_finish_matches_unsplit_conv(hip, HP.BF16, obf)
+
+
+@pytest.mark.parametrize("obf", [0, 1])
+def test_splitk_finish_matches_unsplit_conv_fp16(obf):
+    """The same body on the fp16 library (libcountr_hip_f16.so), one shape per kernel selection."""
+    _splitk_finish_matches_unsplit_conv(HP.library(F16), F16, obf)
+
+
+def _splitk_finish_matches_unsplit_conv(hip, fl, obf):
     Bn, H, W, Cin, Cout = 3, 8, 8, 512, 256
-    x = _mk((Bn, H, W, Cin), torch.bfloat16, 31)
-    w = _mk((Cout, 9 * Cin), torch.bfloat16, 32) * 0.05
+    x = _mk((Bn, H, W, Cin), fl.dtype, 31)
+    w = _mk((Cout, 9 * Cin), fl.dtype, 32) * 0.05
     bias = _mk((Cout,), torch.float32, 33)
     M, K = Bn * H * W, 9 * Cin
-    odt = torch.bfloat16 if obf else torch.float32
+    odt = fl.dtype if obf else torch.float32
     ref = torch.empty((M, Cout), device="cuda", dtype=odt)
     a = _lib.GemmArgs(); a.alpha = 1.0; a.nbatch = 1; a.nb1 = 1; a.splitk = 1
     a.A, a.B, a.C, a.bias = x.data_ptr(), w.data_ptr(), ref.data_ptr(), bias.data_ptr()
@@ -454,7 +486,7 @@ def test_splitk_finish_matches_unsplit_conv(hip, obf):
     torch.cuda.synchronize()
     assert torch.isfinite(out.float()).all()
     scale = ref.float().abs().max().item()
-    assert (out.float() - ref.float()).abs().max().item() <= (8e-3 if obf else 2e-5) * scale
+    assert (out.float() - ref.float()).abs().max().item() <= (HP.bar(fl, 8e-3) if obf else 2e-5) * scale
 
 
 @pytest.mark.parametrize("M,N,K", [(128, 128, 128), (256, 384, 192), (4608, 512, 512), (1152, 768, 3072), (4608, 1536, 256), (4736, 1024, 128),
@@ -468,8 +500,19 @@ def test_lean_linear_matches_fp64_and_generic(hip, monkeypatch, M, N, K, epi):
     against torch fp64 and against gemm_kernel on the
     same inputs (COUNTR_LEAN=0).  Operands are bf16-exact, so the only error is fp32 accumulation order + the output rounding
     (+ <= 2.6e-5 absolute of the GELU fit)."""
-    A = _mk((M, K), torch.bfloat16, 21)
-    W = (_mk((N, K), torch.float32, 22) * 0.25).to(torch.bfloat16)
+    _lean_linear_matches_fp64_and_generic(hip, monkeypatch, HP.BF16, M, N, K, epi)
+
+
+@pytest.mark.parametrize("M,N,K", [(128, 128, 128), (40, 128, 128), (1728, 512, 512), (4736, 1024, 128), (4544, 2304, 128)])
+@pytest.mark.parametrize("epi", ["bf16", "gelu", "gelu_pre", "res", "resmod"])
+def test_lean_linear_matches_fp64_and_generic_fp16(monkeypatch, M, N, K, epi):
+    """fp16 library: the wave-specialised 128 x 128 form (one tile; 40 rows; ragged 1728 rows), the 256 x 128 form (296 tiles) and the 192 x 256 form, every epilogue."""
+    _lean_linear_matches_fp64_and_generic(HP.library(F16), monkeypatch, F16, M, N, K, epi)
+
+
+def _lean_linear_matches_fp64_and_generic(hip, monkeypatch, fl, M, N, K, epi):
+    A = _mk((M, K), fl.dtype, 21)
+    W = (_mk((N, K), torch.float32, 22) * 0.25).to(fl.dtype)
     bias = _mk((N,), torch.float32, 23)
     obf = epi in ("bf16", "gelu", "gelu_pre")
     rmod = (8 if M == 40 else (64 if M % 128 else 128)) if epi == "resmod" else 0      # (a divisor of M)
@@ -481,8 +524,8 @@ def test_lean_linear_matches_fp64_and_generic(hip, monkeypatch, M, N, K, epi):
     outs = []
     for lean in ("1", "0"):
         monkeypatch.setenv("COUNTR_LEAN", lean)
-        out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16 if obf else torch.float32)
-        pre = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16) if epi == "gelu_pre" else None
+        out = torch.full((M, N), float("nan"), device="cuda", dtype=fl.dtype if obf else torch.float32)
+        pre = torch.full((M, N), float("nan"), device="cuda", dtype=fl.dtype) if epi == "gelu_pre" else None
         a = _lib.GemmArgs()
         a.A, a.B, a.C = A.data_ptr(), W.data_ptr(), out.data_ptr()
         a.C2 = pre.data_ptr() if pre is not None else None
@@ -497,22 +540,31 @@ def test_lean_linear_matches_fp64_and_generic(hip, monkeypatch, M, N, K, epi):
         a.nbatch = 1; a.nb1 = 1; a.splitk = 1
         _lib.check(hip.countr_gemm(C.byref(a), 1, 0, 0, _stream()), "gemm")
         torch.cuda.synchronize()
-        tol = 4e-3 if obf else 2e-5                      # bf16 rounding (2^-9 relative to the element, <= that of the maximum) / fp32 order
+        tol = HP.bar(fl, 4e-3) if obf else 2e-5                      # bf16 rounding (2^-9 relative to the element, <= that of the maximum) / fp32 order
         scale = ref.abs().max().item()
         assert torch.isfinite(out.float()).all()
         assert (out.double() - ref).abs().max().item() <= tol * scale + 3e-5, (lean, (out.double() - ref).abs().max().item(), scale)
         if pre is not None:
-            assert (pre.double() - z).abs().max().item() <= 4e-3 * z.abs().max().item()
+            assert (pre.double() - z).abs().max().item() <= HP.bar(fl, 4e-3) * z.abs().max().item()
         outs.append(out)
     # the two kernels differ by accumulation order (and the GELU form): far below one bf16 ulp of the largest element
-    assert (outs[0].double() - outs[1].double()).abs().max().item() <= (8e-3 if obf else 2e-5) * ref.abs().max().item()
+    assert (outs[0].double() - outs[1].double()).abs().max().item() <= (HP.bar(fl, 8e-3) if obf else 2e-5) * ref.abs().max().item()
 
 
 def test_lean_linear_in_place_residual(hip):
     """proj / fc2 write the residual stream in place (C == resid): every element is read before it is written by the same lane."""
+    _lean_linear_in_place_residual(hip, HP.BF16)
+
+
+def test_lean_linear_in_place_residual_fp16():
+    """The same body on the fp16 library (libcountr_hip_f16.so), one shape per kernel selection."""
+    _lean_linear_in_place_residual(HP.library(F16), F16)
+
+
+def _lean_linear_in_place_residual(hip, fl):
     M, N, K = 4608, 768, 768
-    A = _mk((M, K), torch.bfloat16, 31)
-    W = (_mk((N, K), torch.float32, 32) * 0.25).to(torch.bfloat16)
+    A = _mk((M, K), fl.dtype, 31)
+    W = (_mk((N, K), torch.float32, 32) * 0.25).to(fl.dtype)
     bias = _mk((N,), torch.float32, 33)
     x = _mk((M, N), torch.float32, 34)
     ref = x.double() + A.double() @ W.double().t() + bias.double()
@@ -535,8 +587,18 @@ def test_lean_conv3x3_matches_fp64_and_generic(hip, monkeypatch, Bsz, H, W, Cin,
     against gemm_kernel (COUNTR_LEAN_CONV=0) on the same bf16 inputs -- zero padding at every image border, tiles that span image
     boundaries (H x W not a multiple of 256), rows narrower than a 32-pixel staging pass (W = 24), Cin = 64 (one k-tile per tap) and
     512, with and without bias (dgrad)."""
-    x = _mk((Bsz, H, W, Cin), torch.bfloat16, 51)                 # NHWC
-    w = (_mk((Cout, 3, 3, Cin), torch.float32, 52) * 0.1).to(torch.bfloat16)   # OHWI = [Cout][tap][Cin]
+    _lean_conv3x3_matches_fp64_and_generic(hip, monkeypatch, HP.BF16, Bsz, H, W, Cin, Cout, use_bias)
+
+
+@pytest.mark.parametrize("Bsz,H,W,Cin,Cout,use_bias", [(32, 24, 24, 64, 256, True), (3, 100, 100, 64, 256, True), (4, 48, 96, 256, 256, False)])
+def test_lean_conv3x3_matches_fp64_and_generic_fp16(monkeypatch, Bsz, H, W, Cin, Cout, use_bias):
+    """fp16 library: rows narrower than a staging pass with one k-tile per tap, tiles across image boundaries, four k-tiles per tap without bias."""
+    _lean_conv3x3_matches_fp64_and_generic(HP.library(F16), monkeypatch, F16, Bsz, H, W, Cin, Cout, use_bias)
+
+
+def _lean_conv3x3_matches_fp64_and_generic(hip, monkeypatch, fl, Bsz, H, W, Cin, Cout, use_bias):
+    x = _mk((Bsz, H, W, Cin), fl.dtype, 51)                 # NHWC
+    w = (_mk((Cout, 3, 3, Cin), torch.float32, 52) * 0.1).to(fl.dtype)   # OHWI = [Cout][tap][Cin]
     bias = _mk((Cout,), torch.float32, 53) if use_bias else None
     M, K = Bsz * H * W, 9 * Cin
     assert -(-M // 128) * (Cout // 128) > 256
@@ -546,7 +608,7 @@ def test_lean_conv3x3_matches_fp64_and_generic(hip, monkeypatch, Bsz, H, W, Cin,
     monkeypatch.setenv("COUNTR_G256", "0")            # (the 256 x 256 kernel has its own test below)
     for lean in ("1", "0"):
         monkeypatch.setenv("COUNTR_LEAN_CONV", lean)
-        out = torch.full((M, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
+        out = torch.full((M, Cout), float("nan"), device="cuda", dtype=fl.dtype)
         a = _lib.GemmArgs()
         a.A, a.B, a.C = x.data_ptr(), w.data_ptr(), out.data_ptr()
         a.bias = bias.data_ptr() if use_bias else None
@@ -559,9 +621,9 @@ def test_lean_conv3x3_matches_fp64_and_generic(hip, monkeypatch, Bsz, H, W, Cin,
         _lib.check(hip.countr_gemm(C.byref(a), 1, 2, 0, _stream()), "conv")
         torch.cuda.synchronize()
         assert torch.isfinite(out.float()).all()
-        assert (out.double() - ref).abs().max().item() <= 4e-3 * ref.abs().max().item(), lean
+        assert (out.double() - ref).abs().max().item() <= HP.bar(fl, 4e-3) * ref.abs().max().item(), lean
         outs.append(out)
-    assert (outs[0].double() - outs[1].double()).abs().max().item() <= 8e-3 * ref.abs().max().item()
+    assert (outs[0].double() - outs[1].double()).abs().max().item() <= HP.bar(fl, 8e-3) * ref.abs().max().item()
 
 
 @pytest.mark.parametrize("form", ["1", "2", "3"])
@@ -637,8 +699,18 @@ def test_lean_linear_wgrad_matches_fp64_and_generic(hip, monkeypatch, R, N, K, l
     (LIN form: both operands staged K-major as they lie in memory, transposing reads) against fp64 and gemm_kernel
     (COUNTR_LEAN_LWGRAD=0): operand pitches larger than the matrix (a q / k / v slice of a packed qkv gradient, an x with a wider
     row), 128x128 and 128x256 tiles, one slab, a single k-tile per slab."""
-    dyf = _mk((R, lddy), torch.bfloat16, 81)
-    xf = _mk((R, ldx), torch.bfloat16, 82)
+    _lean_linear_wgrad_matches_fp64_and_generic(hip, monkeypatch, HP.BF16, R, N, K, lddy, ldx, sk, with_bias)
+
+
+@pytest.mark.parametrize("R,N,K,lddy,ldx,sk,with_bias", [(64, 128, 128, 128, 128, 1, True), (1152, 256, 384, 256, 512, 3, True), (4608, 512, 512, 1536, 512, 8, False), (2304, 768, 3072, 768, 3072, 2, True)])
+def test_lean_linear_wgrad_matches_fp64_and_generic_fp16(monkeypatch, R, N, K, lddy, ldx, sk, with_bias):
+    """fp16 library: a single k-tile, 128 x 128 tiles with a wider x row, a slice of a packed gradient without bias, 128 x 256 tiles."""
+    _lean_linear_wgrad_matches_fp64_and_generic(HP.library(F16), monkeypatch, F16, R, N, K, lddy, ldx, sk, with_bias)
+
+
+def _lean_linear_wgrad_matches_fp64_and_generic(hip, monkeypatch, fl, R, N, K, lddy, ldx, sk, with_bias):
+    dyf = _mk((R, lddy), fl.dtype, 81)
+    xf = _mk((R, ldx), fl.dtype, 82)
     ref_w = dyf[:, :N].double().t() @ xf[:, :K].double()
     ref_b = dyf[:, :N].double().sum(0)
     res = []
@@ -680,9 +752,19 @@ def test_grouped_linear_wgrads_equal_the_separate_launches(hip, R, shapes, sk):
     """countr_gemm_group: the weight (+ bias) gradients of a block's nn.Linear layers in ONE launch == the same launches through
     countr_gemm one by one, bit for bit (partials and row-sum partials), and == fp64.  Reference: autograd of Mlp / Attention /
     CrossAttention (models_crossvit.py:46-128)."""
+    _grouped_linear_wgrads_equal_the_separate_launches(hip, HP.BF16, R, shapes, sk)
+
+
+@pytest.mark.parametrize("R,shapes,sk", [(1152, [(512, 2048), (1536, 512)], 3), (2304, [(768, 3072), (384, 384), (768, 768)], 1), (4608, [(512, 2048), (2048, 512), (512, 512), (512, 512)], 2)])
+def test_grouped_linear_wgrads_equal_the_separate_launches_fp16(R, shapes, sk):
+    """fp16 library: two launches in three slabs, a group on 128 x 128 tiles, a block on 128 x 256 tiles."""
+    _grouped_linear_wgrads_equal_the_separate_launches(HP.library(F16), F16, R, shapes, sk)
+
+
+def _grouped_linear_wgrads_equal_the_separate_launches(hip, fl, R, shapes, sk):
     n = len(shapes)
-    dys = [_mk((R, N), torch.bfloat16, 91 + i) for i, (N, K) in enumerate(shapes)]
-    xs = [_mk((R, K), torch.bfloat16, 95 + i) for i, (N, K) in enumerate(shapes)]
+    dys = [_mk((R, N), fl.dtype, 91 + i) for i, (N, K) in enumerate(shapes)]
+    xs = [_mk((R, K), fl.dtype, 95 + i) for i, (N, K) in enumerate(shapes)]
 
     def make():
         arr = (_lib.GemmArgs * n)()
@@ -732,15 +814,26 @@ def test_lean_linear_layernorm_folding(hip, M, N2, act):
     rounded RAW row instead of the rounded normalised row, so its rounding error relative to sigma grows by sqrt(1 + (mean / sigma)^2).
     Rows with mean ~ 0 (the transformer's case: per-token means of the residual stream are a fraction of sigma) must match the unfolded
     path's error; every 7th row here has |mean| = 12 sigma and is held to that factor (documented limit, COUNTR_LN_FOLD=0 is the way out)."""
+    _lean_linear_layernorm_folding(hip, HP.BF16, M, N2, act)
+
+
+@pytest.mark.parametrize("M,N2", [(576, 1536), (4400, 2304)])
+@pytest.mark.parametrize("act", [0, 1])
+def test_lean_linear_layernorm_folding_fp16(M, N2, act):
+    """fp16 library: the 128-row form and the 192 x 256 form with a ragged last tile."""
+    _lean_linear_layernorm_folding(HP.library(F16), F16, M, N2, act)
+
+
+def _lean_linear_layernorm_folding(hip, fl, M, N2, act):
     D = 768
     eps = 1e-6
-    A0 = _mk((M, D), torch.bfloat16, 61)
-    W0 = (_mk((D, D), torch.float32, 62) * 0.05).to(torch.bfloat16)
+    A0 = _mk((M, D), fl.dtype, 61)
+    W0 = (_mk((D, D), torch.float32, 62) * 0.05).to(fl.dtype)
     b0 = _mk((D,), torch.float32, 63)
     x_in = _mk((M, D), torch.float32, 64) * 2
     x_in[::7] += 15.0                                             # rows with mean >> sigma
     x = x_in.clone()
-    xb = torch.full((M, D), float("nan"), device="cuda", dtype=torch.bfloat16)
+    xb = torch.full((M, D), float("nan"), device="cuda", dtype=fl.dtype)
     st = torch.full((M, D // 64, 2), float("nan"), device="cuda", dtype=torch.float32)
     a = _lib.GemmArgs()
     a.A, a.B, a.C, a.resid, a.bias = A0.data_ptr(), W0.data_ptr(), x.data_ptr(), x.data_ptr(), b0.data_ptr()
@@ -753,7 +846,7 @@ def test_lean_linear_layernorm_folding(hip, M, N2, act):
     torch.cuda.synchronize()
     xr = x_in.double() + A0.double() @ W0.double().t() + b0.double()
     assert (x.double() - xr).abs().max().item() <= 2e-5 * xr.abs().max().item()
-    assert torch.equal(xb, x.to(torch.bfloat16))                                            # the copy is the rounded fp32 output
+    assert torch.equal(xb, x.to(fl.dtype))                                            # the copy is the rounded fp32 output
     blocks = x.double().view(M, D // 64, 64)
     assert (st[..., 0].double() - blocks.sum(-1)).abs().max().item() <= 1e-4 * blocks.sum(-1).abs().max().item()
     assert (st[..., 1].double() - (blocks ** 2).sum(-1)).abs().max().item() <= 1e-5 * (blocks ** 2).sum(-1).abs().max().item()
@@ -762,10 +855,10 @@ def test_lean_linear_layernorm_folding(hip, M, N2, act):
     beta = _mk((D,), torch.float32, 66) * 0.2
     W1 = _mk((N2, D), torch.float32, 67) * 0.05
     b1 = _mk((N2,), torch.float32, 68)
-    Wf = (W1 * gamma[None, :]).to(torch.bfloat16)
+    Wf = (W1 * gamma[None, :]).to(fl.dtype)
     colsum = Wf.float().sum(1).contiguous()
     bf = (b1 + W1 @ beta).contiguous()
-    out = torch.full((M, N2), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = torch.full((M, N2), float("nan"), device="cuda", dtype=fl.dtype)
     c = _lib.GemmArgs()
     c.A, c.B, c.C, c.bias = xb.data_ptr(), Wf.data_ptr(), out.data_ptr(), bf.data_ptr()
     c.lda, c.ldb, c.ldc = D, D, N2
@@ -783,10 +876,10 @@ def test_lean_linear_layernorm_folding(hip, M, N2, act):
         ref = torch.nn.functional.gelu(ref)
     err = (out.double() - ref).abs()
     # what the unfolded path costs: LN output rounded to bf16, weights rounded to bf16, bf16 output
-    base = torch.nn.functional.layer_norm(x.double(), (D,), gamma.double(), beta.double(), eps).to(torch.bfloat16).double() @ W1.to(torch.bfloat16).double().t() + b1.double()
+    base = torch.nn.functional.layer_norm(x.double(), (D,), gamma.double(), beta.double(), eps).to(fl.dtype).double() @ W1.to(fl.dtype).double().t() + b1.double()
     if act:
         base = torch.nn.functional.gelu(base)
-    base_err = (base.to(torch.bfloat16).double() - ref).abs()
+    base_err = (base.to(fl.dtype).double() - ref).abs()
     assert torch.isfinite(out.float()).all()
     kappa = torch.sqrt(1 + (x.double().mean(1) / x.double().std(1, unbiased=False)) ** 2)          # per-row amplification of the operand rounding
     plain = kappa < 1.5
@@ -811,8 +904,19 @@ def test_g256_linear_matches_fp64_and_lean(hip, monkeypatch, M, N, K, epi):
     forms of linear.hip (COUNTR_G256=0).
     The launch is repeated: a phase-schedule race (an LDS-DMA unit read before the barrier that orders it) shows as run-to-run
     differences long before it shows against fp64."""
-    A = _mk((M, K), torch.bfloat16, 121)
-    W = (_mk((N, K), torch.float32, 122) * 0.25).to(torch.bfloat16)
+    _g256_linear_matches_fp64_and_lean(hip, monkeypatch, HP.BF16, M, N, K, epi)
+
+
+@pytest.mark.parametrize("M,N,K", [(256, 256, 256), (40, 256, 256), (1000, 512, 384), (2880, 3072, 768)])
+@pytest.mark.parametrize("epi", ["bf16", "gelu", "gelu_pre"])
+def test_g256_linear_matches_fp64_and_lean_fp16(monkeypatch, M, N, K, epi):
+    """fp16 library: the shortest legal K, 40 and 1000 ragged rows, fc1 at five images."""
+    _g256_linear_matches_fp64_and_lean(HP.library(F16), monkeypatch, F16, M, N, K, epi)
+
+
+def _g256_linear_matches_fp64_and_lean(hip, monkeypatch, fl, M, N, K, epi):
+    A = _mk((M, K), fl.dtype, 121)
+    W = (_mk((N, K), torch.float32, 122) * 0.25).to(fl.dtype)
     bias = _mk((N,), torch.float32, 123)
     z = A.double() @ W.double().t() + bias.double()
     ref = torch.nn.functional.gelu(z) if epi.startswith("gelu") else z
@@ -821,8 +925,8 @@ def test_g256_linear_matches_fp64_and_lean(hip, monkeypatch, M, N, K, epi):
         monkeypatch.setenv("COUNTR_G256", mode)
         runs = []
         for rep in range(3 if mode == "2" else 1):
-            out = torch.full((M + 8, N), float("nan"), device="cuda", dtype=torch.bfloat16)     # 8 guard rows behind M
-            pre = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16) if epi == "gelu_pre" else None
+            out = torch.full((M + 8, N), float("nan"), device="cuda", dtype=fl.dtype)     # 8 guard rows behind M
+            pre = torch.full((M, N), float("nan"), device="cuda", dtype=fl.dtype) if epi == "gelu_pre" else None
             a = _lib.GemmArgs()
             a.A, a.B, a.C = A.data_ptr(), W.data_ptr(), out.data_ptr()
             a.C2 = pre.data_ptr() if pre is not None else None
@@ -839,9 +943,9 @@ def test_g256_linear_matches_fp64_and_lean(hip, monkeypatch, M, N, K, epi):
             out = out[:M]
             assert torch.isfinite(out.float()).all()
             scale = ref.abs().max().item()
-            assert (out.double() - ref).abs().max().item() <= 4e-3 * scale + 3e-5, (mode, (out.double() - ref).abs().max().item(), scale)
+            assert (out.double() - ref).abs().max().item() <= HP.bar(fl, 4e-3) * scale + 3e-5, (mode, (out.double() - ref).abs().max().item(), scale)
             if pre is not None:
-                assert (pre.double() - z).abs().max().item() <= 4e-3 * z.abs().max().item()
+                assert (pre.double() - z).abs().max().item() <= HP.bar(fl, 4e-3) * z.abs().max().item()
             runs.append(out)
         for r in runs[1:]:
             assert torch.equal(r, runs[0]), "run-to-run difference (phase-schedule race)"
@@ -857,8 +961,19 @@ def test_g256_linear_residual_and_layernorm_producer(hip, monkeypatch, M, N, K, 
     optionally with the LayerNorm producer's bf16 copy and per-64-column {sum, sum of squares} row partials): against fp64 and --
     output, copy and partials BIT FOR BIT -- against linear.hip's kernel (COUNTR_G256=0), ragged M and a row-modulo residual included.
     Reference: Block.forward x = x + attn(norm1(x)); x = x + mlp(norm2(x)) (timm 0.4.9, models_mae_cross.py:32-34)."""
-    A = _mk((M, K), torch.bfloat16, 141)
-    W = (_mk((N, K), torch.float32, 142) * 0.25).to(torch.bfloat16)
+    _g256_linear_residual_and_layernorm_producer(hip, monkeypatch, HP.BF16, M, N, K, res_mod, producer)
+
+
+@pytest.mark.parametrize("M,N,K,res_mod", [(1000, 512, 384, 0), (1152, 256, 256, 576), (40, 768, 256, 0)])
+@pytest.mark.parametrize("producer", [True, False])
+def test_g256_linear_residual_and_layernorm_producer_fp16(monkeypatch, M, N, K, res_mod, producer):
+    """The same body on the fp16 library (libcountr_hip_f16.so), one shape per kernel selection."""
+    _g256_linear_residual_and_layernorm_producer(HP.library(F16), monkeypatch, F16, M, N, K, res_mod, producer)
+
+
+def _g256_linear_residual_and_layernorm_producer(hip, monkeypatch, fl, M, N, K, res_mod, producer):
+    A = _mk((M, K), fl.dtype, 141)
+    W = (_mk((N, K), torch.float32, 142) * 0.25).to(fl.dtype)
     bias = _mk((N,), torch.float32, 143)
     resid = _mk((res_mod if res_mod else M, N), torch.float32, 144) * 3.0
     rr = resid.double().repeat(M // res_mod, 1) if res_mod else resid.double()
@@ -869,7 +984,7 @@ def test_g256_linear_residual_and_layernorm_producer(hip, monkeypatch, M, N, K, 
         runs = []
         for rep in range(3 if mode == "2" else 1):
             out = torch.full((M + 8, N), float("nan"), device="cuda", dtype=torch.float32)
-            xcopy = torch.full((M + 8, N), float("nan"), device="cuda", dtype=torch.bfloat16)
+            xcopy = torch.full((M + 8, N), float("nan"), device="cuda", dtype=fl.dtype)
             stats = torch.full((M + 8, N // 64, 2), float("nan"), device="cuda", dtype=torch.float32)
             a = _lib.GemmArgs()
             a.A, a.B, a.C = A.data_ptr(), W.data_ptr(), out.data_ptr()
@@ -890,7 +1005,7 @@ def test_g256_linear_residual_and_layernorm_producer(hip, monkeypatch, M, N, K, 
                 o = out[:M].double()
                 want = torch.stack([o.view(M, N // 64, 64).sum(-1), (o * o).view(M, N // 64, 64).sum(-1)], dim=-1)
                 assert (stats[:M].double() - want).abs().max().item() <= 1e-5 * want.abs().max().item()
-                assert torch.equal(xcopy[:M], out[:M].to(torch.bfloat16))
+                assert torch.equal(xcopy[:M], out[:M].to(fl.dtype))
             else:
                 assert torch.isnan(xcopy.float()).all() and torch.isnan(stats).all()
             runs.append((out[:M].clone(), xcopy[:M].clone(), stats[:M].clone()))
@@ -907,9 +1022,19 @@ def test_g256_linear_residual_and_layernorm_producer(hip, monkeypatch, M, N, K, 
 def test_g256_linear_layernorm_consumer(hip, monkeypatch, M, N, K):
     """The LayerNorm-fold consumer epilogue of the 256 x 256 kernel (fc1 in the frozen encoder: rstd (acc - mean colsum) + bias' from the
     producer's per-64-column {sum, sum of squares} row partials) against the same launch on linear.hip's kernel and against fp64."""
+    _g256_linear_layernorm_consumer(hip, monkeypatch, HP.BF16, M, N, K)
+
+
+@pytest.mark.parametrize("M,N,K", [(1152, 1536, 512), (300, 256, 256)])
+def test_g256_linear_layernorm_consumer_fp16(monkeypatch, M, N, K):
+    """The same body on the fp16 library (libcountr_hip_f16.so), one shape per kernel selection."""
+    _g256_linear_layernorm_consumer(HP.library(F16), monkeypatch, F16, M, N, K)
+
+
+def _g256_linear_layernorm_consumer(hip, monkeypatch, fl, M, N, K):
     x = _mk((M, K), torch.float32, 131) * 2.0 + _mk((M, 1), torch.float32, 132)
-    xb = x.to(torch.bfloat16)
-    W = (_mk((N, K), torch.float32, 133) * 0.25).to(torch.bfloat16)
+    xb = x.to(fl.dtype)
+    W = (_mk((N, K), torch.float32, 133) * 0.25).to(fl.dtype)
     bias = _mk((N,), torch.float32, 134)
     xs = x.double()                                   # statistics of the fp32 row (what the producer's epilogue sums)
     stats = torch.stack([xs.view(M, K // 64, 64).sum(-1), (xs * xs).view(M, K // 64, 64).sum(-1)], dim=-1).float().contiguous()
@@ -920,7 +1045,7 @@ def test_g256_linear_layernorm_consumer(hip, monkeypatch, M, N, K):
     outs = {}
     for mode in ("2", "0"):
         monkeypatch.setenv("COUNTR_G256", mode)
-        out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.bfloat16)
+        out = torch.full((M, N), float("nan"), device="cuda", dtype=fl.dtype)
         a = _lib.GemmArgs()
         a.A, a.B, a.C, a.bias = xb.data_ptr(), W.data_ptr(), out.data_ptr(), bias.data_ptr()
         a.lda, a.ldb, a.ldc = K, K, N
@@ -931,7 +1056,7 @@ def test_g256_linear_layernorm_consumer(hip, monkeypatch, M, N, K):
         _lib.check(hip.countr_gemm(C.byref(a), 1, 0, 0, _stream()), "gemm")
         torch.cuda.synchronize()
         assert torch.isfinite(out.float()).all()
-        assert (out.double() - ref).abs().max().item() <= 6e-3 * ref.abs().max().item() + 3e-5, mode
+        assert (out.double() - ref).abs().max().item() <= HP.bar(fl, 6e-3) * ref.abs().max().item() + 3e-5, mode
         outs[mode] = out
     # same k order per element, same epilogue arithmetic (explicit fma in both): the kernel a batch size selects must not change a result
     assert torch.equal(outs["2"], outs["0"]), (outs["2"].double() - outs["0"].double()).abs().max().item()
@@ -947,8 +1072,18 @@ def test_g256_conv3x3_matches_fp64_and_lean(hip, monkeypatch, Bsz, H, W, Cin, Co
     24 x 24 = 2.25 images per tile), a map smaller than one tile (20 x 12: most staged rows are masked), Cin = 128 / 256 / 512
     (2 / 4 / 8 k-tiles per tap), with and without bias; a grid of 1.44 rounds of workgroups, which runs as one full round on this kernel plus
     a tail launch of the 128-row kernel on the last rows (split rounds); three runs must agree bit for bit (race screen)."""
-    x = _mk((Bsz, H, W, Cin), torch.bfloat16, 151)
-    w = (_mk((Cout, 3, 3, Cin), torch.float32, 152) * 0.1).to(torch.bfloat16)
+    _g256_conv3x3_matches_fp64_and_lean(hip, monkeypatch, HP.BF16, Bsz, H, W, Cin, Cout, use_bias)
+
+
+@pytest.mark.parametrize("Bsz,H,W,Cin,Cout,use_bias", [(1, 20, 12, 128, 256, True), (3, 100, 100, 128, 512, True), (8, 48, 48, 512, 256, False), (23, 64, 64, 128, 256, True)])
+def test_g256_conv3x3_matches_fp64_and_lean_fp16(monkeypatch, Bsz, H, W, Cin, Cout, use_bias):
+    """fp16 library: a map below one tile, tiles across image boundaries, eight k-tiles per tap without bias, split rounds."""
+    _g256_conv3x3_matches_fp64_and_lean(HP.library(F16), monkeypatch, F16, Bsz, H, W, Cin, Cout, use_bias)
+
+
+def _g256_conv3x3_matches_fp64_and_lean(hip, monkeypatch, fl, Bsz, H, W, Cin, Cout, use_bias):
+    x = _mk((Bsz, H, W, Cin), fl.dtype, 151)
+    w = (_mk((Cout, 3, 3, Cin), torch.float32, 152) * 0.1).to(fl.dtype)
     bias = _mk((Cout,), torch.float32, 153) if use_bias else None
     M, K = Bsz * H * W, 9 * Cin
     ref = torch.nn.functional.conv2d(x.double().permute(0, 3, 1, 2), w.double().permute(0, 3, 1, 2), bias.double() if use_bias else None, padding=1)
@@ -958,7 +1093,7 @@ def test_g256_conv3x3_matches_fp64_and_lean(hip, monkeypatch, Bsz, H, W, Cin, Co
         monkeypatch.setenv("COUNTR_G256", mode)
         runs = []
         for rep in range(3 if mode == "2" else 1):
-            out = torch.full((M, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
+            out = torch.full((M, Cout), float("nan"), device="cuda", dtype=fl.dtype)
             a = _lib.GemmArgs()
             a.A, a.B, a.C = x.data_ptr(), w.data_ptr(), out.data_ptr()
             a.bias = bias.data_ptr() if use_bias else None
@@ -970,7 +1105,7 @@ def test_g256_conv3x3_matches_fp64_and_lean(hip, monkeypatch, Bsz, H, W, Cin, Co
             _lib.check(hip.countr_gemm(C.byref(a), 1, 2, 0, _stream()), "conv")
             torch.cuda.synchronize()
             assert torch.isfinite(out.float()).all()
-            assert (out.double() - ref).abs().max().item() <= 4e-3 * ref.abs().max().item(), mode
+            assert (out.double() - ref).abs().max().item() <= HP.bar(fl, 4e-3) * ref.abs().max().item(), mode
             runs.append(out)
         for r in runs[1:]:
             assert torch.equal(r, runs[0]), "run-to-run difference (phase-schedule race)"
@@ -987,14 +1122,24 @@ def test_conv3x3_groupnorm_row_partials(hip, monkeypatch, Bsz, H, W, Cin, Cout):
     tile or the batch it was computed in -- bit for bit between the 256 x 256 kernel (incl. its split rounds: 23 images of 64 x 64),
     the 128-row kernel alone, and a launch over the first image only; rows behind M are not written; countr_gemm_gn_rows answers the
     selection question and a launch that falls to a kernel without the epilogue fails instead of leaving the buffer unwritten."""
-    x = _mk((Bsz, H, W, Cin), torch.bfloat16, 161)
-    w = (_mk((Cout, 3, 3, Cin), torch.float32, 162) * 0.1).to(torch.bfloat16)
+    _conv3x3_groupnorm_row_partials(hip, monkeypatch, HP.BF16, Bsz, H, W, Cin, Cout)
+
+
+@pytest.mark.parametrize("Bsz,H,W,Cin,Cout", [(2, 96, 96, 256, 256), (23, 64, 64, 128, 256), (3, 100, 100, 128, 512)])
+def test_conv3x3_groupnorm_row_partials_fp16(monkeypatch, Bsz, H, W, Cin, Cout):
+    """fp16 library, same contract: the partials are sums of the ROUNDED fp16 output and the two statistics routes agree bit for bit."""
+    _conv3x3_groupnorm_row_partials(HP.library(F16), monkeypatch, F16, Bsz, H, W, Cin, Cout)
+
+
+def _conv3x3_groupnorm_row_partials(hip, monkeypatch, fl, Bsz, H, W, Cin, Cout):
+    x = _mk((Bsz, H, W, Cin), fl.dtype, 161)
+    w = (_mk((Cout, 3, 3, Cin), torch.float32, 162) * 0.1).to(fl.dtype)
     bias = _mk((Cout,), torch.float32, 163)
     M, K, NG = Bsz * H * W, 9 * Cin, Cout // 32
 
     def launch(mode, m_rows, with_rows=True):
         monkeypatch.setenv("COUNTR_G256", mode)
-        out = torch.full((m_rows, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
+        out = torch.full((m_rows, Cout), float("nan"), device="cuda", dtype=fl.dtype)
         rows = torch.full((m_rows + 4, NG, 2), float("nan"), device="cuda", dtype=torch.float32)
         a = _lib.GemmArgs()
         a.A, a.B, a.C, a.bias = x.data_ptr(), w.data_ptr(), out.data_ptr(), bias.data_ptr()
@@ -1047,8 +1192,8 @@ def test_conv3x3_groupnorm_row_partials(hip, monkeypatch, Bsz, H, W, Cin, Cout):
         _o, rows1 = launch("1", H * W)
         assert torch.equal(rows1[:H * W], res["0"][:H * W])
     # a map of fewer than 257 tiles runs on the generic kernel: the query says so, the launch refuses
-    xs = _mk((1, 24, 24, Cin), torch.bfloat16, 164)
-    outs = torch.empty((576, Cout), device="cuda", dtype=torch.bfloat16)
+    xs = _mk((1, 24, 24, Cin), fl.dtype, 164)
+    outs = torch.empty((576, Cout), device="cuda", dtype=fl.dtype)
     rows = torch.zeros((576, NG, 2), device="cuda")
     a = _lib.GemmArgs()
     a.A, a.B, a.C, a.bias = xs.data_ptr(), w.data_ptr(), outs.data_ptr(), bias.data_ptr()

@@ -6,12 +6,17 @@ import ctypes as C
 import pytest
 import torch
 
+import halfprec as HP
 from countr_amd import _lib
 from oracle import countr_ref as R
 
 pytestmark = pytest.mark.gpu
 
-DT = [(torch.float32, 0, 2e-4), (torch.bfloat16, 1, 2e-2)]
+# (torch dtype, dtype code of the C ABI, max-norm bar).  fp32 and bf16 run on libcountr_hip.so (the session fixture); fp16 is the 16-bit
+# type of libcountr_hip_f16.so -- same code, its own library (HP.library) -- with the bf16 bar / 8 (2^-11 against 2^-8, the convention of
+# tests/test_fp16_gpu.py).  Outputs that are ONE rounding of an fp32 result also meet HP.assert_elementwise with the fp32 bar as floor.
+DT = [(torch.float32, 0, 2e-4), (torch.bfloat16, 1, 2e-2), (torch.float16, 1, 2.5e-3)]
+F32_TOL = DT[0][2]
 
 
 def st():
@@ -36,6 +41,7 @@ def P(t):
 @pytest.mark.parametrize("D", [768, 512, 1024])
 @pytest.mark.parametrize("tdt,code,tol", DT)
 def test_layernorm_fwd_bwd(hip, D, tdt, code, tol):
+    hip = HP.library(tdt, hip)
     rows = 1157
     x = rnd((rows, D), 1, 2.0) + 0.3
     g = 1 + 0.1 * rnd((D,), 2)
@@ -51,19 +57,22 @@ def test_layernorm_fwd_bwd(hip, D, tdt, code, tol):
     br = b.double().requires_grad_(True)
     yr = R.layer_norm(xr, gr, br)
     assert relerr(y, yr) < tol
+    if code:
+        HP.assert_elementwise(y, yr, HP.BY_DTYPE[tdt], F32_TOL, "layernorm y")
+    h16 = tdt if code else torch.bfloat16            # the 16-bit type of the library this case runs on
     nb = hip.countr_layernorm_bwd_nblocks()
     ws = torch.empty((nb, 2, D), device="cuda")
     dx = torch.full((rows, D), 0.5, device="cuda")
     dgb = torch.zeros((2, D), device="cuda")
     dyd = dy.cuda()
-    dxb = torch.empty((rows, D), device="cuda", dtype=torch.bfloat16)
+    dxb = torch.empty((rows, D), device="cuda", dtype=h16)
     _lib.check(hip.countr_layernorm_bwd(P(dyd), P(xd), P(gd), P(mean), P(rstd), P(dx), P(dgb[0]), P(dgb[1]), P(ws), rows, D,
                                         code, 1, 0, P(dxb), st()))   # adjacent dgamma/dbeta: single finisher launch
     yr.backward(dy.double())
     assert relerr(dx - 0.5, xr.grad) < 1e-4
     assert relerr(dgb[0], gr.grad) < 1e-4
     assert relerr(dgb[1], br.grad) < 1e-4
-    assert torch.equal(dxb, dx.bfloat16())          # the optional bf16 copy is the RNE rounding of the updated dx
+    assert torch.equal(dxb, dx.to(h16))             # the optional 16-bit copy is the RNE rounding of the updated dx
     # separate (non-adjacent) outputs, accumulate into existing values, no bf16 copy
     dg2, db2 = torch.ones(D, device="cuda"), torch.ones(D, device="cuda")
     _lib.check(hip.countr_layernorm_bwd(P(dyd), P(xd), P(gd), P(mean), P(rstd), P(dx), P(dg2), P(db2), P(ws), rows, D,
@@ -75,6 +84,7 @@ def test_layernorm_fwd_bwd(hip, D, tdt, code, tol):
 @pytest.mark.parametrize("HW", [24 * 24, 96 * 96, 35 * 35, 100])   # incl. pixel counts that do not divide into the splits
 @pytest.mark.parametrize("tdt,code,tol", DT)
 def test_groupnorm_relu_fwd_bwd(hip, HW, tdt, code, tol):
+    hip = HP.library(tdt, hip)
     B, Cc, G = 2, 256, 8
     x = (rnd((B, HW, Cc), 5, 1.5) + 0.2).to(tdt)
     g = 1 + 0.1 * rnd((Cc,), 6)
@@ -97,6 +107,8 @@ def test_groupnorm_relu_fwd_bwd(hip, HW, tdt, code, tol):
     yr = R.group_norm_relu(xr, gr, br)
     y_ref = yr.permute(0, 2, 3, 1).reshape(B, HW, Cc)
     assert relerr(y, y_ref) < tol
+    if code:
+        HP.assert_elementwise(y, y_ref, HP.BY_DTYPE[tdt], F32_TOL, "groupnorm+relu y")
     # backward (plain)
     dx = torch.empty_like(xd)
     dg = torch.zeros(Cc, device="cuda"); db = torch.zeros(Cc, device="cuda")
@@ -161,6 +173,7 @@ def test_groupnorm_statistics_from_row_partials(hip, HW):
 @pytest.mark.parametrize("H,Cc,avg", [(64, 64, 0), (32, 128, 0), (16, 256, 0), (8, 512, 1), (40, 64, 0), (12, 128, 0)])   # 40, 12: odd band counts
 @pytest.mark.parametrize("tdt,code,tol", DT)
 def test_instnorm_relu_pool(hip, H, Cc, avg, tdt, code, tol, use_ws):
+    hip = HP.library(tdt, hip)
     S = 3
     x = (rnd((S, H, H, Cc), 11, 1.3) + 0.1).to(tdt)
     xd = x.cuda()
@@ -173,6 +186,8 @@ def test_instnorm_relu_pool(hip, H, Cc, avg, tdt, code, tol, use_ws):
     a = R.instance_norm_relu(xr)
     yr = a.mean((2, 3)) if avg else R.max_pool2(a).permute(0, 2, 3, 1)
     assert relerr(y, yr) < tol
+    if code:
+        HP.assert_elementwise(y, yr, HP.BY_DTYPE[tdt], F32_TOL, "instnorm+relu+pool y")
     dyp = rnd(oshape, 12).to(tdt)
     dx = torch.empty_like(xd)
     dypd = dyp.cuda()
@@ -244,6 +259,7 @@ def test_instnorm_on_fp32_maps_survives_large_channel_means(hip, avg, H):
 
 @pytest.mark.parametrize("tdt,code,tol", DT)
 def test_softmax_fwd_bwd(hip, tdt, code, tol):
+    hip = HP.library(tdt, hip)
     rows, n = 2 * 16 * 576, 576
     s = rnd((rows, n), 13, 3.0)
     sd = s.cuda()
@@ -252,6 +268,8 @@ def test_softmax_fwd_bwd(hip, tdt, code, tol):
     sr = s.double().requires_grad_(True)
     pr = torch.softmax(sr, -1)
     assert relerr(p, pr) < tol
+    if code:
+        HP.assert_elementwise(p, pr, HP.BY_DTYPE[tdt], F32_TOL, "softmax")
     dp = rnd((rows, n), 14)
     ds = torch.empty_like(p)
     dpd = dp.cuda()
@@ -266,6 +284,7 @@ def test_softmax_fwd_bwd(hip, tdt, code, tol):
 def test_cross_attention_fwd_bwd(hip, S, tdt, code, tol):
     """S <= 8: keys in registers; more (models_crossvit.py:111-128 has no limit, FSC_test_cross(few-shot).py --box_bound -1 passes every
     annotated box): online softmax over the key rows, dk / dv through per-wave LDS regions in key chunks."""
+    hip = HP.library(tdt, hip)
     B, N, D, Hh = 2, 576, 512, 16
     q = rnd((B, N, D), 15).to(tdt)
     k = rnd((B, S, D), 16).to(tdt)
@@ -285,10 +304,11 @@ def test_cross_attention_fwd_bwd(hip, S, tdt, code, tol):
     dq = torch.empty_like(qd)
     dk = torch.empty((B, S, D), device="cuda"); dv = torch.empty((B, S, D), device="cuda")
     ws = torch.empty(hip.countr_xattn_bwd_workspace_floats(B, N, S, D), device="cuda")
-    dkb = torch.empty((B, S, D), device="cuda", dtype=torch.bfloat16); dvb = torch.empty_like(dkb)
+    h16 = tdt if code else torch.bfloat16
+    dkb = torch.empty((B, S, D), device="cuda", dtype=h16); dvb = torch.empty_like(dkb)
     _lib.check(hip.countr_xattn_bwd(P(qd), P(kd), P(vd), P(dod), P(dq), P(dk), P(dv), P(ws), B, N, S, D, Hh, D, scale, code, P(dkb), P(dvb), st()))
     torch.cuda.synchronize()
-    assert torch.equal(dkb, dk.to(torch.bfloat16)) and torch.equal(dvb, dv.to(torch.bfloat16))     # the optional bf16 copies
+    assert torch.equal(dkb, dk.to(h16)) and torch.equal(dvb, dv.to(h16))     # the optional 16-bit copies
     oref.backward(do.double())
     assert relerr(dq, qr.grad) < tol
     assert relerr(dk, kr.grad) < 1e-3 and relerr(dv, vr.grad) < 1e-3
@@ -296,13 +316,16 @@ def test_cross_attention_fwd_bwd(hip, S, tdt, code, tol):
 
 @pytest.mark.parametrize("tdt,code,tol", DT)
 def test_im2patch_and_c3conv(hip, tdt, code, tol):
+    hip = HP.library(tdt, hip)
     B = 2
     img = torch.rand((B, 3, 384, 384), generator=torch.Generator().manual_seed(19))
     out = torch.empty((B * 576, 768), device="cuda", dtype=tdt)
     imgd = img.cuda()
     _lib.check(hip.countr_im2patch(P(imgd), P(out), B, 384, 384, 16, code, st()))
     ref = img.reshape(B, 3, 24, 16, 24, 16).permute(0, 2, 4, 1, 3, 5).reshape(B * 576, 768)
-    assert relerr(out, ref) < (1e-7 if code == 0 else 4e-3)
+    assert relerr(out, ref) < (1e-7 if code == 0 else HP.bar(tdt, 4e-3))
+    if code:
+        HP.assert_elementwise(out, ref, HP.BY_DTYPE[tdt], 1e-7, "im2patch")
     # first exemplar conv
     S = 4
     bx = torch.rand((S, 3, 64, 64), generator=torch.Generator().manual_seed(20))
@@ -313,6 +336,8 @@ def test_im2patch_and_c3conv(hip, tdt, code, tol):
     wr = w.double().requires_grad_(True); br = bias.double().requires_grad_(True)
     yr = torch.nn.functional.conv2d(bx.double(), wr, br, padding=1)
     assert relerr(y, yr.permute(0, 2, 3, 1)) < tol
+    if code:
+        HP.assert_elementwise(y, yr.permute(0, 2, 3, 1), HP.BY_DTYPE[tdt], F32_TOL, "c3 conv")
     dy = rnd((S, 64, 64, 64), 23).to(tdt)
     dw = torch.zeros_like(wd); db = torch.zeros_like(bd)
     ws = torch.empty(hip.countr_conv3x3_c3_wgrad_nblocks() * 64 * 28, device="cuda")
@@ -328,6 +353,7 @@ def test_first_exemplar_conv_quad_kernel_equals_the_per_pixel_kernel(hip, monkey
     """conv3x3_c3_fwd4_kernel (four pixels of a row per thread: a tap's weights read from LDS once for four pixels, the 3 x 6 input
     window loaded once) against the per-pixel kernel (COUNTR_C3_QUAD=0): same taps in the same order per output -- IDENTICAL values --
     and against conv2d in fp64; image borders at every quad position, rows of one quad."""
+    hip = HP.library(tdt, hip)
     x = torch.rand((S, 3, H, W), generator=torch.Generator().manual_seed(61)).cuda()
     w = rnd((64, 3, 3, 3), 62, 0.2).cuda(); bias = rnd((64,), 63, 0.1).cuda()
     outs = {}
@@ -346,6 +372,7 @@ def test_first_exemplar_conv_quad_kernel_equals_the_per_pixel_kernel(hip, monkey
 @pytest.mark.parametrize("Cc", [256, 1])
 @pytest.mark.parametrize("tdt,code,tol", DT)
 def test_upsample2x_fwd_bwd(hip, Cc, tdt, code, tol, H, W):
+    hip = HP.library(tdt, hip)
     B = 2
     x = rnd((B, H, W, Cc), 24).to(tdt)
     xd = x.cuda()
@@ -356,6 +383,8 @@ def test_upsample2x_fwd_bwd(hip, Cc, tdt, code, tol, H, W):
     ref_t = torch.nn.functional.interpolate(x.double().permute(0, 3, 1, 2), scale_factor=2, mode="bilinear", align_corners=False)
     assert relerr(yr, ref_t) < 1e-12  # oracle restatement == torch semantics
     assert relerr(y, yr.permute(0, 2, 3, 1)) < tol
+    if code:
+        HP.assert_elementwise(y, yr.permute(0, 2, 3, 1), HP.BY_DTYPE[tdt], F32_TOL, "upsample2x")
     dy = rnd((B, 2 * H, 2 * W, Cc), 25).to(tdt)
     dx = torch.empty_like(xd)
     dyd = dy.cuda()
@@ -372,6 +401,7 @@ def test_upsample2x_chunk_kernel_equals_the_per_pixel_kernels(hip, monkeypatch, 
     instructions on per-lane indices), and both directions in an XCD-contiguous block order; same loads and arithmetic in the same order
     -- the outputs must be IDENTICAL to the per-pixel kernels' (COUNTR_UP2_ROWS=0, with and without the XCD order) and meet the
     oracle's tolerance."""
+    hip = HP.library(tdt, hip)
     Cc = 256
     x = rnd((B, H, W, Cc), 31).to(tdt).cuda()
     dy = rnd((B, 2 * H, 2 * W, Cc), 32).to(tdt).cuda()
@@ -400,6 +430,7 @@ def test_upsample2x_chunk_kernel_equals_the_per_pixel_kernels(hip, monkeypatch, 
 
 @pytest.mark.parametrize("tdt,code,tol", DT)
 def test_gelu_bwd_colsum(hip, tdt, code, tol):
+    hip = HP.library(tdt, hip)
     M, N = 1152, 2048
     pre = rnd((M, N), 26, 1.5).to(tdt)
     dh = rnd((M, N), 27).to(tdt)
@@ -417,6 +448,7 @@ def test_gelu_bwd_colsum(hip, tdt, code, tol):
 
 @pytest.mark.parametrize("tdt,code,tol", DT)
 def test_conv_dgrad_via_permuted_weights(hip, tdt, code, tol):
+    hip = HP.library(tdt, hip)
     # cast_permute mode 1 (OHWI) feeds the forward conv; mode 2 (dgrad form) turns dgrad into a forward conv
     B, H, W, Ci, Co = 2, 12, 12, 128, 256
     w = rnd((Co, Ci, 3, 3), 28, 0.05)
@@ -425,7 +457,13 @@ def test_conv_dgrad_via_permuted_weights(hip, tdt, code, tol):
     w_d = torch.empty((Ci, 9, Co), device="cuda", dtype=tdt)
     _lib.check(hip.countr_cast_permute(P(wd), P(w_f), w.numel(), 1, Co, Ci, 9, code, st()))
     _lib.check(hip.countr_cast_permute(P(wd), P(w_d), w.numel(), 2, Co, Ci, 9, code, st()))
-    assert relerr(w_f, w.permute(0, 2, 3, 1).reshape(Co, 9, Ci)) < 5e-3
+    assert relerr(w_f, w.permute(0, 2, 3, 1).reshape(Co, 9, Ci)) < (HP.bar(tdt, 5e-3) if code else 5e-3)
+    if code:            # a cast computes nothing: no floor.  Mode 2 is [Ci][8 - tap][Co] (countr_conv_shadows' dgrad form)
+        HP.assert_elementwise(w_f, w.permute(0, 2, 3, 1).reshape(Co, 9, Ci), HP.BY_DTYPE[tdt], 0.0, "cast_permute mode 1")
+        HP.assert_elementwise(w_d, w.reshape(Co, Ci, 9).flip(2).permute(1, 2, 0), HP.BY_DTYPE[tdt], 0.0, "cast_permute mode 2")
+        flat = torch.empty(w.numel(), device="cuda", dtype=tdt)
+        _lib.check(hip.countr_cast_permute(P(wd), P(flat), w.numel(), 0, 0, 0, 0, code, st()))
+        HP.assert_elementwise(flat, w.reshape(-1), HP.BY_DTYPE[tdt], 0.0, "cast_permute mode 0")
     dy = rnd((B, H, W, Co), 29).to(tdt)
     dyd = dy.cuda()
     dx = torch.empty((B * H * W, Ci), device="cuda", dtype=torch.float32)
@@ -443,6 +481,14 @@ def test_conv_dgrad_via_permuted_weights(hip, tdt, code, tol):
 
 
 def test_masked_mse_and_adamw(hip):
+    _masked_mse_and_adamw(hip, HP.BF16)
+
+
+def test_masked_mse_and_adamw_fp16():
+    _masked_mse_and_adamw(HP.library(HP.FP16), HP.FP16)
+
+
+def _masked_mse_and_adamw(hip, fl):
     B, HW = 3, 384 * 384
     g = torch.Generator().manual_seed(30)
     pred = torch.rand((B, HW), generator=g); gt = torch.rand((B, HW), generator=g)
@@ -465,7 +511,7 @@ def test_masked_mse_and_adamw(hip):
     n, n0 = 100003, 60000
     p0 = rnd((n,), 31); p = p0.cuda().clone()
     m = torch.zeros(n, device="cuda"); v = torch.zeros(n, device="cuda")
-    shadow = torch.empty(n, device="cuda", dtype=torch.bfloat16)
+    shadow = torch.empty(n, device="cuda", dtype=fl.dtype)
     gn = torch.zeros(hip.countr_adamw_gnorm_floats(), device="cuda")
     ta, tb = torch.nn.Parameter(p0[:n0].double().clone()), torch.nn.Parameter(p0[n0:].double().clone())
     opt = torch.optim.AdamW([{"params": [ta], "weight_decay": 0.05}, {"params": [tb], "weight_decay": 0.0}], lr=1e-3, betas=(0.9, 0.95), eps=1e-8)
@@ -500,6 +546,7 @@ def test_masked_mse_and_adamw(hip):
         want = gsteps[:n0].double().pow(2).sum() + (gsteps[n0:].double().pow(2).sum() if b_has else 0.0)
         assert abs(gn[0].item() - want.sqrt().item()) < 1e-5 * want.sqrt().item(), step
     assert relerr(shadow, pr_) < 5e-3
+    assert torch.equal(shadow, p.to(fl.dtype))       # the shadow IS the rounding of the stored parameter
     # scalar form (no device hyper): every range uses `step`
     p2 = p0.cuda().clone(); m2 = torch.zeros(n, device="cuda"); v2 = torch.zeros(n, device="cuda")
     g1 = rnd((n,), 77)
@@ -510,14 +557,31 @@ def test_masked_mse_and_adamw(hip):
     assert relerr(p2, torch.cat([a, b])) < 1e-5
 
 
-@pytest.mark.parametrize("B,N,H,dh", [(2, 576, 12, 64), (2, 576, 16, 32), (1, 200, 3, 64), (1, 64, 2, 32), (2, 729, 16, 32)])
+# fused attention: max-norm bars per flavour.  bf16: P and the output are rounded to 2^-9; fp16: the bars of tests/test_fp16_gpu.py
+FA_OUT = {HP.BF16: 1.5e-2, HP.FP16: 2e-3}
+FA_GRAD = {HP.BF16: 2.5e-2, HP.FP16: 4e-3}
+FA_FWD_SHAPES = [(2, 576, 12, 64), (2, 576, 16, 32), (1, 200, 3, 64), (1, 64, 2, 32), (2, 729, 16, 32)]
+
+
+@pytest.mark.parametrize("B,N,H,dh", FA_FWD_SHAPES)
 def test_flash_attention_fwd(hip, B, N, H, dh):
     """Fused bf16 attention vs fp64 softmax(q k^T * scale) v on the same (bf16-representable) inputs, including a
     spiked key that forces the online-softmax rescale branch and ragged N (not a multiple of the 64-key tile)."""
-    qkv = rnd((B, N, 3, H, dh), 50, 1.0).to(torch.bfloat16)
+    _flash_attention_fwd(hip, HP.BF16, B, N, H, dh)
+
+
+@pytest.mark.parametrize("B,N,H,dh", FA_FWD_SHAPES)
+def test_flash_attention_fwd_fp16(B, N, H, dh):
+    """The same on the fp16 library, whose forward kernel is another algorithm: the running-max loop always (flash_attn_fwd.hip: NOMAX =
+    !COUNTR_HALF_FP16 -- an fp16 P overflows at 2^16).  Bars of tests/test_fp16_gpu.py: out 2e-3, lse 1e-4."""
+    _flash_attention_fwd(HP.library(HP.FP16), HP.FP16, B, N, H, dh)
+
+
+def _flash_attention_fwd(hip, fl, B, N, H, dh):
+    qkv = rnd((B, N, 3, H, dh), 50, 1.0).to(fl.dtype)
     qkv[0, N // 2, 1, 0] = 6.0  # one key with large logits against every query -> running max jumps mid-sequence
     qd = qkv.cuda()
-    out = torch.empty((B, N, H * dh), device="cuda", dtype=torch.bfloat16)
+    out = torch.full((B, N, H * dh), float("nan"), device="cuda", dtype=fl.dtype)
     lse = torch.empty((B, H, N), device="cuda")
     scale = dh ** -0.5
     _lib.check(hip.countr_attn_fwd(P(qd), P(out), P(lse), B, N, H, dh, scale, st()))
@@ -525,44 +589,72 @@ def test_flash_attention_fwd(hip, B, N, H, dh):
     v = qkv[:, :, 2].double().permute(0, 2, 1, 3)
     sc = (q @ k.transpose(-1, -2)) * scale
     ref = (torch.softmax(sc, -1) @ v).permute(0, 2, 1, 3).reshape(B, N, H * dh)
-    assert relerr(out, ref) < 1.5e-2   # bf16 P and bf16 output rounding
+    assert torch.isfinite(out.float()).all()
+    assert relerr(out, ref) < FA_OUT[fl]   # P and output rounding
     assert relerr(lse, torch.logsumexp(sc, -1)) < 1e-4
 
 
-@pytest.mark.parametrize("B,N,H", [(2, 576, 12), (1, 64, 3), (1, 1088, 2)])
+FA_PRE_SHAPES = [(2, 576, 12), (1, 64, 3), (1, 1088, 2)]
+
+
+@pytest.mark.parametrize("B,N,H", FA_PRE_SHAPES)
+def test_flash_attention_fwd_prescaled_q_fp16(B, N, H):
+    _flash_attention_fwd_prescaled_q(HP.library(HP.FP16), HP.FP16, B, N, H)
+
+
+@pytest.mark.parametrize("B,N,H", FA_PRE_SHAPES)
 def test_flash_attention_fwd_prescaled_q(hip, B, N, H):
     """scale <= 0: q arrives multiplied by dh^-0.5 * log2(e) (rounded once to bf16, as the engine packs the frozen encoder's q
     projection); the kernel works in the exp2 domain with accumulators started at -m_ref.  Reference in fp64 on the SAME bf16
     inputs: softmax over 2^(q' k).  A spiked key forces the rescale branch (which must also shift the pending next-tile scores)."""
+    _flash_attention_fwd_prescaled_q(hip, HP.BF16, B, N, H)
+
+
+def _flash_attention_fwd_prescaled_q(hip, fl, B, N, H):
     dh = 64
     c = dh ** -0.5 * 1.4426950408889634
     qkv = rnd((B, N, 3, H, dh), 52, 1.0)
     qkv[0, N // 2, 1, 0] = 6.0
     qkv[0, N - 3, 1, H - 1] = -5.0
     qkv[:, :, 0] *= c
-    qkv = qkv.to(torch.bfloat16)
+    qkv = qkv.to(fl.dtype)
     qd = qkv.cuda()
-    out = torch.full((B, N, H * dh), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = torch.full((B, N, H * dh), float("nan"), device="cuda", dtype=fl.dtype)
     lse = torch.empty((B, H, N), device="cuda")
     _lib.check(hip.countr_attn_fwd(P(qd), P(out), P(lse), B, N, H, dh, 0.0, st()))
     q = qkv[:, :, 0].double().permute(0, 2, 1, 3); k = qkv[:, :, 1].double().permute(0, 2, 1, 3)
     v = qkv[:, :, 2].double().permute(0, 2, 1, 3)
     sc = (q @ k.transpose(-1, -2)) * 0.6931471805599453
     ref = (torch.softmax(sc, -1) @ v).permute(0, 2, 1, 3).reshape(B, N, H * dh)
-    assert relerr(out, ref) < 1.5e-2
+    assert torch.isfinite(out.float()).all()
+    assert relerr(out, ref) < FA_OUT[fl]
     assert relerr(lse, torch.logsumexp(sc, -1)) < 1e-4
     # unsupported shapes are refused, not silently computed with another scale
     assert hip.countr_attn_fwd(P(qd), P(out), P(lse), B, N, H * 2, 32, 0.0, st()) != 0
 
 
-@pytest.mark.parametrize("N,H,dh,pre,spike", [(576, 12, 64, False, 40.0), (576, 12, 64, True, 40.0), (576, 12, 64, True, 250.0), (576, 16, 32, False, 60.0),
-                                              (200, 3, 64, False, 60.0), (288, 12, 64, False, 250.0)])
+FA_FAR = [(576, 12, 64, False, 40.0), (576, 12, 64, True, 40.0), (576, 12, 64, True, 250.0), (576, 16, 32, False, 60.0),
+          (200, 3, 64, False, 60.0), (288, 12, 64, False, 250.0)]
+
+
+@pytest.mark.parametrize("N,H,dh,pre,spike", FA_FAR)
+def test_flash_attention_fwd_scores_far_above_the_first_key_tile_fp16(N, H, dh, pre, spike):
+    """The fp16 library has no fast path: every strip runs the running-max loop, on which these rows jump by tens to hundreds of log2
+    units behind the first tile and P must stay below fp16's 2^16."""
+    _flash_attention_fwd_far_above(HP.library(HP.FP16), HP.FP16, N, H, dh, pre, spike)
+
+
+@pytest.mark.parametrize("N,H,dh,pre,spike", FA_FAR)
 def test_flash_attention_fwd_scores_far_above_the_first_key_tile(hip, N, H, dh, pre, spike):
     """Round 6: the bf16 kernel's steady state keeps the FIRST key tile's row max as the softmax reference (no running max: a later score
     d above it just makes P 2^d, exact while nothing overflows); every lane checks l < 2^64 and O finite at the end and a workgroup with
     a miss runs its strip again on the exact running-max loop.  Here keys behind the first tile score tens (spike 40 / 60) to hundreds
     (250: exp2 overflows to inf on the fast path) of log2 units above it for some query rows of ONE (batch, head) -- above AND below, the
     scores are signed -- while the other heads stay ordinary: both paths inside one launch, each against fp64."""
+    _flash_attention_fwd_far_above(hip, HP.BF16, N, H, dh, pre, spike)
+
+
+def _flash_attention_fwd_far_above(hip, fl, N, H, dh, pre, spike):
     B = 2
     c = dh ** -0.5 * 1.4426950408889634
     qkv = rnd((B, N, 3, H, dh), 57, 1.0)
@@ -573,9 +665,9 @@ def test_flash_attention_fwd_scores_far_above_the_first_key_tile(hip, N, H, dh, 
     qkv[1, N - 1, 1, H - 1] = spike * sign                  # ... and the very last key of another (batch, head)
     if pre:
         qkv[:, :, 0] *= c
-    qkv = qkv.to(torch.bfloat16)
+    qkv = qkv.to(fl.dtype)
     qd = qkv.cuda()
-    out = torch.full((B, N, H * dh), float("nan"), device="cuda", dtype=torch.bfloat16)
+    out = torch.full((B, N, H * dh), float("nan"), device="cuda", dtype=fl.dtype)
     lse = torch.empty((B, H, N), device="cuda")
     _lib.check(hip.countr_attn_fwd(P(qd), P(out), P(lse), B, N, H, dh, 0.0 if pre else dh ** -0.5, st()))
     q = qkv[:, :, 0].double().permute(0, 2, 1, 3); k = qkv[:, :, 1].double().permute(0, 2, 1, 3)
@@ -585,21 +677,65 @@ def test_flash_attention_fwd_scores_far_above_the_first_key_tile(hip, N, H, dh, 
     assert (top > 64).sum() > 8 and (top < 1).sum() > 8        # rows that need the exact path, rows that do not
     ref = (torch.softmax(sc, -1) @ v).permute(0, 2, 1, 3).reshape(B, N, H * dh)
     assert torch.isfinite(out.float()).all()
-    assert relerr(out, ref) < 1.5e-2
+    assert relerr(out, ref) < FA_OUT[fl]
     assert relerr(lse, torch.logsumexp(sc, -1)) < 1e-4
 
 
-@pytest.mark.parametrize("B,N,H,dh", [(2, 576, 16, 32), (1, 576, 12, 64), (1, 200, 3, 32), (2, 64, 2, 64)])
+@pytest.mark.parametrize("N,H,dh", [(200, 3, 64), (729, 16, 32)])
+def test_flash_attention_fwd_fp16_spike_on_the_last_key_of_a_ragged_sequence(N, H, dh):
+    """fp16 library only (its forward is the running-max loop): in ONE head the very last key of a ragged sequence (N % 64 = 8 and 25)
+    scores 40 dh^-0.5 |q|_1-ish above everything for the query rows on one side of a sign pattern -- their running max jumps on the
+    final PARTIAL key tile, and the O accumulated over every earlier tile must be rescaled there -- while key 10 (first tile) carries
+    the mirrored pattern, so the other rows of the same head have their maximum in the first tile and never rescale afterwards."""
+    hip, fl, B = HP.library(HP.FP16), HP.FP16, 2
+    qkv = rnd((B, N, 3, H, dh), 59, 1.0)
+    sign = (torch.randint(0, 2, (dh,), generator=torch.Generator().manual_seed(60)) * 2 - 1).float()
+    qkv[0, N - 1, 1, 1] = 40.0 * sign
+    qkv[0, 10, 1, 1] = -6.0 * sign
+    qkv = qkv.to(fl.dtype)
+    qd = qkv.cuda()
+    out = torch.full((B, N, H * dh), float("nan"), device="cuda", dtype=fl.dtype)
+    lse = torch.empty((B, H, N), device="cuda")
+    _lib.check(hip.countr_attn_fwd(P(qd), P(out), P(lse), B, N, H, dh, dh ** -0.5, st()))
+    q = qkv[:, :, 0].double().permute(0, 2, 1, 3); k = qkv[:, :, 1].double().permute(0, 2, 1, 3)
+    v = qkv[:, :, 2].double().permute(0, 2, 1, 3)
+    sc = (q @ k.transpose(-1, -2)) * dh ** -0.5
+    arg = sc[0, 1].argmax(-1)
+    jump = (sc[0, 1, :, N - 1] - sc[0, 1, :, :N - 1].max(-1).values) * 1.4426950408889634
+    assert ((arg == N - 1) & (jump > 16)).sum() > 8 and (arg < 64).sum() > 8       # rows that rescale on the last tile, rows that never do
+    ref = (torch.softmax(sc, -1) @ v).permute(0, 2, 1, 3).reshape(B, N, H * dh)
+    assert torch.isfinite(out.float()).all()
+    assert relerr(out, ref) < FA_OUT[fl]
+    assert relerr(lse, torch.logsumexp(sc, -1)) < 1e-4
+    # the rows in question on their own: the max norm above is set by whichever head is largest
+    rows = (arg == N - 1).nonzero().reshape(-1)
+    o1, r1 = out[0, rows, dh:2 * dh], ref[0, rows, dh:2 * dh]
+    assert relerr(o1, r1) < FA_OUT[fl]
+
+
+FA_BWD_SHAPES = [(2, 576, 16, 32), (1, 576, 12, 64), (1, 200, 3, 32), (2, 64, 2, 64)]
+
+
+@pytest.mark.parametrize("B,N,H,dh", FA_BWD_SHAPES)
+def test_flash_attention_bwd_fp16(B, N, H, dh):
+    _flash_attention_bwd(HP.library(HP.FP16), HP.FP16, B, N, H, dh)
+
+
+@pytest.mark.parametrize("B,N,H,dh", FA_BWD_SHAPES)
 def test_flash_attention_bwd(hip, B, N, H, dh):
     """Fused attention backward (dq, dk, dv in one packed tensor) vs fp64 autograd of softmax(q k^T * scale) v."""
-    qkv = (rnd((B, N, 3, H, dh), 60, 1.0)).to(torch.bfloat16)
+    _flash_attention_bwd(hip, HP.BF16, B, N, H, dh)
+
+
+def _flash_attention_bwd(hip, fl, B, N, H, dh):
+    qkv = (rnd((B, N, 3, H, dh), 60, 1.0)).to(fl.dtype)
     qkv[0, N // 3, 1, 0] = 5.0
-    do = rnd((B, N, H * dh), 61, 1.0).to(torch.bfloat16)
+    do = rnd((B, N, H * dh), 61, 1.0).to(fl.dtype)
     qd, dod = qkv.cuda(), do.cuda()
-    out = torch.empty((B, N, H * dh), device="cuda", dtype=torch.bfloat16)
+    out = torch.empty((B, N, H * dh), device="cuda", dtype=fl.dtype)
     lse = torch.empty((B, H, N), device="cuda")
     delta = torch.empty((B, H, N), device="cuda")
-    dqkv = torch.full((B, N, 3, H, dh), float("nan"), device="cuda", dtype=torch.bfloat16)
+    dqkv = torch.full((B, N, 3, H, dh), float("nan"), device="cuda", dtype=fl.dtype)
     scale = dh ** -0.5
     _lib.check(hip.countr_attn_fwd(P(qd), P(out), P(lse), B, N, H, dh, scale, st()))
     _lib.check(hip.countr_attn_bwd(P(qd), P(out), P(dod), P(lse), P(delta), P(dqkv), B, N, H, dh, scale, st()))
@@ -609,15 +745,16 @@ def test_flash_attention_bwd(hip, B, N, H, dh):
     ref.backward(do.double())
     assert torch.isfinite(dqkv.float()).all()
     for slot, name in enumerate(("dq", "dk", "dv")):
-        assert relerr(dqkv[:, :, slot], x.grad[:, :, slot]) < 2.5e-2, name   # bf16 P/dS operands and bf16 outputs
+        assert relerr(dqkv[:, :, slot], x.grad[:, :, slot]) < FA_GRAD[fl], name   # 16-bit P/dS operands and 16-bit outputs
 
 
-@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32, torch.float16])
 def test_conv_shadows_permutations(hip, dt):
     """countr_conv_shadows: torch OIHW conv weights -> the forward operand [Co][tap][Ci] (OHWI) and the dgrad operand
     [Ci][8 - tap][Co] (transposed, taps reversed: the flipped kernel of the transposed convolution), several convolutions per
     launch, ragged channel counts included (tiles are 32 x 32)."""
     import ctypes as C
+    hip = HP.library(dt, hip)
     shapes = [(256, 512), (128, 64), (40, 24), (33, 65)]
     ws = [torch.randn(co, ci, 3, 3, device="cuda") for co, ci in shapes]
     wf = [torch.full((co, 9, ci), float("nan"), device="cuda", dtype=dt) for co, ci in shapes]
@@ -625,7 +762,7 @@ def test_conv_shadows_permutations(hip, dt):
     n = len(shapes)
     vp, ip = C.c_void_p * n, C.c_int * n
     _lib.check(hip.countr_conv_shadows(n, vp(*[w.data_ptr() for w in ws]), vp(*[w.data_ptr() for w in wf]), vp(*[w.data_ptr() for w in wd]),
-                                       ip(*[s[0] for s in shapes]), ip(*[s[1] for s in shapes]), ip(*[9] * n), 1 if dt == torch.bfloat16 else 0,
+                                       ip(*[s[0] for s in shapes]), ip(*[s[1] for s in shapes]), ip(*[9] * n), 0 if dt == torch.float32 else 1,
                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)), "conv_shadows")
     torch.cuda.synchronize()
     for w, f, d in zip(ws, wf, wd):
@@ -638,13 +775,21 @@ def test_conv_shadows_permutations(hip, dt):
 def test_conv_shadows_transposes_linear_weights(hip):
     """taps = 1, wf = NULL: the entry is an nn.Linear weight [N][K] and wd receives its bf16 transpose [K][N] (the B operand of the
     (ROW, ROW) input-gradient GEMM); 20 weights in one launch beside a 3x3 convolution (the table holds up to 32)."""
+    _conv_shadows_transposes_linear_weights(hip, torch.bfloat16)
+
+
+def test_conv_shadows_transposes_linear_weights_fp16():
+    _conv_shadows_transposes_linear_weights(HP.library(HP.FP16), torch.float16)
+
+
+def _conv_shadows_transposes_linear_weights(hip, h16):
     import ctypes as C
     lin = [(512, 512), (1536, 512), (2048, 512), (512, 2048), (40, 24)] * 4
     ws = [torch.randn(n, k, device="cuda") for n, k in lin]
-    wt = [torch.full((k, n), float("nan"), device="cuda", dtype=torch.bfloat16) for n, k in lin]
+    wt = [torch.full((k, n), float("nan"), device="cuda", dtype=h16) for n, k in lin]
     cw = torch.randn(64, 32, 3, 3, device="cuda")
-    cf = torch.full((64, 9, 32), float("nan"), device="cuda", dtype=torch.bfloat16)
-    cd = torch.full((32, 9, 64), float("nan"), device="cuda", dtype=torch.bfloat16)
+    cf = torch.full((64, 9, 32), float("nan"), device="cuda", dtype=h16)
+    cd = torch.full((32, 9, 64), float("nan"), device="cuda", dtype=h16)
     n = len(lin) + 1
     vp, ip = C.c_void_p * n, C.c_int * n
     _lib.check(hip.countr_conv_shadows(n, vp(*([w.data_ptr() for w in ws] + [cw.data_ptr()])), vp(*([None] * len(lin) + [cf.data_ptr()])),
@@ -653,15 +798,23 @@ def test_conv_shadows_transposes_linear_weights(hip):
                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)), "conv_shadows")
     torch.cuda.synchronize()
     for w, t in zip(ws, wt):
-        assert torch.equal(t, w.t().contiguous().to(torch.bfloat16))
-    assert torch.equal(cf, cw.reshape(64, 32, 9).permute(0, 2, 1).to(torch.bfloat16))
-    assert torch.equal(cd, cw.reshape(64, 32, 9).flip(2).permute(1, 2, 0).to(torch.bfloat16))
+        assert torch.equal(t, w.t().contiguous().to(h16))
+    assert torch.equal(cf, cw.reshape(64, 32, 9).permute(0, 2, 1).to(h16))
+    assert torch.equal(cd, cw.reshape(64, 32, 9).flip(2).permute(1, 2, 0).to(h16))
 
 
 def test_transpose16_many_matrices_one_launch(hip):
     """countr_transpose16 (ABI 8): the W^T shadows from the 16-bit shadow W -- 82 matrices of the MAE model's shapes (and 96, the table's
     size) in one launch, bit-identical to torch's transpose of the same 16-bit values and to what countr_conv_shadows (taps = 1) makes
     of the fp32 master; shapes that are not multiples of 64 and more than 96 matrices are refused."""
+    _transpose16_many_matrices_one_launch(hip, torch.bfloat16)
+
+
+def test_transpose16_many_matrices_one_launch_fp16():
+    _transpose16_many_matrices_one_launch(HP.library(HP.FP16), torch.float16)
+
+
+def _transpose16_many_matrices_one_launch(hip, h16):
     import ctypes as C
     shapes = ([(2304, 768), (768, 768), (3072, 768), (768, 3072)] * 12 + [(1536, 512), (512, 512), (2048, 512), (512, 2048)] * 8 + [(512, 768), (768, 512)])[:82]
     shapes += [(64, 64), (128, 192)] * 7
@@ -670,8 +823,8 @@ def test_transpose16_many_matrices_one_launch(hip):
     for n in (82, 96, 1):
         sh = shapes[:n]
         ws = [torch.randn(r, c, device="cuda") for r, c in sh]
-        w16 = [w.to(torch.bfloat16) for w in ws]
-        wt = [torch.full((c, r), float("nan"), device="cuda", dtype=torch.bfloat16) for r, c in sh]
+        w16 = [w.to(h16) for w in ws]
+        wt = [torch.full((c, r), float("nan"), device="cuda", dtype=h16) for r, c in sh]
         vp, ip = C.c_void_p * n, C.c_int * n
         _lib.check(hip.countr_transpose16(n, vp(*[w.data_ptr() for w in w16]), vp(*[w.data_ptr() for w in wt]), ip(*[s_[0] for s_ in sh]),
                                           ip(*[s_[1] for s_ in sh]), st), "transpose16")
@@ -680,15 +833,15 @@ def test_transpose16_many_matrices_one_launch(hip):
             assert torch.equal(t, w.t().contiguous())
         if n == 82:      # against the fp32 route, 32 at a time
             m = 32
-            old = [torch.full((c, r), float("nan"), device="cuda", dtype=torch.bfloat16) for r, c in sh[:m]]
+            old = [torch.full((c, r), float("nan"), device="cuda", dtype=h16) for r, c in sh[:m]]
             vpm, ipm = C.c_void_p * m, C.c_int * m
             _lib.check(hip.countr_conv_shadows(m, vpm(*[w.data_ptr() for w in ws[:m]]), vpm(*([None] * m)), vpm(*[w.data_ptr() for w in old]),
                                                ipm(*[s_[0] for s_ in sh[:m]]), ipm(*[s_[1] for s_ in sh[:m]]), ipm(*([1] * m)), 1, st), "conv_shadows")
             torch.cuda.synchronize()
             for a, b in zip(old, wt[:m]):
                 assert torch.equal(a, b)
-    a = torch.zeros(40, 64, device="cuda", dtype=torch.bfloat16)
-    b = torch.zeros(64, 40, device="cuda", dtype=torch.bfloat16)
+    a = torch.zeros(40, 64, device="cuda", dtype=h16)
+    b = torch.zeros(64, 40, device="cuda", dtype=h16)
     one_p, one_i = C.c_void_p * 1, C.c_int * 1
     assert hip.countr_transpose16(1, one_p(a.data_ptr()), one_p(b.data_ptr()), one_i(40), one_i(64), st) != 0
     assert b"multiples of 64" in hip.countr_last_error()

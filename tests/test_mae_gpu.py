@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.nn as nn
 
+import halfprec as HP
 from oracle import mae_ref as M
 from oracle import weights as W
 
@@ -34,22 +35,36 @@ def build(name, precision, seed=0, norm_pix_loss=False):
 
 
 # ---------------------------------------------------------------- kernels
-@pytest.mark.parametrize("sdt,ddt", [(0, 0), (0, 1), (1, 1), (1, 0)])
+GATHER_DTYPES = [(0, 0), (0, 1), (1, 1), (1, 0)]
+
+
+@pytest.mark.parametrize("sdt,ddt", GATHER_DTYPES)
 def test_gather_rows(hip, sdt, ddt):
+    _gather_rows(hip, HP.BF16, sdt, ddt)
+
+
+@pytest.mark.parametrize("sdt,ddt", GATHER_DTYPES)
+def test_gather_rows_fp16(sdt, ddt):
+    _gather_rows(HP.library(HP.FP16), HP.FP16, sdt, ddt)
+
+
+def _gather_rows(hip, fl, sdt, ddt):
     g = torch.Generator().manual_seed(1)
     rows_src, rows, cols = 300, 700, 512
     src = torch.randn(rows_src, cols, generator=g)
     idx = torch.randint(-1, rows_src, (rows,), generator=g, dtype=torch.int32)
     dflt, add = torch.randn(cols, generator=g), torch.randn(64, cols, generator=g)
-    s = (src.bfloat16() if sdt else src).cuda()
-    out = torch.empty(rows, cols, device="cuda", dtype=torch.bfloat16 if ddt else torch.float32)
+    s = (src.to(fl.dtype) if sdt else src).cuda()
+    out = torch.empty(rows, cols, device="cuda", dtype=fl.dtype if ddt else torch.float32)
     assert hip.countr_gather_rows(s.data_ptr(), idx.cuda().data_ptr(), out.data_ptr(), dflt.cuda().data_ptr(), add.cuda().data_ptr(), 64,
                                   rows, cols, sdt, ddt, _s()) == 0
     sv = s.float().cpu()
     ref = torch.where((idx >= 0).unsqueeze(1), sv[idx.clamp(min=0).long()], dflt.unsqueeze(0)) + add[torch.arange(rows) % 64]
-    if ddt:
-        ref = ref.bfloat16().float()
-    assert torch.equal(out.float().cpu(), ref)   # a gather is exact (bf16 output: one RNE rounding of the exact sum)
+    if ddt:       # one rounding of the fp32 sum, every element within an ulp of the EXACT sum (no floor: nothing else is computed)
+        exact = torch.where((idx >= 0).unsqueeze(1), sv[idx.clamp(min=0).long()], dflt.unsqueeze(0)).double() + add[torch.arange(rows) % 64].double()
+        HP.assert_elementwise(out, exact, fl, 0.0, "gather_rows")
+        ref = ref.to(fl.dtype).float()
+    assert torch.equal(out.float().cpu(), ref)   # a gather is exact (16-bit output: one RNE rounding of the exact sum)
     # identity / no default / no add
     out2 = torch.empty(rows_src, cols, device="cuda")
     assert hip.countr_gather_rows(src.cuda().data_ptr(), None, out2.data_ptr(), None, None, 0, rows_src, cols, 0, 0, _s()) == 0
