@@ -49,8 +49,10 @@ def bar(flavour_or_dtype, bf16_bar):
 
 def elementwise_excess(out, ref, flavour, floor):
     """max over ALL elements of |out - ref| - (2 u |ref| + tiny + floor max|ref|), in fp64: <= 0 means the bound holds everywhere.
-    A non-finite element of `out` where `ref` is finite (or the reverse) gives +inf; equal infinities and NaN against NaN pass."""
-    o, r = out.detach().double().cpu().reshape(-1), ref.detach().double().cpu().reshape(-1)
+    A non-finite element of `out` where `ref` is finite (or the reverse) gives +inf; equal infinities and NaN against NaN pass.
+    Computed where `out` lives (the same fp64 operations: a 19 M-element head map stays on the GPU)."""
+    o = out.detach().double().reshape(-1)
+    r = ref.detach().double().reshape(-1).to(o.device)
     assert o.shape == r.shape, (out.shape, ref.shape)
     fin = torch.isfinite(r)
     same = (o == r) | (torch.isnan(o) & torch.isnan(r))

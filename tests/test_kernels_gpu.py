@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import halfprec as HP
+import stagecheck as SC
 from countr_amd import _lib
 from oracle import countr_ref as R
 
@@ -138,6 +139,49 @@ def test_groupnorm_relu_fwd_bwd(hip, HW, tdt, code, tol):
     assert relerr(dw1, w1r.grad) < 2e-3 and relerr(db1, b1r.grad) < 1e-4
 
 
+@pytest.mark.parametrize("HW", [576, 35 * 35, 100])
+@pytest.mark.parametrize("tdt,code,tol", DT)
+def test_groupnorm_relu_bwd_engine_form_leaves_per_image_sums(hip, HW, tdt, code, tol):
+    """countr_groupnorm_relu_bwd as the engine calls it: dgamma = dbeta = dw1 = NULL, the parameter gradients are finished elsewhere from
+    the per-image sums [B][3][256] = {sum g, sum g xhat, sum d1 y} that the finalize pass leaves at
+    countr_groupnorm_bwd_image_sums_offset(B, HW) -- the plain call and the fused 1x1-head call, against fp64 on the same x and (mean,
+    rstd), per image, at the 2e-3 of dg / db above; dx element-wise (16-bit) with the undecidable ReLU gates left out."""
+    hip = HP.library(tdt, hip)
+    B, Cc, G = 3, 256, 8
+    x = (rnd((B, HW, Cc), 81, 1.5) + 0.2).to(tdt).cuda()
+    g = (1 + 0.1 * rnd((Cc,), 82)).cuda(); b = (0.1 * rnd((Cc,), 83)).cuda()
+    dy = rnd((B, HW, Cc), 84).to(tdt).cuda()
+    w1 = (0.1 * rnd((Cc,), 85)).cuda(); d1 = rnd((B, HW), 86).cuda()
+    stats = torch.empty((B, G, 2), device="cuda")
+    wsf = torch.empty(B * 128 * 3 * Cc + 64 + 16 * B + B * 3 * Cc, device="cuda")
+    y = torch.empty_like(x)
+    _lib.check(hip.countr_groupnorm_relu_fwd(P(x), P(g), P(b), P(y), None, None, None, P(stats), P(wsf), B, HW, Cc, G, 1e-5, code, st()))
+    off = int(hip.countr_groupnorm_bwd_image_sums_offset(B, HW))
+    assert off == B * hip.countr_groupnorm_nsplit(HW) * 3 * Cc + 64 + 16 * B
+    for head in (False, True):
+        ws = torch.full((off + B * 3 * Cc,), float("nan"), device="cuda")
+        dx = torch.full((B, HW, Cc), float("nan"), device="cuda", dtype=tdt)
+        db1 = torch.zeros(1, device="cuda")
+        _lib.check(hip.countr_groupnorm_relu_bwd(P(x), None if head else P(dy), P(d1) if head else None, P(w1) if head else None, P(stats),
+                                                 P(g), P(b), P(dx), None, None, None, P(db1) if head else None, P(ws), B, HW, Cc, G, code, 0, st()))
+        torch.cuda.synchronize()
+        got = ws[off:].view(B, 3, Cc)
+        ref_dx, sums, near = SC.groupnorm_relu_bwd(x, stats, g, b, **(dict(d1=d1, w1=w1) if head else dict(dy=dy)))
+        assert bool(torch.isfinite(got).all())
+        for bi in range(B):
+            for plane in range(3 if head else 2):
+                assert relerr(got[bi, plane], sums[bi, plane]) < 2e-3, (head, bi, plane)
+        if not head:
+            assert not bool(got[:, 2].any())
+        else:
+            assert relerr(db1, d1.double().sum().reshape(1)) < 1e-4
+        keep = SC.gate_keep(near, "groupnorm bwd gates")
+        if code:
+            SC.assert_16bit(dx, ref_dx, HP.BY_DTYPE[tdt], "groupnorm bwd dx (engine form, head=%s)" % head, keep)
+        else:
+            assert relerr(dx.reshape(-1)[keep.reshape(-1)], ref_dx.reshape(-1)[keep.reshape(-1)]) < 5e-4
+
+
 @pytest.mark.parametrize("HW", [96 * 96, 48 * 48, 35 * 35, 100])
 def test_groupnorm_statistics_from_row_partials(hip, HW):
     """countr_groupnorm_relu_fwd_rows (ABI 9): the statistics pass reads {sum, sum of squares} per pixel and 32-channel group (what a
@@ -218,6 +262,39 @@ def test_instnorm_relu_pool(hip, H, Cc, avg, tdt, code, tol, use_ws):
         d, r = dx2.double().cpu().reshape(-1), xr.grad.permute(0, 2, 3, 1).reshape(-1)
         assert (d @ r / (d.norm() * r.norm())).item() > 0.995 and abs(d.norm().item() / r.norm().item() - 1) < 0.02
         assert hip.countr_instnorm_relu_pool_fwd(P(x32), P(y2), P(stats), S, H, H, Cc, avg, 1e-5, code, None, P(x32), 1, st()) != 0   # bf16 x-hat in place of an fp32 map: refused
+
+
+@pytest.mark.parametrize("use_ws", [False, True])
+@pytest.mark.parametrize("H,Cc,avg", [(64, 64, 0), (32, 128, 0), (16, 256, 0), (8, 512, 1), (40, 64, 0), (12, 128, 0)])
+@pytest.mark.parametrize("tdt,code,tol", DT)
+def test_instnorm_stored_xhat_path_element_wise(hip, H, Cc, avg, tdt, code, tol, use_ws):
+    """The only form the 16-bit engines use: an fp32 map in (x_f32), the rounded x-hat stored (xhat_out), the backward on the stored x-hat
+    (x_is_xhat).  The cosine comparison above has to allow for a reference on the unrounded map; here every output is compared with
+    fp64 ON WHAT THE KERNEL READ: statistics from the fp32 map, x-hat element-wise, the max-pooled y EQUAL to maxpool(relu(stored
+    x-hat)), the averaged y element-wise, and dx element-wise from the stored x-hat and rstd (gate and max-pool routing read stored
+    values: nothing is left out).  fp32: the same path with an fp32 x-hat, max-norm bars."""
+    hip = HP.library(tdt, hip)
+    S = 3
+    x = (rnd((S, H, H, Cc), 91, 1.3) + 0.1).cuda()          # fp32, not 16-bit exact: a convolution's output
+    oshape = (S, Cc) if avg else (S, H // 2, H // 2, Cc)
+    nan = lambda shape, dt: torch.full(shape, float("nan"), device="cuda", dtype=dt)
+    y, xh, stats = nan(oshape, tdt), nan((S, H, H, Cc), tdt), nan((S, Cc, 2), torch.float32)
+    ws = torch.empty(hip.countr_instnorm_workspace_floats(S, Cc), device="cuda") if use_ws else None
+    _lib.check(hip.countr_instnorm_relu_pool_fwd(P(x), P(y), P(stats), S, H, H, Cc, avg, 1e-5, code, P(ws), P(xh), int(code != 0), st()))
+    torch.cuda.synchronize()
+    sref = SC.instnorm_stats(x)
+    SC.assert_stats(stats, sref, "instnorm statistics")
+    one = (lambda out, ref, what: SC.assert_16bit(out, ref, HP.BY_DTYPE[tdt], what)) if code else SC.assert_f32
+    one(xh, SC.instnorm_xhat(x, sref), "stored x-hat")
+    if avg:
+        one(y, SC.avgpool(torch.relu(xh)), "mean(relu(x-hat))")
+    else:
+        assert torch.equal(y, SC.maxpool2(torch.relu(xh)))
+    dyp = rnd(oshape, 92).to(tdt).cuda()
+    dx = nan((S, H, H, Cc), tdt)
+    _lib.check(hip.countr_instnorm_relu_pool_bwd(P(xh), P(dyp), P(stats), P(dx), S, H, H, Cc, avg, code, P(ws), 1, st()))
+    torch.cuda.synchronize()
+    one(dx, SC.instnorm_relu_pool_bwd(xh, stats[..., 1], dyp, avg), "dx from the stored x-hat")
 
 
 @pytest.mark.parametrize("avg,H", [(1, 8), (0, 16)])
@@ -345,6 +422,30 @@ def test_im2patch_and_c3conv(hip, tdt, code, tol):
     _lib.check(hip.countr_conv3x3_c3_wgrad(P(bxd), P(dyd), P(dw), P(db), P(ws), S, 64, 64, code, 0, st()))
     yr.backward(dy.double().permute(0, 3, 1, 2))
     assert relerr(dw, wr.grad) < 1e-4 and relerr(db, br.grad) < 1e-4
+
+
+# pixels per block of conv3x3_c3_wgrad_kernel (512 blocks, 64-pixel tiles): 8 | 48 | 72 = the first range with a second, ragged tile (the
+# engine runs B * S = 6, 9, 24, 78 crops) | fewer pixels than blocks: empty blocks must contribute zeros
+@pytest.mark.parametrize("S,H,W", [(1, 64, 64), (6, 64, 64), (9, 64, 64), (3, 20, 12), (2, 5, 8)])
+@pytest.mark.parametrize("tdt,code,tol", DT)
+def test_first_exemplar_conv_wgrad_block_ranges_and_accumulation(hip, tdt, code, tol, S, H, W):
+    hip = HP.library(tdt, hip)
+    bx = torch.rand((S, 3, H, W), generator=torch.Generator().manual_seed(71))
+    dy = rnd((S, H, W, 64), 72).to(tdt)
+    wr, br = torch.zeros((64, 3, 3, 3), dtype=torch.float64, requires_grad=True), torch.zeros(64, dtype=torch.float64, requires_grad=True)
+    torch.nn.functional.conv2d(bx.double(), wr, br, padding=1).backward(dy.double().permute(0, 3, 1, 2))
+    bxd, dyd = bx.cuda(), dy.cuda()
+    nws = hip.countr_conv3x3_c3_wgrad_nblocks() * 64 * 28
+    dw0, db0 = rnd((64, 3, 3, 3), 73, float(wr.grad.abs().max())), rnd((64,), 74, float(br.grad.abs().max()))
+    for acc in (0, 1):
+        ws = torch.full((nws,), float("nan"), device="cuda")
+        dw = dw0.cuda() if acc else torch.full((64, 3, 3, 3), float("nan"), device="cuda")
+        db = db0.cuda() if acc else torch.full((64,), float("nan"), device="cuda")
+        _lib.check(hip.countr_conv3x3_c3_wgrad(P(bxd), P(dyd), P(dw), P(db), P(ws), S, H, W, code, acc, st()))
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(dw).all()) and bool(torch.isfinite(db).all()), acc
+        assert relerr(dw, wr.grad + (dw0.double() if acc else 0)) < 1e-4, acc
+        assert relerr(db, br.grad + (db0.double() if acc else 0)) < 1e-4, acc
 
 
 @pytest.mark.parametrize("S,H,W", [(24, 64, 64), (3, 20, 12), (2, 5, 8), (1, 64, 4)])
