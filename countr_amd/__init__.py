@@ -18,6 +18,9 @@ def __getattr__(name):
     if name in ("TileStitcher", "tiles_host", "tile_starts"):
         from . import tiles
         return getattr(tiles, name)
+    if name in ("YuvFrame", "YuvConverter", "yuv_host"):
+        from . import yuv
+        return getattr(yuv, name)
     if name in ("match_host", "PointMatcher", "localization_metrics", "LocalizationTotals"):
         from . import match
         return getattr(match, name)

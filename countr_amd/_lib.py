@@ -244,3 +244,42 @@ def tiles_check(rc, what=""):
 def tiles_exported_symbols():
     """Names declared in include/countr_hip_tiles.h, which are the names the tiles library exports."""
     return sorted(TILES_PROTOS)
+
+
+# ---- the yuv library: 4:2:0 decoder surfaces (NV12, NV21, I420, P010) converted to the packed RGB the raw-frame entry points take.
+# include/countr_hip_yuv.h is its one statement, in the same dialect; nothing of it enters the bindings above or this module's COUNTR_*
+# globals.
+YUV_LIB_PATH = os.environ.get("COUNTR_LIB_YUV", os.path.join(_HERE, "libcountr_hip_yuv.so"))
+YUV_HEADER = os.path.join(_HERE, "..", "include", "countr_hip_yuv.h")
+YUV_CONSTS, YUV_STRUCTS, YUV_PROTOS = parse_header(open(YUV_HEADER).read())
+_yuv = None
+
+
+def yuv_lib():
+    """Load (once) and return the ctypes handle of libcountr_hip_yuv.so, bound from its header; raises CountrError if it is not built or
+    was built from another version of the header."""
+    global _yuv
+    if _yuv is None:
+        if not os.path.exists(YUV_LIB_PATH):
+            raise CountrError(
+                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
+                "the HIP path has no CPU fallback" % os.path.basename(YUV_LIB_PATH))
+        L = C.CDLL(YUV_LIB_PATH)
+        for name, (restype, argtypes) in YUV_PROTOS.items():
+            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
+            fn.restype, fn.argtypes = restype, argtypes
+        if L.countr_yuv_version() != YUV_CONSTS["COUNTR_YUV_ABI_VERSION"]:
+            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
+                              % (os.path.basename(YUV_LIB_PATH), L.countr_yuv_version(), YUV_CONSTS["COUNTR_YUV_ABI_VERSION"]))
+        _yuv = L
+    return _yuv
+
+
+def yuv_check(rc, what=""):
+    if rc != 0:
+        raise CountrError("%s failed (rc=%d): %s" % (what or "countr_yuv call", rc, (yuv_lib().countr_yuv_last_error() or b"").decode()))
+
+
+def yuv_exported_symbols():
+    """Names declared in include/countr_hip_yuv.h, which are the names the yuv library exports."""
+    return sorted(YUV_PROTOS)

@@ -1,5 +1,5 @@
-"""Build libcountr_hip.so (all HIP kernels + the C ABI) and the extension libraries libcountr_hip_ext.so, libcountr_hip_classes.so and
-libcountr_hip_tiles.so in-tree for gfx950.
+"""Build libcountr_hip.so (all HIP kernels + the C ABI) and the extension libraries libcountr_hip_ext.so, libcountr_hip_classes.so,
+libcountr_hip_tiles.so and libcountr_hip_yuv.so in-tree for gfx950.
 
 hipcc cross-compiles without a GPU, so this runs in the build container and on the GPU box.
 The .so is git-ignored but travels with the repo snapshot to the GPU box.
@@ -48,6 +48,10 @@ CLASSES_HEADER = os.path.join(HERE, "..", "include", "countr_hip_classes.h")
 CSRC_TILES = os.path.join(HERE, "csrc_tiles")
 LIB_TILES = os.path.join(HERE, "libcountr_hip_tiles.so")
 TILES_HEADER = os.path.join(HERE, "..", "include", "countr_hip_tiles.h")
+# the yuv library (include/countr_hip_yuv.h), built the same way, from csrc_yuv/
+CSRC_YUV = os.path.join(HERE, "csrc_yuv")
+LIB_YUV = os.path.join(HERE, "libcountr_hip_yuv.so")
+YUV_HEADER = os.path.join(HERE, "..", "include", "countr_hip_yuv.h")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"]
 
 
@@ -63,14 +67,20 @@ def tiles_sources():
     return sorted(glob.glob(os.path.join(CSRC_TILES, "*.hip")))
 
 
+def yuv_sources():
+    return sorted(glob.glob(os.path.join(CSRC_YUV, "*.hip")))
+
+
 # the libraries built once, without a 16-bit twin: tag -> (library, sources, its header)
 SINGLE = {"ext": (LIB_EXT, ext_sources, EXT_HEADER), "classes": (LIB_CLASSES, classes_sources, CLASSES_HEADER),
           "tiles": (LIB_TILES, tiles_sources, TILES_HEADER)}
+# the same table for the libraries that came after SINGLE's keys were pinned; build() walks both
+SINGLE_LATER = {"yuv": (LIB_YUV, yuv_sources, YUV_HEADER)}
 
 
 def build(force=False, verbose=True):
     """Compile every csrc/*.hip for gfx950 and link libcountr_hip.so + libcountr_hip_f16.so, and every csrc_ext/*.hip into
-    libcountr_hip_ext.so, every csrc_classes/*.hip into libcountr_hip_classes.so, every csrc_tiles/*.hip into libcountr_hip_tiles.so.  An object is reused only if the record
+    libcountr_hip_ext.so, every csrc_classes/*.hip into libcountr_hip_classes.so, every csrc_tiles/*.hip into libcountr_hip_tiles.so, every csrc_yuv/*.hip into libcountr_hip_yuv.so.  An object is reused only if the record
     written when it was compiled (build/<variant>/<src>.o.sha256: content hash of the source, of every shared header and of the flags)
     still matches -- content, not mtime, so a snapshot copy or a checkout cannot make a stale object look fresh.  COUNTR_BUILD_FORCE=1
     (or force=True / --force) recompiles everything.  Prints how many objects were compiled."""
@@ -81,11 +91,12 @@ def build(force=False, verbose=True):
     procs, reused, total = [], 0, 0
     links = []
     jobs = int(os.environ.get("COUNTR_BUILD_JOBS", "0")) or max(2, (os.cpu_count() or 4))
-    for tag, lib, extra in VARIANTS + tuple((t, lib_, None) for t, (lib_, _s, _h) in SINGLE.items()):
+    single = dict(SINGLE, **SINGLE_LATER)
+    for tag, lib, extra in VARIANTS + tuple((t, lib_, None) for t, (lib_, _s, _h) in single.items()):
         bdir = os.path.join(HERE, "build", tag) if tag else os.path.join(HERE, "build")
         os.makedirs(bdir, exist_ok=True)
         objs, fresh = [], False
-        for src in sources() if extra is not None else SINGLE[tag][1]():
+        for src in sources() if extra is not None else single[tag][1]():
             obj = os.path.join(bdir, os.path.basename(src) + ".o")
             objs.append(obj)
             total += 1
@@ -94,7 +105,7 @@ def build(force=False, verbose=True):
             else:
                 cmd = ([hipcc] + FLAGS + ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] + extra
                        + EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj])
-            want = _digest([src] + (hdrs if extra is not None else shared + [SINGLE[tag][2]]), " ".join(cmd[1:-3]))
+            want = _digest([src] + (hdrs if extra is not None else shared + [single[tag][2]]), " ".join(cmd[1:-3]))
             rec = obj + ".sha256"
             if not force and os.path.exists(obj) and os.path.exists(rec) and open(rec).read().strip() == want:
                 reused += 1
@@ -123,9 +134,9 @@ def build(force=False, verbose=True):
             subprocess.check_call(cmd)
             open(lrec, "w").write(lwant + "\n")
     if verbose:
-        print("build_mode: %s -- %d of %d objects compiled (2 libraries x %d sources + %d of the extension library + %d of the classes library + %d of the tiles library), %d reused after a "
+        print("build_mode: %s -- %d of %d objects compiled (2 libraries x %d sources + %d of the extension library + %d of the classes library + %d of the tiles library + %d of the yuv library), %d reused after a "
               "content-hash check (source + headers + flags)"
-              % ("full" if reused == 0 else "incremental", len(procs), total, len(sources()), len(ext_sources()), len(classes_sources()), len(tiles_sources()), reused), flush=True)
+              % ("full" if reused == 0 else "incremental", len(procs), total, len(sources()), len(ext_sources()), len(classes_sources()), len(tiles_sources()), len(yuv_sources()), reused), flush=True)
     return LIB
 
 

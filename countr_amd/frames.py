@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, classes as classes_, inference, peaks, regions as regions_, tiles as tiles_
+from . import _lib, classes as classes_, inference, peaks, regions as regions_, tiles as tiles_, yuv as yuv_
 
 NEW_H = 384
 BOX = 64                    # exemplar crops are 64 x 64 (demo.py:67)
@@ -129,6 +129,7 @@ class FramePrep:
         self._slots = {}       # (H, W) -> [_Slot, ...]
         self._tmp = {}         # (H, W, out height) -> uint8 [n, H, out_w, 3]
         self._last = None      # (stream, event) of the previous prepare: a call on another stream waits for it before it reuses the buffers
+        self.yuv = None       # the YuvConverter of the YuvFrame items, made on first use
 
     def tables(self, in_size, out_size):
         t = self._tables.get((in_size, out_size))
@@ -156,10 +157,28 @@ class FramePrep:
         slot.copied.record(torch.cuda.current_stream(self.device))
         return slot.dev
 
+    def _convert_yuv(self, frames):
+        """frames with every YuvFrame replaced by its RGB device buffer.  The buffers are reused from call to call like the slots, so the
+        cross-stream guard of prepare() comes first."""
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            if self._last is not None and self._last[0] != cur:
+                cur.wait_event(self._last[1])
+            if self.yuv is None:
+                self.yuv = yuv_.YuvConverter(self.device)
+            idxs = [i for i, f in enumerate(frames) if isinstance(f, yuv_.YuvFrame)]
+            for i, rgb in zip(idxs, self.yuv.convert([frames[i] for i in idxs])):
+                frames[i] = rgb
+        return frames
+
     def prepare(self, frames, new_h=NEW_H):
         """frames: uint8 [H, W, 3] each (np.ndarray, CPU tensor or device tensor) -> [[1, 3, new_h, new_W] fp32 device tensors], each equal
-        to ToTensor(PIL resize((new_W, new_h), BILINEAR)) bit for bit.  Frames of one shape share launches (up to 16 per launch pair)."""
+        to ToTensor(PIL resize((new_W, new_h), BILINEAR)) bit for bit.  Frames of one shape share launches (up to 16 per launch pair).
+        A YuvFrame item (countr_amd/yuv.py) is first converted to RGB on the device, into a buffer of the YuvConverter this FramePrep
+        owns, and is from there on a device frame like any other."""
         new_h = int(new_h)
+        if any(isinstance(f, yuv_.YuvFrame) for f in frames):
+            frames = self._convert_yuv(list(frames))
         out = [None] * len(frames)
         by_shape = {}
         for i, f in enumerate(frames):

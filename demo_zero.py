@@ -19,8 +19,15 @@ regions_<stem>.json = {"count", "regions": {name: {"count", "area"}}} is written
 outlines.  It works together with --points.  `--zoom {2,3,4,auto}` counts from the image's own pixels (countr_amd.frames.count_frames
 with zoom=): the decoded image is resized on the device to height 384 k and covered by a 2-D grid of tiles (--band_stride: the row
 stride of the grid, --zoom_max: the largest k "auto" takes; without exemplar boxes "auto" is 1).  Counts, --points and their JSON
-work as before; viz_<name>.jpg is drawn from the zoomed image and map, at the zoomed size.  --regions_json is for --zoom 1.  demo.py is
-the few-shot counterpart (exemplar boxes)."""
+work as before; viz_<name>.jpg is drawn from the zoomed image and map, at the zoomed size.  --regions_json is for --zoom 1.
+`--yuv FORMAT:WxH[:MATRIX[:RANGE[:CHROMA]]]` counts a raw video clip: --input_path is then a file of consecutive packed frames (Y plane,
+then the chroma plane(s), no padding) in nv12, nv21, i420 or p010, as a decoder or `ffmpeg -f rawvideo` writes them; MATRIX is bt709
+(default) or bt601, RANGE limited (default) or full, CHROMA nearest (default) or linear.  The frames go to the device as they are --
+1.5 bytes a pixel -- and are converted there (countr_amd/yuv.py, include/countr_hip_yuv.h); p010 is reduced to 8 bits by that rule alone,
+without tone mapping.  --max_frames N reads the first N frames; an incomplete trailing frame is an error.  The frames are counted
+--group_images at a time through countr_amd.frames.count_frames, each prints `<stem>#<index>: Count: ... - Time: ...`, and
+viz_<stem>_<index>.jpg, points_<stem>_<index>.json and regions_<stem>_<index>.json are what they are for an image, the picture drawn
+from countr_amd.yuv_host of the frame.  demo.py is the few-shot counterpart (exemplar boxes)."""
 import json
 import time
 from argparse import ArgumentParser
@@ -32,7 +39,7 @@ import torch
 from PIL import Image, ImageDraw
 
 import models_mae_cross
-from countr_amd import frames, inference
+from countr_amd import frames, inference, yuv
 
 shot_num = 0
 
@@ -151,6 +158,77 @@ def save_visualisation(sample, density_map, pred_cnt, path, old_w, old_h, points
     im.save(path)
 
 
+def parse_yuv(spec):
+    """--yuv FORMAT:WxH[:MATRIX[:RANGE[:CHROMA]]] -> (W, H, YuvFrame keywords)."""
+    parts = spec.lower().split(":")
+    names = ("format", "matrix", "range", "chroma")
+    tables = (yuv.FORMATS, yuv.MATRICES, yuv.RANGES, yuv.CHROMAS)
+    try:
+        if not 2 <= len(parts) <= 5:
+            raise ValueError("FORMAT:WxH[:MATRIX[:RANGE[:CHROMA]]]")
+        w, h = (int(v) for v in parts[1].split("x"))
+        kw = dict(zip(names, parts[:1] + parts[2:]))
+        for (name, value), table in zip(kw.items(), tables):
+            if value not in table:
+                raise ValueError("%s is one of %s" % (name, ", ".join(table)))
+        if not (1 <= w <= yuv.MAX_SIDE and 1 <= h <= yuv.MAX_SIDE):
+            raise ValueError("W and H are 1..%d" % yuv.MAX_SIDE)
+    except ValueError as e:
+        raise SystemExit("--yuv %s: %s" % (spec, e))
+    return w, h, kw
+
+
+def read_clip(path, w, h, kw, max_frames=None):
+    """The packed frames of a raw clip as YuvFrame views of one host array."""
+    size = yuv.frame_bytes(kw["format"], w, h)
+    total = path.stat().st_size
+    if total == 0 or total % size:
+        raise SystemExit("%s: %d bytes are %d frames of %d bytes (%s %dx%d) and an incomplete frame of %d bytes"
+                         % (path, total, total // size, size, kw["format"], w, h, total % size))
+    n = total // size if max_frames is None else min(total // size, max_frames)
+    data = np.fromfile(path, dtype=np.uint8, count=n * size)
+    return [yuv.YuvFrame.from_buffer(data[k * size:(k + 1) * size], w, h, **kw) for k in range(n)]
+
+
+def run_yuv(args, model, device, zoom, region_names, polygons, clip):
+    """--yuv: the clip's frames, --group_images at a time, through frames.count_frames on YuvFrame views."""
+    h, w, _ = clip[0].shape
+    stem = args.input_path.stem
+    prep = frames.frame_prep(device)
+    group = max(args.group_images, 1)
+    for g0 in range(0, len(clip), group):
+        raw = clip[g0:g0 + group]
+        t0 = time.perf_counter()
+        if zoom != 1:
+            got = count_zoomed(model, raw, None, zoom, args, False)
+        else:
+            results = frames.count_frames(model, raw, normalization=False)
+            located = [(None, None, None)] * len(raw)
+            if args.points:
+                located = frames.locate_maps(results, [(w, h)] * len(raw), radius=args.points_radius, rel_threshold=args.points_rel_threshold,
+                                             keep=args.points_keep)
+            summed = [None] * len(raw)
+            if polygons is not None:
+                summed = frames.region_maps(results, [(w, h)] * len(raw), None, frames.frame_regions(polygons, [(w, h)] * len(raw)))
+            torch.cuda.synchronize()
+            got = [(c, dm, pts, score, total, None, 1) for (c, dm), (pts, score, total) in zip(results, located)]
+        dt = (time.perf_counter() - t0) / len(raw)
+        for k, (f, (pred_cnt, dm, pts, score, total, sample, zk)) in enumerate(zip(raw, got)):
+            name = "%s_%d" % (stem, g0 + k)
+            if pts is not None:
+                write_points(args.output_path / ("points_%s.json" % name), pred_cnt, total, pts, score)
+            if not args.no_viz:
+                if zk == 1:                 # the picture of the frame: the rule on the host, resized as the model saw it
+                    sample = prep.prepare([yuv.yuv_host(f)])[0][0]
+                vw, vh = (sample.shape[2], sample.shape[1]) if zk > 1 else (w, h)
+                save_visualisation(sample, dm.float(), pred_cnt, args.output_path / ("viz_%s.jpg" % name), vw, vh,
+                                   points=points_on(pts, w, h, vw, vh) if pts is not None else None, regions=polygons if zk == 1 else None)
+            print("%s#%d: Count: %s - Time: %s" % (stem, g0 + k, pred_cnt, dt))
+            if zoom == 1 and polygons is not None:
+                reg = summed[k]
+                report_regions(args.output_path / ("regions_%s.json" % name), pred_cnt, region_names, reg[0], reg[1])
+
+
 def main():
     p = ArgumentParser()
     p.add_argument("--input_path", type=Path, required=True)
@@ -164,10 +242,17 @@ def main():
     add_points_args(p)
     add_regions_args(p)
     add_zoom_args(p)
+    p.add_argument("--yuv", default=None, metavar="FORMAT:WxH[:MATRIX[:RANGE[:CHROMA]]]",
+                   help="--input_path is a raw clip of packed nv12 / nv21 / i420 / p010 frames, converted to RGB on the device")
+    p.add_argument("--max_frames", type=int, default=None, help="with --yuv: read the first N frames of the clip")
     args = p.parse_args()
     zoom = parse_zoom(args)
     if zoom != 1 and args.regions_json is not None:
         p.error("--regions_json is for --zoom 1")
+    clip = None
+    if args.yuv:                      # read before the model is built: a truncated clip fails at once
+        yw, yh, ykw = parse_yuv(args.yuv)
+        clip = read_clip(args.input_path, yw, yh, ykw, args.max_frames)
     args.output_path.mkdir(exist_ok=True, parents=True)
     device = torch.device("cuda")
     region_names, polygons = load_regions(args.regions_json)
@@ -181,6 +266,8 @@ def main():
         print("Resume checkpoint %s" % args.model_path)
     model.to(device).eval()
 
+    if args.yuv:
+        return run_yuv(args, model, device, zoom, region_names, polygons, clip)
     if args.input_path.is_dir():
         inputs = sorted(chain(args.input_path.glob("*.jpg"), args.input_path.glob("*.png")))
     else:
