@@ -3,9 +3,12 @@ build, the CPU tools) stays free of torch."""
 
 
 def __getattr__(name):
-    if name in ("count_frames", "locate_frames", "count_regions", "count_classes", "ClassCounts", "FramePrep"):
+    if name in ("count_frames", "locate_frames", "count_regions", "count_classes", "ClassCounts", "FramePrep", "annotate_frames"):
         from . import frames
         return getattr(frames, name)
+    if name in ("Overlay", "overlay_host"):
+        from . import overlay
+        return getattr(overlay, name)
     if name in ("PeakFinder", "peaks_host", "Peaks"):
         from . import peaks
         return getattr(peaks, name)

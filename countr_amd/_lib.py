@@ -283,3 +283,43 @@ def yuv_check(rc, what=""):
 def yuv_exported_symbols():
     """Names declared in include/countr_hip_yuv.h, which are the names the yuv library exports."""
     return sorted(YUV_PROTOS)
+
+
+# ---- the overlay library: annotated frames composed on the device (density overlay, marks, RGB or 4:2:0 out).
+# include/countr_hip_overlay.h is its one statement, in the same dialect; nothing of it enters the bindings above or this module's
+# COUNTR_* globals.
+OVERLAY_LIB_PATH = os.environ.get("COUNTR_LIB_OVERLAY", os.path.join(_HERE, "libcountr_hip_overlay.so"))
+OVERLAY_HEADER = os.path.join(_HERE, "..", "include", "countr_hip_overlay.h")
+OVERLAY_CONSTS, OVERLAY_STRUCTS, OVERLAY_PROTOS = parse_header(open(OVERLAY_HEADER).read())
+OverlayFrame = OVERLAY_STRUCTS["countr_overlay_frame"]
+_overlay = None
+
+
+def overlay_lib():
+    """Load (once) and return the ctypes handle of libcountr_hip_overlay.so, bound from its header; raises CountrError if it is not built
+    or was built from another version of the header."""
+    global _overlay
+    if _overlay is None:
+        if not os.path.exists(OVERLAY_LIB_PATH):
+            raise CountrError(
+                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
+                "the HIP path has no CPU fallback" % os.path.basename(OVERLAY_LIB_PATH))
+        L = C.CDLL(OVERLAY_LIB_PATH)
+        for name, (restype, argtypes) in OVERLAY_PROTOS.items():
+            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
+            fn.restype, fn.argtypes = restype, argtypes
+        if L.countr_overlay_version() != OVERLAY_CONSTS["COUNTR_OVERLAY_ABI_VERSION"]:
+            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
+                              % (os.path.basename(OVERLAY_LIB_PATH), L.countr_overlay_version(), OVERLAY_CONSTS["COUNTR_OVERLAY_ABI_VERSION"]))
+        _overlay = L
+    return _overlay
+
+
+def overlay_check(rc, what=""):
+    if rc != 0:
+        raise CountrError("%s failed (rc=%d): %s" % (what or "countr_overlay call", rc, (overlay_lib().countr_overlay_last_error() or b"").decode()))
+
+
+def overlay_exported_symbols():
+    """Names declared in include/countr_hip_overlay.h, which are the names the overlay library exports."""
+    return sorted(OVERLAY_PROTOS)

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, classes as classes_, inference, peaks, regions as regions_, tiles as tiles_, yuv as yuv_
+from . import _lib, classes as classes_, inference, overlay as overlay_, peaks, regions as regions_, tiles as tiles_, yuv as yuv_
 
 NEW_H = 384
 BOX = 64                    # exemplar crops are 64 x 64 (demo.py:67)
@@ -170,6 +170,36 @@ class FramePrep:
             for i, rgb in zip(idxs, self.yuv.convert([frames[i] for i in idxs])):
                 frames[i] = rgb
         return frames
+
+    def device_frames(self, frames):
+        """The uint8 RGB device tensor [H, W, 3] of every item: the front part of prepare().  A host array goes through the pinned
+        staging of its slot, a YuvFrame through the converter this FramePrep owns, a device tensor is used where it lies.  Handing the
+        result to prepare() (or to an entry point) uploads and converts nothing again, so a frame goes to the device once for counting
+        and for drawing.  The tensors of host and YuvFrame items are this FramePrep's buffers: the next call overwrites them."""
+        frames = list(frames)
+        if any(isinstance(f, yuv_.YuvFrame) for f in frames):
+            frames = self._convert_yuv(frames)
+        out, seen = [None] * len(frames), {}
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            if self._last is not None and self._last[0] != cur:
+                cur.wait_event(self._last[1])
+            for i, f in enumerate(frames):
+                if not _is_u8(f) or len(f.shape) != 3 or f.shape[2] != 3:
+                    raise ValueError("FramePrep.device_frames: frames are uint8 [H, W, 3], got %s %s" % (f.dtype, tuple(f.shape)))
+                key = (int(f.shape[0]), int(f.shape[1]))
+                k = seen[key] = seen.get(key, -1) + 1
+                slot = None
+                if not (isinstance(f, torch.Tensor) and f.is_cuda):
+                    slots = self._slots.setdefault(key, [])
+                    while len(slots) <= k:
+                        slots.append(_Slot(key[0], key[1], self.device))
+                    slot = slots[k]
+                out[i] = self._frame_on_device(f, slot)
+            if self._last is None or self._last[0] != cur:
+                self._last = (cur, torch.cuda.Event())
+            self._last[1].record(cur)
+        return out
 
     def prepare(self, frames, new_h=NEW_H):
         """frames: uint8 [H, W, 3] each (np.ndarray, CPU tensor or device tensor) -> [[1, 3, new_h, new_W] fp32 device tensors], each equal
@@ -526,6 +556,59 @@ def locate_frames(model, frames, boxes=None, *, radius=4, threshold=0.0, rel_thr
     per = frame_regions(regions, sizes)
     sums = region_maps([(r[0], r[1]) for r in res], sizes, [r[5] for r in res], per)
     return [r[:4] + (counts, regions_.point_regions(r[2], rs)) for r, rs, (counts, _area) in zip(res, per, sums)]
+
+
+def _frame_polygons(regions, n):
+    """annotate_frames' `regions` -> one list of polygons per frame (one list for every frame, or one list per frame)."""
+    if regions is None:
+        return [None] * n
+    regions = list(regions)
+    per = [regions] * n if all(_is_region(r) for r in regions) else regions
+    if len(per) != n:
+        raise ValueError("regions: one list for every frame, or one list per frame")
+    if any(_is_grid(r) for rs in per for r in rs):
+        raise ValueError("annotate_frames draws polygons: a grid has no outline")
+    return per
+
+
+@torch.no_grad()
+def annotate_frames(model, frames, boxes=None, *, out="rgb", gain=127.5, colormap="red", points=False, point_radius=2, regions=None,
+                    label=True, matrix=None, range=None, radius=4, threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all",
+                    normalization=True, max_s_cnt=1, max_batch=32, zoom=1, zoom_max=3, band_stride=128):
+    """count_frames that also shows what it found: [(count, density map, annotated, points or None, score or None), ...].  count and
+    density map are count_frames' bit for bit and, with points=True, points and score are locate_frames' (radius, threshold,
+    rel_threshold, max_points, keep: its peak settings).  annotated is the frame's own pixels at the frame's own size with the density map
+    as a colour overlay (gain, colormap), the count as a label (label=True), the outlines of `regions` (polygons as count_regions takes
+    them; they are drawn, not counted) and a dot of point_radius per point, composed on the device (countr_amd/overlay.py states the
+    rule): a uint8 device tensor [H, W, 3], or for out = "nv12" / "nv21" / "i420" the packed 4:2:0 buffer YuvFrame.from_buffer reads,
+    in `matrix` / `range` (default: a YuvFrame's own, bt709 / limited for other frames).  The tensors are buffers of the device's
+    Overlay: the next call overwrites them.  Every frame goes to the device once (FramePrep.device_frames) for counting and drawing.
+    A frame that took the 3 x 3 split has no single map of the frame: it is drawn WITHOUT heat, with label and marks only.  Under zoom
+    the heat comes from the [384 k, Wk] map."""
+    tiles_.check_zoom(zoom, zoom_max, band_stride)
+    device = next(model.parameters()).device
+    n = len(frames)
+    sizes = [(int(f.shape[1]), int(f.shape[0])) for f in frames]
+    spaces = [(matrix or (f.matrix if isinstance(f, yuv_.YuvFrame) else "bt709"), range or (f.range if isinstance(f, yuv_.YuvFrame) else "limited"))
+              for f in frames]
+    polygons = _frame_polygons(regions, n)
+    dev = frame_prep(device).device_frames(frames)
+    if zoom != 1:
+        ks = frame_zooms(dev, boxes, zoom, zoom_max, max_s_cnt)
+        res = count_frames_zoomed(model, dev, boxes, ks, normalization, max_s_cnt, max_batch, band_stride, crops=True)
+        heights = [NEW_H * k for k in ks]
+    else:
+        res = count_items_crops(model, prepare_items(device, dev, boxes), normalization, max_s_cnt, max_batch)
+        heights = NEW_H
+    located = [(None, None, None)] * n
+    if points:
+        located = locate_maps([(c, dm) for c, dm, _cr in res], sizes, [cr for _c, _dm, cr in res], radius=radius, threshold=threshold,
+                              rel_threshold=rel_threshold, max_points=max_points, keep=keep, new_h=heights)
+    pictures = overlay_.overlay_for(device).render(
+        dev, [None if cr is not None else dm for _c, dm, cr in res], gain=gain, colormap=colormap, points=[p for p, _s, _t in located],
+        point_radius=point_radius, regions=polygons, labels=[overlay_.count_label(r[0], *wh) if label else None for r, wh in zip(res, sizes)],
+        out=out, matrix=[s[0] for s in spaces], range=[s[1] for s in spaces])
+    return [(c, dm, pic, p, s) for (c, dm, _cr), pic, (p, s, _t) in zip(res, pictures, located)]
 
 
 def map_placement(W, H, new_w, new_h=NEW_H):

@@ -27,7 +27,12 @@ then the chroma plane(s), no padding) in nv12, nv21, i420 or p010, as a decoder 
 without tone mapping.  --max_frames N reads the first N frames; an incomplete trailing frame is an error.  The frames are counted
 --group_images at a time through countr_amd.frames.count_frames, each prints `<stem>#<index>: Count: ... - Time: ...`, and
 viz_<stem>_<index>.jpg, points_<stem>_<index>.json and regions_<stem>_<index>.json are what they are for an image, the picture drawn
-from countr_amd.yuv_host of the frame.  demo.py is the few-shot counterpart (exemplar boxes)."""
+from countr_amd.yuv_host of the frame.  `--out_yuv FILE[:FORMAT]` (with --yuv) writes the annotated clip -- density overlay, count label, the
+outlines of --regions_json and the dots of --points on the frame's own pixels -- as raw packed frames in nv12, nv21 or i420 (default: the
+input's format, nv12 for p010; the input's matrix and range), composed on the device by countr_amd.frames.annotate_frames
+(countr_amd/overlay.py states the rule).  `--device_viz`, for images and clips, writes viz_<name>.jpg from the device-composed RGB at the
+input's size instead of the host composition (with --out_yuv the picture is decoded from the written frame).  Both are off by default.
+demo.py is the few-shot counterpart (exemplar boxes)."""
 import json
 import time
 from argparse import ArgumentParser
@@ -158,6 +163,34 @@ def save_visualisation(sample, density_map, pred_cnt, path, old_w, old_h, points
     im.save(path)
 
 
+def parse_out_yuv(spec, input_format):
+    """--out_yuv FILE[:FORMAT] -> (path, format); the format defaults to the input's own, nv12 for p010."""
+    head, _, tail = spec.rpartition(":")
+    if head and tail.lower() in ("nv12", "nv21", "i420"):
+        return Path(head), tail.lower()
+    return Path(spec), "nv12" if input_format == "p010" else input_format
+
+
+def annotate_group(model, raw, args, zoom, polygons, out, **space):
+    """frames.annotate_frames for the demos -> per frame (count, map, picture, points or None, score, total peaks, (region counts, areas) or
+    None).  The counts are count_frames', the points locate_maps' with the demo's settings."""
+    sizes = [(r.shape[1], r.shape[0]) for r in raw]
+    res = frames.annotate_frames(model, raw, None, out=out, points=args.points, regions=polygons, normalization=False,
+                                 radius=args.points_radius, rel_threshold=args.points_rel_threshold, keep=args.points_keep, zoom=zoom,
+                                 zoom_max=args.zoom_max, band_stride=args.band_stride, **space)
+    results = [(c, dm) for c, dm, _pic, _p, _s in res]
+    totals = [None] * len(raw)
+    if args.points:                     # the number of peaks found, for points_<stem>.json: the peak finder once more, no forward
+        ks = frames.frame_zooms(raw, None, zoom, args.zoom_max) if zoom != 1 else [1] * len(raw)
+        totals = [t for _p, _s, t in frames.locate_maps(results, sizes, radius=args.points_radius, rel_threshold=args.points_rel_threshold,
+                                                        keep=args.points_keep, new_h=[frames.NEW_H * k for k in ks])]
+    summed = [None] * len(raw)
+    if polygons is not None:
+        summed = frames.region_maps(results, sizes, None, frames.frame_regions(polygons, sizes))
+    torch.cuda.synchronize()
+    return [(c, dm, pic, pts, score, total, reg) for (c, dm, pic, pts, score), total, reg in zip(res, totals, summed)]
+
+
 def parse_yuv(spec):
     """--yuv FORMAT:WxH[:MATRIX[:RANGE[:CHROMA]]] -> (W, H, YuvFrame keywords)."""
     parts = spec.lower().split(":")
@@ -196,9 +229,31 @@ def run_yuv(args, model, device, zoom, region_names, polygons, clip):
     stem = args.input_path.stem
     prep = frames.frame_prep(device)
     group = max(args.group_images, 1)
+    out_file = None
+    if args.out_yuv is not None:
+        out_path, out_format = parse_out_yuv(args.out_yuv, clip[0].format)
+        out_file = open(out_path, "wb")
     for g0 in range(0, len(clip), group):
         raw = clip[g0:g0 + group]
         t0 = time.perf_counter()
+        if out_file is not None or args.device_viz:
+            got = annotate_group(model, raw, args, zoom, polygons, out_format if out_file is not None else "rgb")
+            dt = (time.perf_counter() - t0) / len(raw)
+            for k, (f, (pred_cnt, dm, pic, pts, score, total, reg)) in enumerate(zip(raw, got)):
+                name = "%s_%d" % (stem, g0 + k)
+                pic = pic.cpu().numpy()
+                if out_file is not None:
+                    out_file.write(pic.tobytes())
+                if pts is not None:
+                    write_points(args.output_path / ("points_%s.json" % name), pred_cnt, total, pts, score)
+                if args.device_viz and not args.no_viz:
+                    if out_file is not None:
+                        pic = yuv.yuv_host(yuv.YuvFrame.from_buffer(pic, w, h, format=out_format, matrix=f.matrix, range=f.range))
+                    Image.fromarray(pic).save(args.output_path / ("viz_%s.jpg" % name))
+                print("%s#%d: Count: %s - Time: %s" % (stem, g0 + k, pred_cnt, dt))
+                if reg is not None:
+                    report_regions(args.output_path / ("regions_%s.json" % name), pred_cnt, region_names, reg[0], reg[1])
+            continue
         if zoom != 1:
             got = count_zoomed(model, raw, None, zoom, args, False)
         else:
@@ -227,6 +282,8 @@ def run_yuv(args, model, device, zoom, region_names, polygons, clip):
             if zoom == 1 and polygons is not None:
                 reg = summed[k]
                 report_regions(args.output_path / ("regions_%s.json" % name), pred_cnt, region_names, reg[0], reg[1])
+    if out_file is not None:
+        out_file.close()
 
 
 def main():
@@ -245,7 +302,12 @@ def main():
     p.add_argument("--yuv", default=None, metavar="FORMAT:WxH[:MATRIX[:RANGE[:CHROMA]]]",
                    help="--input_path is a raw clip of packed nv12 / nv21 / i420 / p010 frames, converted to RGB on the device")
     p.add_argument("--max_frames", type=int, default=None, help="with --yuv: read the first N frames of the clip")
+    p.add_argument("--out_yuv", default=None, metavar="FILE[:FORMAT]",
+                   help="with --yuv: write the annotated clip as raw nv12 / nv21 / i420 frames, composed on the device")
+    p.add_argument("--device_viz", action="store_true", help="viz_*.jpg from the device-composed RGB at the input's size")
     args = p.parse_args()
+    if args.out_yuv is not None and not args.yuv:
+        p.error("--out_yuv is for --yuv")
     zoom = parse_zoom(args)
     if zoom != 1 and args.regions_json is not None:
         p.error("--regions_json is for --zoom 1")
@@ -275,6 +337,24 @@ def main():
     done = 0
     for g0 in range(0, len(inputs), max(args.group_images, 1)):
         paths = inputs[g0:g0 + max(args.group_images, 1)]
+        if args.device_viz:           # the picture composed on the device from the decoded frame's own pixels
+            raw = [np.asarray(Image.open(pth).convert("RGB"), dtype=np.uint8) for pth in paths]
+            t0 = time.perf_counter()
+            got = annotate_group(model, raw, args, zoom, polygons, "rgb")
+            dt = (time.perf_counter() - t0) / len(paths)
+            for pth, (pred_cnt, dm, pic, pts, score, total, reg) in zip(paths, got):
+                done += 1
+                if pts is not None:
+                    write_points(args.output_path / ("points_%s.json" % pth.stem), pred_cnt, total, pts, score)
+                if not args.no_viz:
+                    Image.fromarray(pic.cpu().numpy()).save(args.output_path / ("viz_%s.jpg" % pth.stem))
+                if len(inputs) > 1:
+                    print("[%3d/%d] %s:\tcount = %5.2f  -  time = %5.2f" % (done, len(inputs), pth.name, pred_cnt, dt))
+                else:
+                    print("Count:", pred_cnt, "- Time:", dt)
+                if reg is not None:
+                    report_regions(args.output_path / ("regions_%s.json" % pth.stem), pred_cnt, region_names, reg[0], reg[1])
+            continue
         if zoom != 1:                 # from the image's own pixels: the decoded frames go to the device as they are
             raw = [np.asarray(Image.open(pth).convert("RGB"), dtype=np.uint8) for pth in paths]
             t0 = time.perf_counter()
