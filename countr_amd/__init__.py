@@ -3,12 +3,15 @@ build, the CPU tools) stays free of torch."""
 
 
 def __getattr__(name):
-    if name in ("count_frames", "locate_frames", "count_regions", "count_classes", "ClassCounts", "FramePrep", "annotate_frames"):
+    if name in ("count_frames", "locate_frames", "count_regions", "count_classes", "ClassCounts", "FramePrep", "annotate_frames", "count_clip"):
         from . import frames
         return getattr(frames, name)
     if name in ("Overlay", "overlay_host"):
         from . import overlay
         return getattr(overlay, name)
+    if name in ("tracks_host", "Tracker", "ClipCounts"):
+        from . import tracks
+        return getattr(tracks, name)
     if name in ("PeakFinder", "peaks_host", "Peaks"):
         from . import peaks
         return getattr(peaks, name)

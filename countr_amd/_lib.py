@@ -323,3 +323,43 @@ def overlay_check(rc, what=""):
 def overlay_exported_symbols():
     """Names declared in include/countr_hip_overlay.h, which are the names the overlay library exports."""
     return sorted(OVERLAY_PROTOS)
+
+
+# ---- the tracks library: the frames' points joined over time (track ids, line crossings, distinct count).
+# include/countr_hip_tracks.h is its one statement, in the same dialect; nothing of it enters the bindings above or this module's
+# COUNTR_* globals.
+TRACKS_LIB_PATH = os.environ.get("COUNTR_LIB_TRACKS", os.path.join(_HERE, "libcountr_hip_tracks.so"))
+TRACKS_HEADER = os.path.join(_HERE, "..", "include", "countr_hip_tracks.h")
+TRACKS_CONSTS, TRACKS_STRUCTS, TRACKS_PROTOS = parse_header(open(TRACKS_HEADER).read())
+TracksStream = TRACKS_STRUCTS["countr_tracks_stream"]
+_tracks = None
+
+
+def tracks_lib():
+    """Load (once) and return the ctypes handle of libcountr_hip_tracks.so, bound from its header; raises CountrError if it is not built
+    or was built from another version of the header."""
+    global _tracks
+    if _tracks is None:
+        if not os.path.exists(TRACKS_LIB_PATH):
+            raise CountrError(
+                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
+                "the HIP path has no CPU fallback" % os.path.basename(TRACKS_LIB_PATH))
+        L = C.CDLL(TRACKS_LIB_PATH)
+        for name, (restype, argtypes) in TRACKS_PROTOS.items():
+            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
+            fn.restype, fn.argtypes = restype, argtypes
+        if L.countr_tracks_version() != TRACKS_CONSTS["COUNTR_TRACKS_ABI_VERSION"]:
+            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
+                              % (os.path.basename(TRACKS_LIB_PATH), L.countr_tracks_version(), TRACKS_CONSTS["COUNTR_TRACKS_ABI_VERSION"]))
+        _tracks = L
+    return _tracks
+
+
+def tracks_check(rc, what=""):
+    if rc != 0:
+        raise CountrError("%s failed (rc=%d): %s" % (what or "countr_tracks call", rc, (tracks_lib().countr_tracks_last_error() or b"").decode()))
+
+
+def tracks_exported_symbols():
+    """Names declared in include/countr_hip_tracks.h, which are the names the tracks library exports."""
+    return sorted(TRACKS_PROTOS)

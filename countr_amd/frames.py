@@ -558,6 +558,76 @@ def locate_frames(model, frames, boxes=None, *, radius=4, threshold=0.0, rel_thr
     return [r[:4] + (counts, regions_.point_regions(r[2], rs)) for r, rs, (counts, _area) in zip(res, per, sums)]
 
 
+def cut_exemplars(device, frame, boxes, prep=None):
+    """The exemplar crops [1, S, 3, 64, 64] of one frame's boxes (pixels of that frame), cut on the device as prepare_items cuts them."""
+    if boxes is None or len(boxes) == 0:
+        raise ValueError("shared exemplars: at least one box")
+    return prepare_items(device, [frame], [boxes], prep)[0][1]
+
+
+def shared_exemplar_items(device, frames, crops, prep=None):
+    """The items of frames that all count with ONE set of exemplar crops (cut_exemplars): every item is (image, crops, None) -- no
+    rectangles, so no frame takes the 3 x 3 split or the rectangle normalisation.  What a user who outlines objects on the first frame of
+    a clip means."""
+    return [(im, crops, None) for im, _ex, _r in prepare_items(device, frames, None, prep)]
+
+
+def _is_shared(boxes):
+    return isinstance(boxes, tuple) and len(boxes) == 2 and isinstance(boxes[0], (int, np.integer))
+
+
+@torch.no_grad()
+def count_clip(model, frames, boxes=None, *, max_dist, lines=None, group=8, max_missed=2, min_hits=3, beta=0.5, tracker=None, radius=4,
+               threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all", normalization=True, max_s_cnt=1, max_batch=32, summaries=False):
+    """locate_frames over a clip, its points joined over time: ([(count, density map, points, score, ids int32 [P], events uint32 [P]),
+    ...] per frame, ClipCounts(started, confirmed, dropped, line_counts int [L, 2] as (forward, backward), live)).  frames: whatever
+    count_frames takes, YuvFrames included, in time order.  Consecutive groups of `group` frames go through locate_frames' path -- count,
+    map, points and score are locate_frames' over the same group bit for bit -- and each group's points then go through Tracker.run on
+    the same stream: one more synchronisation per group, not per frame.  ids[i] is the track of point i (-1: dropped at the 4096-track
+    limit); bit k of events[i] says the point's track crossed line k forward on this frame, bit 16 + k backward (countr_amd/tracks.py
+    and include/countr_hip_tracks.h state the rule).  Points are pixel centres of the original frame, so max_dist is in pixels of the
+    frame per frame interval, and lines -- up to 16 segments (ax, ay, bx, by) -- are in the same pixels.
+    boxes: None, one list per frame, or (k, boxes): the exemplar crops are cut once from frame k of the call and reused for every frame
+    (cut_exemplars, shared_exemplar_items), equal to count_items on those items bit for bit.
+    tracker=: a Tracker(streams=1) to continue -- the live-stream case; max_dist, lines, max_missed, min_hits and beta are then the
+    tracker's own and lines must be left None.  summaries=True: each frame's tuple ends with its step's summary int32 [40] (live,
+    started, confirmed, matched, born, died, dropped, frame, counts[16][2]).  zoom is not taken: the clip is tracked at zoom 1.  The defaults of max_missed, min_hits
+    and beta, like radius and rel_threshold, are unmeasured: no accuracy figure exists."""
+    from . import tracks as tracks_
+    device = next(model.parameters()).device
+    if int(group) != group or group < 1:
+        raise ValueError("count_clip: group is >= 1")
+    if tracker is None:
+        tracker = tracks_.Tracker(device, max_dist=max_dist, max_missed=max_missed, min_hits=min_hits, beta=beta, lines=lines if lines is not None else ())
+    elif tracker.streams != 1 or lines is not None:
+        raise ValueError("count_clip: tracker= is a Tracker of one stream, and the lines are its own")
+    frames = list(frames)
+    cut = None
+    if _is_shared(boxes):
+        k, bx = boxes
+        if not 0 <= int(k) < len(frames):
+            raise ValueError("count_clip: (k, boxes) names a frame of the call")
+        cut = cut_exemplars(device, frames[int(k)], bx)
+    out, last = [], None
+    for g0 in range(0, len(frames), int(group)):
+        part = frames[g0:g0 + int(group)]
+        sizes = [(int(f.shape[1]), int(f.shape[0])) for f in part]
+        if cut is not None:
+            items = shared_exemplar_items(device, part, cut)
+        else:
+            items = prepare_items(device, part, boxes[g0:g0 + int(group)] if boxes is not None else None)
+        res = locate_items(model, items, sizes, radius=radius, threshold=threshold, rel_threshold=rel_threshold, max_points=max_points,
+                           keep=keep, normalization=normalization, max_s_cnt=max_s_cnt, max_batch=max_batch)
+        for r, (ids, events, summary) in zip(res, tracker.run([r[2] for r in res])):
+            out.append(r[:4] + (ids, events) + ((summary,) if summaries else ()))
+            last = summary
+    L = tracker.lines.shape[0]
+    if last is None:
+        st = tracker.state()
+        return out, tracks_.ClipCounts(st["started"], st["confirmed"], st["dropped"], st["counts"][:L].astype(np.int64), st["id"].shape[0])
+    return out, tracks_.clip_counts(last, L)
+
+
 def _frame_polygons(regions, n):
     """annotate_frames' `regions` -> one list of polygons per frame (one list for every frame, or one list per frame)."""
     if regions is None:

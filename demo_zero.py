@@ -32,6 +32,12 @@ outlines of --regions_json and the dots of --points on the frame's own pixels --
 input's format, nv12 for p010; the input's matrix and range), composed on the device by countr_amd.frames.annotate_frames
 (countr_amd/overlay.py states the rule).  `--device_viz`, for images and clips, writes viz_<name>.jpg from the device-composed RGB at the
 input's size instead of the host composition (with --out_yuv the picture is decoded from the written frame).  Both are off by default.
+`--track --track_dist D [--lines_json FILE] [--track_missed M] [--track_hits H]` (with --yuv, at --zoom 1) joins the frames' points over
+time (countr_amd.frames.count_clip, include/countr_hip_tracks.h): --track implies --points, D is the largest move of an object between
+two frames in pixels of the frame, --lines_json is {"name": [[ax, ay], [bx, by]], ...} (up to 16 counting lines in pixels of the frame).
+Each frame's line gains ` - tracks: <live> - crossed: {name: [forward, backward]}` (the crossings of that frame), points_<stem>_<i>.json gains
+"ids", viz_*.jpg gets the lines, and at the end {"clip": {"started", "confirmed", "lines": {name: [forward, backward]}}} is printed and
+written to tracks_<stem>.json.  The defaults of --track_missed and --track_hits are unmeasured.  Without --track nothing changes.
 demo.py is the few-shot counterpart (exemplar boxes)."""
 import json
 import time
@@ -69,10 +75,13 @@ def draw_points(image, points, radius=2):
     return image
 
 
-def write_points(path, pred_cnt, total, points, score):
+def write_points(path, pred_cnt, total, points, score, ids=None):
     with open(path, "w") as f:
-        json.dump({"count": pred_cnt, "total_peaks": int(total),
-                   "points": [[float(x), float(y), float(s)] for (x, y), s in zip(points, score)]}, f)
+        doc = {"count": pred_cnt, "total_peaks": int(total),
+               "points": [[float(x), float(y), float(s)] for (x, y), s in zip(points, score)]}
+        if ids is not None:
+            doc["ids"] = [int(i) for i in ids]
+        json.dump(doc, f)
 
 
 def add_points_args(p):
@@ -146,8 +155,9 @@ def report_regions(path, pred_cnt, names, counts, area):
         json.dump({"count": pred_cnt, "regions": {name: {"count": float(c), "area": int(a)} for name, c, a in zip(names, counts, area)}}, f)
 
 
-def save_visualisation(sample, density_map, pred_cnt, path, old_w, old_h, points=None, regions=None):
-    """demo_zero.py:77-90; points: [(x, y), ...] and regions: polygons of the input image, drawn after the resize back to its size."""
+def save_visualisation(sample, density_map, pred_cnt, path, old_w, old_h, points=None, regions=None, lines=None):
+    """demo_zero.py:77-90; points: [(x, y), ...], regions: polygons and lines: segments (ax, ay, bx, by) of the input image, drawn after
+    the resize back to its size."""
     _, h, w = sample.shape
     pred_fig = torch.stack((density_map, torch.zeros_like(density_map), torch.zeros_like(density_map)))
     count_im = Image.new(mode="RGB", size=(w, h), color=(0, 0, 0))
@@ -158,6 +168,10 @@ def save_visualisation(sample, density_map, pred_cnt, path, old_w, old_h, points
     im = Image.fromarray(arr).resize((old_w, old_h), Image.BILINEAR)
     if regions is not None:
         draw_regions(im, regions)
+    if lines is not None:
+        d = ImageDraw.Draw(im)
+        for ax, ay, bx, by in lines:
+            d.line([(ax, ay), (bx, by)], fill=(0, 255, 255), width=1)
     if points is not None:
         draw_points(im, points)
     im.save(path)
@@ -286,6 +300,50 @@ def run_yuv(args, model, device, zoom, region_names, polygons, clip):
         out_file.close()
 
 
+def load_lines(path):
+    """--lines_json -> (names, [(ax, ay, bx, by), ...]); ([], []) without the flag."""
+    if path is None:
+        return [], []
+    named = json.load(open(path))
+    if not isinstance(named, dict) or not all(np.shape(v) == (2, 2) for v in named.values()):
+        raise ValueError('--lines_json: a JSON object {"name": [[ax, ay], [bx, by]], ...}')
+    return list(named), [(float(a[0]), float(a[1]), float(b[0]), float(b[1])) for a, b in named.values()]
+
+
+def run_track(args, model, device, clip):
+    """--yuv --track: the clip's frames, --group_images at a time, through frames.count_clip with one tracker kept over the groups."""
+    from countr_amd.tracks import Tracker
+    h, w, _ = clip[0].shape
+    stem = args.input_path.stem
+    prep = frames.frame_prep(device)
+    group = max(args.group_images, 1)
+    names, lines = load_lines(args.lines_json)
+    tracker = Tracker(device, max_dist=args.track_dist, max_missed=args.track_missed, min_hits=args.track_hits, lines=lines)
+    peak = dict(radius=args.points_radius, rel_threshold=args.points_rel_threshold, keep=args.points_keep)
+    clip_counts = None
+    for g0 in range(0, len(clip), group):
+        raw = clip[g0:g0 + group]
+        t0 = time.perf_counter()
+        got, clip_counts = frames.count_clip(model, raw, max_dist=args.track_dist, group=group, tracker=tracker, normalization=False,
+                                             summaries=True, **peak)
+        dt = (time.perf_counter() - t0) / len(raw)
+        # the number of peaks found, for points_<stem>.json: the peak finder once more, no forward
+        totals = [t for _p, _s, t in frames.locate_maps([(r[0], r[1]) for r in got], [(w, h)] * len(raw), **peak)]
+        for k, (f, (pred_cnt, dm, pts, score, ids, events, summary), total) in enumerate(zip(raw, got, totals)):
+            name = "%s_%d" % (stem, g0 + k)
+            write_points(args.output_path / ("points_%s.json" % name), pred_cnt, total, pts, score, ids)
+            if not args.no_viz:
+                sample = prep.prepare([yuv.yuv_host(f)])[0][0]
+                save_visualisation(sample, dm.float(), pred_cnt, args.output_path / ("viz_%s.jpg" % name), w, h, points=pts, lines=lines)
+            crossed = {n: [int(((events >> j) & 1).sum()), int(((events >> (16 + j)) & 1).sum())] for j, n in enumerate(names)}
+            print("%s#%d: Count: %s - Time: %s - tracks: %d - crossed: %s" % (stem, g0 + k, pred_cnt, dt, int(summary[0]), json.dumps(crossed)))
+    doc = {"clip": {"started": clip_counts.started, "confirmed": clip_counts.confirmed,
+                    "lines": {n: [int(v) for v in clip_counts.line_counts[j]] for j, n in enumerate(names)}}}
+    print(json.dumps(doc))
+    with open(args.output_path / ("tracks_%s.json" % stem), "w") as f:
+        json.dump(doc, f)
+
+
 def main():
     p = ArgumentParser()
     p.add_argument("--input_path", type=Path, required=True)
@@ -305,10 +363,23 @@ def main():
     p.add_argument("--out_yuv", default=None, metavar="FILE[:FORMAT]",
                    help="with --yuv: write the annotated clip as raw nv12 / nv21 / i420 frames, composed on the device")
     p.add_argument("--device_viz", action="store_true", help="viz_*.jpg from the device-composed RGB at the input's size")
+    p.add_argument("--track", action="store_true", help="with --yuv: join the frames' points over time (implies --points)")
+    p.add_argument("--track_dist", type=float, default=None, help="with --track: the largest move between two frames, in pixels of the frame")
+    p.add_argument("--lines_json", type=Path, default=None, help='with --track: counting lines {"name": [[ax, ay], [bx, by]], ...}, up to 16')
+    p.add_argument("--track_missed", type=int, default=2, help="a track survives this many frames without a detection (the default is unmeasured)")
+    p.add_argument("--track_hits", type=int, default=3, help="detections that confirm a track (the default is unmeasured)")
     args = p.parse_args()
     if args.out_yuv is not None and not args.yuv:
         p.error("--out_yuv is for --yuv")
     zoom = parse_zoom(args)
+    if args.track:
+        if not args.yuv or args.track_dist is None:
+            p.error("--track is for --yuv and needs --track_dist")
+        if zoom != 1 or args.regions_json is not None or args.out_yuv is not None or args.device_viz:
+            p.error("--track is for --zoom 1, without --regions_json, --out_yuv and --device_viz")
+        args.points = True
+    elif args.track_dist is not None or args.lines_json is not None:
+        p.error("--track_dist and --lines_json are for --track")
     if zoom != 1 and args.regions_json is not None:
         p.error("--regions_json is for --zoom 1")
     clip = None
@@ -328,6 +399,8 @@ def main():
         print("Resume checkpoint %s" % args.model_path)
     model.to(device).eval()
 
+    if args.track:
+        return run_track(args, model, device, clip)
     if args.yuv:
         return run_yuv(args, model, device, zoom, region_names, polygons, clip)
     if args.input_path.is_dir():

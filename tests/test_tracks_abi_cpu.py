@@ -1,0 +1,172 @@
+"""CPU: include/countr_hip_tracks.h is the one statement of the tracks library's C ABI, as the six older headers are of theirs.
+countr_amd/_lib.py reads the binding from it and libcountr_hip_tracks.so exports exactly it; checked against the library's own dynamic
+symbols and literal pins.  Every refusal runs on the host: a refused call launches nothing."""
+import ctypes as C
+import glob
+import os
+import re
+import subprocess
+
+from countr_amd import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")      # the compiler countr_amd/build.py uses
+NAMES = ("ABI_VERSION", "MAX_STREAMS", "MAX_TRACKS", "MAX_POINTS", "MAX_LINES", "HEAD_INTS", "FIELDS", "SUMMARY_INTS")
+FIELDS = ("state", "points", "ids", "events", "summary", "lines", "N", "L", "max_dist", "beta", "max_missed", "min_hits")
+EXPORTS = ["countr_tracks_last_error", "countr_tracks_reset", "countr_tracks_state_bytes", "countr_tracks_step", "countr_tracks_version",
+           "countr_tracks_workspace"]
+
+
+def test_header_compiles_as_c_and_the_struct_has_the_compiler_s_layout(tmp_path):
+    assert list(_lib.TRACKS_STRUCTS) == ["countr_tracks_stream"]
+    S = _lib.TracksStream
+    assert [f[0] for f in S._fields_] == list(FIELDS)
+    prints = ["COUNTR_TRACKS_" + n for n in NAMES] + ["(int)sizeof(countr_tracks_stream)"] + ["(int)offsetof(countr_tracks_stream, %s)" % f for f in FIELDS]
+    src = tmp_path / "use.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "countr_hip_tracks.h"\nint main(void) {\n  printf("%s\\n", %s);\n  return 0;\n}\n'
+                   % (" ".join(["%d"] * len(prints)), ", ".join(prints)))
+    subprocess.check_call([HIPCC, "-x", "c", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "use")])
+    got = [int(v) for v in subprocess.check_output([str(tmp_path / "use")], text=True).split()]
+    assert got[:len(NAMES)] == [_lib.TRACKS_CONSTS["COUNTR_TRACKS_" + n] for n in NAMES]
+    assert list(_lib.TRACKS_CONSTS) == ["COUNTR_TRACKS_" + n for n in NAMES]
+    assert got[len(NAMES)] == C.sizeof(S) == 72 and got[len(NAMES) + 1:] == [getattr(S, f).offset for f in FIELDS]
+
+
+def test_library_exports_the_header_and_nothing_else():
+    readelf = subprocess.check_output([HIPCC, "-print-prog-name=llvm-readelf"], text=True).strip()
+    rows = [line.split() for line in subprocess.check_output([readelf, "--dyn-syms", "-W", _lib.TRACKS_LIB_PATH], text=True).splitlines()]
+    defined = [r[7].split("@")[0] for r in rows if len(r) == 8 and r[0][:-1].isdigit() and r[6] != "UND"]
+    assert sorted(n for n in defined if n.startswith("countr_")) == _lib.tracks_exported_symbols() == EXPORTS
+    assert [n for n in defined if not n.startswith(("countr_", "__hip_cuid_"))] == []
+
+
+def test_every_prototype_is_defined_extern_c_in_the_sources():
+    paths = glob.glob(os.path.join(ROOT, "countr_amd", "csrc_tracks", "*.hip"))
+    src = "".join(open(p).read() for p in paths)
+    for name in _lib.tracks_exported_symbols():
+        assert re.search(r'extern "C" [\w ]+\*? ?%s\(' % name, src), name
+    assert re.search(r"countr_tracks_version\(void\) \{ return COUNTR_TRACKS_ABI_VERSION; \}", src)
+    # the library's sources stay outside the globs the other libraries are built from
+    others = [os.path.basename(p) for d in ("csrc", "csrc_ext", "csrc_classes", "csrc_tiles", "csrc_yuv", "csrc_overlay")
+              for p in glob.glob(os.path.join(ROOT, "countr_amd", d, "*.hip"))]
+    assert paths and not set(os.path.basename(p) for p in paths) & set(others)
+    from countr_amd import build
+    # pinned by the older tests: left alone
+    assert list(build.SINGLE) == ["ext", "classes", "tiles"] and list(build.SINGLE_LATER) == ["yuv"] and list(build.SINGLE_OVERLAY) == ["overlay"]
+    assert list(build.SINGLE_TRACKS) == ["tracks"] and build.SINGLE_TRACKS["tracks"][1]() == sorted(paths)
+    assert build.SINGLE_TRACKS["tracks"][0] == os.path.join(ROOT, "countr_amd", "libcountr_hip_tracks.so")
+    assert os.path.samefile(build.SINGLE_TRACKS["tracks"][2], _lib.TRACKS_HEADER)
+
+
+def test_version_limits_binding_and_errors():
+    snapshot = lambda: (dict(_lib.CONSTS), dict(_lib.STRUCTS), dict(_lib.PROTOS), _lib.exported_symbols(),
+                        dict(_lib.EXT_CONSTS), dict(_lib.EXT_STRUCTS), dict(_lib.EXT_PROTOS), _lib.ext_exported_symbols(),
+                        dict(_lib.CLASSES_CONSTS), dict(_lib.CLASSES_STRUCTS), dict(_lib.CLASSES_PROTOS), _lib.classes_exported_symbols(),
+                        dict(_lib.TILES_CONSTS), dict(_lib.TILES_STRUCTS), dict(_lib.TILES_PROTOS), _lib.tiles_exported_symbols(),
+                        dict(_lib.YUV_CONSTS), dict(_lib.YUV_STRUCTS), dict(_lib.YUV_PROTOS), _lib.yuv_exported_symbols(),
+                        dict(_lib.OVERLAY_CONSTS), dict(_lib.OVERLAY_STRUCTS), dict(_lib.OVERLAY_PROTOS), _lib.overlay_exported_symbols())
+    before = snapshot()
+    L = _lib.tracks_lib()
+    assert L.countr_tracks_version() == _lib.TRACKS_CONSTS["COUNTR_TRACKS_ABI_VERSION"] == 1
+    K = {k[len("COUNTR_TRACKS_"):]: v for k, v in _lib.TRACKS_CONSTS.items()}
+    assert K == {"ABI_VERSION": 1, "MAX_STREAMS": 16, "MAX_TRACKS": 4096, "MAX_POINTS": 4096, "MAX_LINES": 16, "HEAD_INTS": 64, "FIELDS": 9,
+                 "SUMMARY_INTS": 40}
+    assert L.countr_tracks_state_bytes() == 4 * (64 + 9 * 4096) and L.countr_tracks_state_bytes() % 16 == 0
+    vp, ci = C.c_void_p, C.c_int
+    assert L.countr_tracks_last_error.restype is C.c_char_p and L.countr_tracks_last_error.argtypes == []
+    assert L.countr_tracks_state_bytes.restype is ci and L.countr_tracks_state_bytes.argtypes == []
+    assert L.countr_tracks_workspace.restype is ci and L.countr_tracks_workspace.argtypes == [ci, ci]
+    assert L.countr_tracks_reset.restype is ci and L.countr_tracks_reset.argtypes == [vp, ci, vp]
+    assert L.countr_tracks_step.restype is ci and L.countr_tracks_step.argtypes == [C.POINTER(_lib.TracksStream), ci, vp, vp]
+    # loading the tracks library leaves the six older bindings as their pinned tests read them
+    assert snapshot() == before
+    assert (len(_lib.PROTOS) == 87 and len(_lib.EXT_PROTOS) == 4 and len(_lib.CLASSES_PROTOS) == 4 and len(_lib.TILES_PROTOS) == 5
+            and len(_lib.YUV_PROTOS) == 3 and len(_lib.OVERLAY_PROTOS) == 3)
+    older = (set(_lib.PROTOS) | set(_lib.EXT_PROTOS) | set(_lib.CLASSES_PROTOS) | set(_lib.TILES_PROTOS) | set(_lib.YUV_PROTOS)
+             | set(_lib.OVERLAY_PROTOS))
+    assert not set(_lib.TRACKS_PROTOS) & older
+    assert not any(k.startswith(("TRACKS_ABI", "TRACKS_MAX", "TRACKS_HEAD_", "TRACKS_FIELDS", "TRACKS_SUMMARY")) for k in vars(_lib))
+    try:
+        _lib.tracks_check(-1, "probe")
+    except _lib.CountrError as e:
+        assert "probe failed" in str(e)
+    else:
+        raise AssertionError("tracks_check(-1) did not raise")
+    # the scratch of a call: the predictions and the tracks' bests of every tracker, and the detections' bests
+    assert L.countr_tracks_workspace(1, 0) == 4096 * 10 and L.countr_tracks_workspace(16, 4096) == 16 * 4096 * 12
+    assert L.countr_tracks_workspace(3, 5) == 3 * (4096 * 10 + 16)
+
+
+def test_refusals_run_on_the_host():
+    """Every refusal returns before anything is read on the device or a kernel is launched: the device pointers are aligned numbers, not
+    buffers."""
+    L = _lib.tracks_lib()
+    err = lambda: L.countr_tracks_last_error().decode()
+    WS = 0x7000000
+
+    def records(n=17, **fields):
+        recs = (_lib.TracksStream * n)()
+        for j in range(n):
+            base = 0x1000000 * (j + 1)
+            recs[j].state, recs[j].points, recs[j].ids, recs[j].events = base, base + 0x100000, base + 0x200000, base + 0x300000
+            recs[j].summary, recs[j].lines = base + 0x400000, base + 0x500000
+            recs[j].N, recs[j].L, recs[j].max_dist, recs[j].beta, recs[j].max_missed, recs[j].min_hits = 5, 1, 8.0, 0.5, 2, 3
+            for k, v in fields.items():
+                setattr(recs[j], k, v)
+        return recs
+
+    def call(recs=None, n=1, ws=WS):
+        return L.countr_tracks_step(records() if recs is None else recs, n, ws, None)
+
+    def one(field, value, j=1, n=3):
+        recs = records()
+        setattr(recs[j], field, value)
+        return call(recs, n=n)
+
+    # n out of range
+    assert call(n=0) < 0 and "1..16 trackers a call, got 0" in err()
+    assert call(n=17) < 0 and "got 17" in err()
+    assert call(n=-1) < 0 and "got -1" in err()
+    # the arrays
+    assert L.countr_tracks_step(None, 1, WS, None) < 0 and "streams array is required" in err()
+    assert call(ws=None) < 0 and "workspace is required and 16-byte aligned" in err()
+    assert call(ws=WS + 8) < 0 and "workspace is required and 16-byte aligned" in err()
+    # ranges
+    assert one("N", -1) < 0 and "tracker 1: 0..4096 points, got -1" in err()
+    assert one("N", 4097) < 0 and "got 4097" in err()
+    assert one("L", 17) < 0 and "tracker 1: 0..16 lines, got 17" in err()
+    assert one("L", -1) < 0 and "got -1" in err()
+    assert one("max_missed", 256) < 0 and "max_missed is 0..255, got 256" in err()
+    assert one("max_missed", -1) < 0 and "got -1" in err()
+    assert one("min_hits", 0) < 0 and "min_hits is 1..255, got 0" in err()
+    assert one("min_hits", 256) < 0 and "got 256" in err()
+    # non-finite or out-of-range parameters
+    for bad in (0.0, -1.0, float("inf"), float("nan"), 1e30):      # (the fp32 square of 1e30 is not finite)
+        assert one("max_dist", bad, j=2) < 0 and "tracker 2: max_dist is finite and > 0" in err(), bad
+    for bad in (-0.1, 1.5, float("nan"), float("inf")):
+        assert one("beta", bad) < 0 and "tracker 1: beta is 0..1" in err(), bad
+    # null pointers: required always, or only with N > 0 / L > 0
+    for field in ("state", "summary", "points", "ids", "events", "lines"):
+        assert one(field, None, j=2) < 0 and "tracker 2 has a null pointer" in err(), field
+    # alignment
+    assert one("state", 0x2000008) < 0 and "the state and the lines are 16-byte aligned" in err()
+    assert one("lines", 0x2500004) < 0 and "the state and the lines are 16-byte aligned" in err()
+    assert one("points", 0x2100004) < 0 and "the points are 8-byte aligned" in err()
+    for field in ("ids", "events", "summary"):
+        assert one(field, 0x2200002) < 0 and "4-byte aligned" in err(), field
+    # two trackers of a call share no state
+    recs = records()
+    recs[2].state = recs[0].state
+    assert call(recs, n=3) < 0 and "trackers 0 and 2 share a state" in err()
+    # the reset and the workspace
+    ptrs = (C.c_void_p * 17)(*[0x1000000 * (j + 1) for j in range(17)])
+    assert L.countr_tracks_reset(ptrs, 0, None) < 0 and "1..16 trackers a call, got 0" in err()
+    assert L.countr_tracks_reset(ptrs, 17, None) < 0 and "got 17" in err()
+    assert L.countr_tracks_reset(None, 1, None) < 0 and "states array is required" in err()
+    ptrs[1] = None
+    assert L.countr_tracks_reset(ptrs, 2, None) < 0 and "tracker 1: the state is required and 16-byte aligned" in err()
+    ptrs[1] = 0x2000004
+    assert L.countr_tracks_reset(ptrs, 2, None) < 0 and "tracker 1" in err()
+    assert L.countr_tracks_workspace(0, 5) < 0 and "got 0 of 5" in err()
+    assert L.countr_tracks_workspace(17, 5) < 0 and L.countr_tracks_workspace(1, -1) < 0 and L.countr_tracks_workspace(1, 4097) < 0
+    assert "got 1 of 4097" in err()
