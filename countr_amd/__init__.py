@@ -3,9 +3,13 @@ build, the CPU tools) stays free of torch."""
 
 
 def __getattr__(name):
-    if name in ("count_frames", "locate_frames", "count_regions", "count_classes", "ClassCounts", "FramePrep", "annotate_frames", "count_clip"):
+    if name in ("count_frames", "locate_frames", "count_regions", "count_classes", "ClassCounts", "FramePrep", "annotate_frames", "count_clip",
+                "count_flow"):
         from . import frames
         return getattr(frames, name)
+    if name in ("flow_host", "FlowCounter", "FlowCounts", "blob_scene"):
+        from . import flow
+        return getattr(flow, name)
     if name in ("Overlay", "overlay_host"):
         from . import overlay
         return getattr(overlay, name)

@@ -363,3 +363,43 @@ def tracks_check(rc, what=""):
 def tracks_exported_symbols():
     """Names declared in include/countr_hip_tracks.h, which are the names the tracks library exports."""
     return sorted(TRACKS_PROTOS)
+
+
+# ---- the flow library: line counts from density flux (luma, block-matching motion, flux of a density map through counting lines).
+# include/countr_hip_flow.h is its one statement, in the same dialect; nothing of it enters the bindings above or this module's
+# COUNTR_* globals.
+FLOW_LIB_PATH = os.environ.get("COUNTR_LIB_FLOW", os.path.join(_HERE, "libcountr_hip_flow.so"))
+FLOW_HEADER = os.path.join(_HERE, "..", "include", "countr_hip_flow.h")
+FLOW_CONSTS, FLOW_STRUCTS, FLOW_PROTOS = parse_header(open(FLOW_HEADER).read())
+FlowMap = FLOW_STRUCTS["countr_flow_map"]
+_flow = None
+
+
+def flow_lib():
+    """Load (once) and return the ctypes handle of libcountr_hip_flow.so, bound from its header; raises CountrError if it is not built or
+    was built from another version of the header."""
+    global _flow
+    if _flow is None:
+        if not os.path.exists(FLOW_LIB_PATH):
+            raise CountrError(
+                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
+                "the HIP path has no CPU fallback" % os.path.basename(FLOW_LIB_PATH))
+        L = C.CDLL(FLOW_LIB_PATH)
+        for name, (restype, argtypes) in FLOW_PROTOS.items():
+            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
+            fn.restype, fn.argtypes = restype, argtypes
+        if L.countr_flow_version() != FLOW_CONSTS["COUNTR_FLOW_ABI_VERSION"]:
+            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
+                              % (os.path.basename(FLOW_LIB_PATH), L.countr_flow_version(), FLOW_CONSTS["COUNTR_FLOW_ABI_VERSION"]))
+        _flow = L
+    return _flow
+
+
+def flow_check(rc, what=""):
+    if rc != 0:
+        raise CountrError("%s failed (rc=%d): %s" % (what or "countr_flow call", rc, (flow_lib().countr_flow_last_error() or b"").decode()))
+
+
+def flow_exported_symbols():
+    """Names declared in include/countr_hip_flow.h, which are the names the flow library exports."""
+    return sorted(FLOW_PROTOS)

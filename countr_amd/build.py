@@ -1,5 +1,5 @@
 """Build libcountr_hip.so (all HIP kernels + the C ABI) and the extension libraries libcountr_hip_ext.so, libcountr_hip_classes.so,
-libcountr_hip_tiles.so, libcountr_hip_yuv.so, libcountr_hip_overlay.so and libcountr_hip_tracks.so in-tree for gfx950.
+libcountr_hip_tiles.so, libcountr_hip_yuv.so, libcountr_hip_overlay.so, libcountr_hip_tracks.so and libcountr_hip_flow.so in-tree for gfx950.
 
 hipcc cross-compiles without a GPU, so this runs in the build container and on the GPU box.
 The .so is git-ignored but travels with the repo snapshot to the GPU box.
@@ -98,11 +98,22 @@ def tracks_sources():
 
 
 SINGLE_TRACKS = {"tracks": (LIB_TRACKS, tracks_sources, TRACKS_HEADER)}
+# the flow library (include/countr_hip_flow.h), from csrc_flow/: every older table's keys are pinned, so it has a table of its own
+CSRC_FLOW = os.path.join(HERE, "csrc_flow")
+LIB_FLOW = os.path.join(HERE, "libcountr_hip_flow.so")
+FLOW_HEADER = os.path.join(HERE, "..", "include", "countr_hip_flow.h")
+
+
+def flow_sources():
+    return sorted(glob.glob(os.path.join(CSRC_FLOW, "*.hip")))
+
+
+SINGLE_FLOW = {"flow": (LIB_FLOW, flow_sources, FLOW_HEADER)}
 
 
 def build(force=False, verbose=True):
     """Compile every csrc/*.hip for gfx950 and link libcountr_hip.so + libcountr_hip_f16.so, and every csrc_ext/*.hip into
-    libcountr_hip_ext.so, every csrc_classes/*.hip into libcountr_hip_classes.so, every csrc_tiles/*.hip into libcountr_hip_tiles.so, every csrc_yuv/*.hip into libcountr_hip_yuv.so, every csrc_overlay/*.hip into libcountr_hip_overlay.so, every csrc_tracks/*.hip into libcountr_hip_tracks.so.  An object is reused only if the record
+    libcountr_hip_ext.so, every csrc_classes/*.hip into libcountr_hip_classes.so, every csrc_tiles/*.hip into libcountr_hip_tiles.so, every csrc_yuv/*.hip into libcountr_hip_yuv.so, every csrc_overlay/*.hip into libcountr_hip_overlay.so, every csrc_tracks/*.hip into libcountr_hip_tracks.so, every csrc_flow/*.hip into libcountr_hip_flow.so.  An object is reused only if the record
     written when it was compiled (build/<variant>/<src>.o.sha256: content hash of the source, of every shared header and of the flags)
     still matches -- content, not mtime, so a snapshot copy or a checkout cannot make a stale object look fresh.  COUNTR_BUILD_FORCE=1
     (or force=True / --force) recompiles everything.  Prints how many objects were compiled."""
@@ -113,7 +124,7 @@ def build(force=False, verbose=True):
     procs, reused, total = [], 0, 0
     links = []
     jobs = int(os.environ.get("COUNTR_BUILD_JOBS", "0")) or max(2, (os.cpu_count() or 4))
-    single = dict(SINGLE, **SINGLE_LATER, **SINGLE_OVERLAY, **SINGLE_TRACKS)
+    single = dict(SINGLE, **SINGLE_LATER, **SINGLE_OVERLAY, **SINGLE_TRACKS, **SINGLE_FLOW)
     for tag, lib, extra in VARIANTS + tuple((t, lib_, None) for t, (lib_, _s, _h) in single.items()):
         bdir = os.path.join(HERE, "build", tag) if tag else os.path.join(HERE, "build")
         os.makedirs(bdir, exist_ok=True)
@@ -156,9 +167,9 @@ def build(force=False, verbose=True):
             subprocess.check_call(cmd)
             open(lrec, "w").write(lwant + "\n")
     if verbose:
-        print("build_mode: %s -- %d of %d objects compiled (2 libraries x %d sources + %d of the extension library + %d of the classes library + %d of the tiles library + %d of the yuv library + %d of the overlay library + %d of the tracks library), %d reused after a "
+        print("build_mode: %s -- %d of %d objects compiled (2 libraries x %d sources + %d of the extension library + %d of the classes library + %d of the tiles library + %d of the yuv library + %d of the overlay library + %d of the tracks library + %d of the flow library), %d reused after a "
               "content-hash check (source + headers + flags)"
-              % ("full" if reused == 0 else "incremental", len(procs), total, len(sources()), len(ext_sources()), len(classes_sources()), len(tiles_sources()), len(yuv_sources()), len(overlay_sources()), len(tracks_sources()), reused), flush=True)
+              % ("full" if reused == 0 else "incremental", len(procs), total, len(sources()), len(ext_sources()), len(classes_sources()), len(tiles_sources()), len(yuv_sources()), len(overlay_sources()), len(tracks_sources()), len(flow_sources()), reused), flush=True)
     return LIB
 
 

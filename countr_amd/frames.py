@@ -628,6 +628,60 @@ def count_clip(model, frames, boxes=None, *, max_dist, lines=None, group=8, max_
     return out, tracks_.clip_counts(last, L)
 
 
+@torch.no_grad()
+def count_flow(model, frames, boxes=None, *, lines, search=4, interval=1, min_gain=256, band=None, group=8, counter=None, motion=False,
+               normalization=True, max_s_cnt=1, max_batch=32):
+    """count_frames over a clip, with the number of objects that crossed each line read from the flux of the density map -- the
+    peak-free counterpart of count_clip's line counts: ([(count, density map, flux float32 [L, 2] as (forward, backward) or None), ...]
+    per frame, FlowCounts(line_counts float64 [L, 2], frames, counted)); with motion=True each tuple ends with the frame's motion field
+    int16 [48, new_W / 8, 2] as (x, y) in 1/16 map px (zeros for the first `interval` frames).  frames: whatever count_frames takes,
+    YuvFrames included, in time order and of ONE shape.  Consecutive groups of `group` frames go through count_frames' path -- count and
+    map are count_frames' over the same group bit for bit -- and then through FlowCounter.run on the same stream: the luma of the
+    prepared image the forward read, its motion against the frame `interval` back (the history crosses the groups), the flux of the map
+    through the lines (countr_amd/flow.py and include/countr_hip_flow.h state the rule); one more synchronisation per group.
+    flux is scale * the frame's flux with scale = count / (total / 60), the test-time normalisation carried as count_regions carries it;
+    line_counts is its sum over the clip in float64.  The first `interval` frames count nothing (flux None), and so does a frame that
+    took the 3 x 3 split: it has no frame map; its luma still enters the history.  lines: up to 16 segments (ax, ay, bx, by) in pixels of
+    the original frame, the tracker's lines: forward ends on its side 1.  band: the width of the counting band in frame pixels (default
+    8 H / 384).  boxes: None, one list per frame, or (k, boxes) as in count_clip.  counter=: a FlowCounter to continue -- the live-stream
+    case; lines, search, interval, min_gain and band are then the counter's own and lines must be None.  zoom is not taken.  The defaults
+    of search, min_gain and band are unmeasured and no accuracy figure exists; motion under about half a map pixel per interval is
+    underestimated, which is what interval is for."""
+    from . import flow as flow_
+    device = next(model.parameters()).device
+    if int(group) != group or group < 1:
+        raise ValueError("count_flow: group is >= 1")
+    if counter is None:
+        counter = flow_.FlowCounter(device, lines=lines if lines is not None else (), search=search, interval=interval, min_gain=min_gain, band=band)
+    elif lines is not None:
+        raise ValueError("count_flow: counter= is a FlowCounter, and the lines are its own")
+    frames = list(frames)
+    cut = None
+    if _is_shared(boxes):
+        k, bx = boxes
+        if not 0 <= int(k) < len(frames):
+            raise ValueError("count_flow: (k, boxes) names a frame of the call")
+        cut = cut_exemplars(device, frames[int(k)], bx)
+    out = []
+    for g0 in range(0, len(frames), int(group)):
+        part = frames[g0:g0 + int(group)]
+        sizes = [(int(f.shape[1]), int(f.shape[0])) for f in part]
+        if cut is not None:
+            items = shared_exemplar_items(device, part, cut)
+        else:
+            items = prepare_items(device, part, boxes[g0:g0 + int(group)] if boxes is not None else None)
+        res = count_items_crops(model, items, normalization, max_s_cnt, max_batch)
+        got = counter.run([it[0] for it in items], [None if cr is not None else dm for _c, dm, cr in res], sizes,
+                          counts=[c for c, _dm, _cr in res], motion=motion)
+        for (c, dm, _cr), (flux, mv, total) in zip(res, got):
+            if flux is not None:
+                flux = (flow_.frame_scale(c, total) * flux.astype(np.float64)).astype(np.float32)
+            if motion and mv is None:
+                mv = np.zeros((dm.shape[0] // flow_.CELL, dm.shape[1] // flow_.CELL, 2), np.int16)
+            out.append((c, dm, flux) + ((mv,) if motion else ()))
+    return out, counter.counts()
+
+
 def _frame_polygons(regions, n):
     """annotate_frames' `regions` -> one list of polygons per frame (one list for every frame, or one list per frame)."""
     if regions is None:

@@ -38,6 +38,11 @@ two frames in pixels of the frame, --lines_json is {"name": [[ax, ay], [bx, by]]
 Each frame's line gains ` - tracks: <live> - crossed: {name: [forward, backward]}` (the crossings of that frame), points_<stem>_<i>.json gains
 "ids", viz_*.jpg gets the lines, and at the end {"clip": {"started", "confirmed", "lines": {name: [forward, backward]}}} is printed and
 written to tracks_<stem>.json.  The defaults of --track_missed and --track_hits are unmeasured.  Without --track nothing changes.
+`--flow --lines_json FILE [--flow_search R] [--flow_interval S] [--flow_band W]` (with --yuv, at --zoom 1, without --track) counts the
+crossings of the same lines from the flux of the density map instead (countr_amd.frames.count_flow, include/countr_hip_flow.h): no peaks
+and no tracks.  Each frame's line gains ` - flux: {name: [forward, backward]}` (that frame's share; null for the first S frames) and at
+the end {"clip": {"flux": {name: [forward, backward]}}} is printed and written to flow_<stem>.json.  The defaults of --flow_search and
+--flow_band are unmeasured; slow motion needs --flow_interval.  Without --flow nothing changes.
 demo.py is the few-shot counterpart (exemplar boxes)."""
 import json
 import time
@@ -344,6 +349,34 @@ def run_track(args, model, device, clip):
         json.dump(doc, f)
 
 
+def run_flow(args, model, device, clip):
+    """--yuv --flow: the clip's frames, --group_images at a time, through frames.count_flow with one FlowCounter kept over the groups."""
+    from countr_amd.flow import FlowCounter
+    h, w, _ = clip[0].shape
+    stem = args.input_path.stem
+    prep = frames.frame_prep(device)
+    group = max(args.group_images, 1)
+    names, lines = load_lines(args.lines_json)
+    counter = FlowCounter(device, lines=lines, search=args.flow_search, interval=args.flow_interval, band=args.flow_band)
+    for g0 in range(0, len(clip), group):
+        raw = clip[g0:g0 + group]
+        t0 = time.perf_counter()
+        got, _counts = frames.count_flow(model, raw, lines=None, group=group, counter=counter, normalization=False)
+        dt = (time.perf_counter() - t0) / len(raw)
+        for k, (f, (pred_cnt, dm, flux)) in enumerate(zip(raw, got)):
+            name = "%s_%d" % (stem, g0 + k)
+            if not args.no_viz:
+                sample = prep.prepare([yuv.yuv_host(f)])[0][0]
+                save_visualisation(sample, dm.float(), pred_cnt, args.output_path / ("viz_%s.jpg" % name), w, h, lines=lines)
+            share = None if flux is None else {n: [float(flux[j, 0]), float(flux[j, 1])] for j, n in enumerate(names)}
+            print("%s#%d: Count: %s - Time: %s - flux: %s" % (stem, g0 + k, pred_cnt, dt, json.dumps(share)))
+    total = counter.counts().line_counts
+    doc = {"clip": {"flux": {n: [float(total[j, 0]), float(total[j, 1])] for j, n in enumerate(names)}}}
+    print(json.dumps(doc))
+    with open(args.output_path / ("flow_%s.json" % stem), "w") as f:
+        json.dump(doc, f)
+
+
 def main():
     p = ArgumentParser()
     p.add_argument("--input_path", type=Path, required=True)
@@ -368,6 +401,10 @@ def main():
     p.add_argument("--lines_json", type=Path, default=None, help='with --track: counting lines {"name": [[ax, ay], [bx, by]], ...}, up to 16')
     p.add_argument("--track_missed", type=int, default=2, help="a track survives this many frames without a detection (the default is unmeasured)")
     p.add_argument("--track_hits", type=int, default=3, help="detections that confirm a track (the default is unmeasured)")
+    p.add_argument("--flow", action="store_true", help="with --yuv and --lines_json: line crossings from the flux of the density map")
+    p.add_argument("--flow_search", type=int, default=4, help="with --flow: the motion search radius in map pixels (the default is unmeasured)")
+    p.add_argument("--flow_interval", type=int, default=1, help="with --flow: match against the frame this many frames back (slow motion needs > 1)")
+    p.add_argument("--flow_band", type=float, default=None, help="with --flow: the counting band in pixels of the frame (default 8 H / 384, unmeasured)")
     args = p.parse_args()
     if args.out_yuv is not None and not args.yuv:
         p.error("--out_yuv is for --yuv")
@@ -378,8 +415,15 @@ def main():
         if zoom != 1 or args.regions_json is not None or args.out_yuv is not None or args.device_viz:
             p.error("--track is for --zoom 1, without --regions_json, --out_yuv and --device_viz")
         args.points = True
+    elif args.flow:
+        if not args.yuv or args.lines_json is None or args.track_dist is not None:
+            p.error("--flow is for --yuv, needs --lines_json and excludes --track")
+        if zoom != 1 or args.regions_json is not None or args.out_yuv is not None or args.device_viz or args.points:
+            p.error("--flow is for --zoom 1, without --points, --regions_json, --out_yuv and --device_viz")
     elif args.track_dist is not None or args.lines_json is not None:
-        p.error("--track_dist and --lines_json are for --track")
+        p.error("--track_dist and --lines_json are for --track or --flow")
+    if args.flow and args.track:
+        p.error("--flow excludes --track")
     if zoom != 1 and args.regions_json is not None:
         p.error("--regions_json is for --zoom 1")
     clip = None
@@ -401,6 +445,8 @@ def main():
 
     if args.track:
         return run_track(args, model, device, clip)
+    if args.flow:
+        return run_flow(args, model, device, clip)
     if args.yuv:
         return run_yuv(args, model, device, zoom, region_names, polygons, clip)
     if args.input_path.is_dir():
