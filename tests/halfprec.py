@@ -12,7 +12,8 @@ elementwise_excess is for outputs that are ONE rounding of an fp32 computation o
 boundary of the exact one still passes; tiny is the same ulp where the format is subnormal; floor is the bar the test already states for
 the same kernel in fp32 mode (the error of the fp32 computation itself, relative to the largest value).  Nothing is measured.  The
 max-norm relerr of the kernel tests cannot see an error confined to small elements (a wrong lane of a packed pair, a flushed
-subnormal); this bound can."""
+subnormal); this bound can.  Outputs that carry MORE than one 16-bit rounding (fused attention: P, dS and the stored O are rounded before
+they are summed) have their own row-wise bound in tests/attnref.py."""
 import collections
 
 import torch

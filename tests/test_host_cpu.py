@@ -177,7 +177,8 @@ def test_init_distributed_mode_reads_the_three_launcher_conventions(monkeypatch)
     monkeypatch.setattr(torch.cuda, "set_device", lambda d: calls.append(("device", d)))
     monkeypatch.setattr(torch.cuda, "device_count", lambda: 8)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "SLURM_PROCID", "OMPI_COMM_WORLD_RANK", "MASTER_ADDR", "MASTER_PORT", "COUNTR_DIST_BACKEND"):
-        monkeypatch.delenv(k, raising=False)
+        monkeypatch.setenv(k, "")       # (recorded as absent even where it is: --dist_on_itp exports RANK / WORLD_SIZE / LOCAL_RANK into
+        monkeypatch.delenv(k)           # os.environ itself, and the CLI tests that run after this one start child processes)
     a = types.SimpleNamespace(dist_on_itp=False, world_size=1, dist_url="env://")
     misc.init_distributed_mode(a)
     assert not a.distributed and (a.rank, a.world_size, a.gpu) == (0, 1, 0) and not calls

@@ -6,6 +6,7 @@ import ctypes as C
 import pytest
 import torch
 
+import attnref as AR
 import halfprec as HP
 import stagecheck as SC
 from countr_amd import _lib
@@ -361,8 +362,20 @@ def test_softmax_fwd_bwd(hip, tdt, code, tol):
 def test_cross_attention_fwd_bwd(hip, S, tdt, code, tol):
     """S <= 8: keys in registers; more (models_crossvit.py:111-128 has no limit, FSC_test_cross(few-shot).py --box_bound -1 passes every
     annotated box): online softmax over the key rows, dk / dv through per-wave LDS regions in key chunks."""
+    _cross_attention_fwd_bwd(hip, 576, S, tdt, code, tol)
+
+
+@pytest.mark.parametrize("N,S", [(1, 1), (1, 9), (65, 1), (65, 9)])
+@pytest.mark.parametrize("tdt,code,tol", DT)
+def test_cross_attention_fwd_bwd_short_sequences(hip, N, S, tdt, code, tol):
+    """One query row (three waves of the forward's only block idle, one partial block of the backward) and 65 (a last block of one
+    row), on the register form (S = 1) and the any-S form (S = 9)."""
+    _cross_attention_fwd_bwd(hip, N, S, tdt, code, tol)
+
+
+def _cross_attention_fwd_bwd(hip, N, S, tdt, code, tol):
     hip = HP.library(tdt, hip)
-    B, N, D, Hh = 2, 576, 512, 16
+    B, D, Hh = 2, 512, 16
     q = rnd((B, N, D), 15).to(tdt)
     k = rnd((B, S, D), 16).to(tdt)
     v = rnd((B, S, D), 17).to(tdt)
@@ -389,6 +402,14 @@ def test_cross_attention_fwd_bwd(hip, S, tdt, code, tol):
     oref.backward(do.double())
     assert relerr(dq, qr.grad) < tol
     assert relerr(dk, kr.grad) < 1e-3 and relerr(dv, vr.grad) < 1e-3
+    # row by row (tests/attnref.py): out and dq are one 16-bit rounding of an fp32 result (fp32 mode: the floor alone), dk and dv fp32
+    # sums -- the floor, relative to the companion of their own row
+    vals, comp = AR.cross_attention(q, k, v, do, Hh, scale)
+    fl = HP.BY_DTYPE[tdt] if code else None
+    for name, got in (("out", o), ("dq", dq)):
+        AR.assert_attn_rows(got.reshape(B, N, Hh, 32), vals[name], comp[name][0], fl, AR.K_ONE_ROUNDING, F32_TOL, comp[name][1], name)
+    for name, got in (("dk", dk), ("dv", dv)):
+        AR.assert_attn_rows(got.reshape(B, S, Hh, 32), vals[name], comp[name][0], None, 0, F32_TOL, None, name)
 
 
 @pytest.mark.parametrize("tdt,code,tol", DT)
@@ -661,7 +682,16 @@ def _masked_mse_and_adamw(hip, fl):
 # fused attention: max-norm bars per flavour.  bf16: P and the output are rounded to 2^-9; fp16: the bars of tests/test_fp16_gpu.py
 FA_OUT = {HP.BF16: 1.5e-2, HP.FP16: 2e-3}
 FA_GRAD = {HP.BF16: 2.5e-2, HP.FP16: 4e-3}
-FA_FWD_SHAPES = [(2, 576, 12, 64), (2, 576, 16, 32), (1, 200, 3, 64), (1, 64, 2, 32), (2, 729, 16, 32)]
+FA_FWD_SHAPES = AR.FWD_SHAPES       # (the shape lists and the inputs live in tests/attnref.py: tests/test_attnref_cpu.py walks the same cases)
+
+
+def attn_forward_checks(fl, ref, out, lse, what):
+    """What every forward test asserts: finite, the max-norm bars, and row by row the companion bound of tests/attnref.py."""
+    B, H, N, dh = ref.q.shape
+    assert torch.isfinite(out.float()).all()
+    assert relerr(out, AR.to_rows(ref.out).reshape(B, N, H * dh)) < FA_OUT[fl]   # P and output rounding
+    assert relerr(lse, ref.lse) < 1e-4
+    AR.assert_self_attention_rows(ref, fl, out=out, what=what)
 
 
 @pytest.mark.parametrize("B,N,H,dh", FA_FWD_SHAPES)
@@ -679,23 +709,15 @@ def test_flash_attention_fwd_fp16(B, N, H, dh):
 
 
 def _flash_attention_fwd(hip, fl, B, N, H, dh):
-    qkv = rnd((B, N, 3, H, dh), 50, 1.0).to(fl.dtype)
-    qkv[0, N // 2, 1, 0] = 6.0  # one key with large logits against every query -> running max jumps mid-sequence
-    qd = qkv.cuda()
+    inp = AR.inputs_fwd_spiked(fl, B, N, H, dh)   # one key with large logits against every query -> running max jumps mid-sequence
+    qd = inp.qkv.cuda()
     out = torch.full((B, N, H * dh), float("nan"), device="cuda", dtype=fl.dtype)
     lse = torch.empty((B, H, N), device="cuda")
-    scale = dh ** -0.5
-    _lib.check(hip.countr_attn_fwd(P(qd), P(out), P(lse), B, N, H, dh, scale, st()))
-    q = qkv[:, :, 0].double().permute(0, 2, 1, 3); k = qkv[:, :, 1].double().permute(0, 2, 1, 3)
-    v = qkv[:, :, 2].double().permute(0, 2, 1, 3)
-    sc = (q @ k.transpose(-1, -2)) * scale
-    ref = (torch.softmax(sc, -1) @ v).permute(0, 2, 1, 3).reshape(B, N, H * dh)
-    assert torch.isfinite(out.float()).all()
-    assert relerr(out, ref) < FA_OUT[fl]   # P and output rounding
-    assert relerr(lse, torch.logsumexp(sc, -1)) < 1e-4
+    _lib.check(hip.countr_attn_fwd(P(qd), P(out), P(lse), B, N, H, dh, inp.scale, st()))
+    attn_forward_checks(fl, AR.reference_of(inp), out, lse, "fwd")
 
 
-FA_PRE_SHAPES = [(2, 576, 12), (1, 64, 3), (1, 1088, 2)]
+FA_PRE_SHAPES = AR.PRE_SHAPES
 
 
 @pytest.mark.parametrize("B,N,H", FA_PRE_SHAPES)
@@ -713,29 +735,17 @@ def test_flash_attention_fwd_prescaled_q(hip, B, N, H):
 
 def _flash_attention_fwd_prescaled_q(hip, fl, B, N, H):
     dh = 64
-    c = dh ** -0.5 * 1.4426950408889634
-    qkv = rnd((B, N, 3, H, dh), 52, 1.0)
-    qkv[0, N // 2, 1, 0] = 6.0
-    qkv[0, N - 3, 1, H - 1] = -5.0
-    qkv[:, :, 0] *= c
-    qkv = qkv.to(fl.dtype)
-    qd = qkv.cuda()
+    inp = AR.inputs_fwd_prescaled(fl, B, N, H)
+    qd = inp.qkv.cuda()
     out = torch.full((B, N, H * dh), float("nan"), device="cuda", dtype=fl.dtype)
     lse = torch.empty((B, H, N), device="cuda")
     _lib.check(hip.countr_attn_fwd(P(qd), P(out), P(lse), B, N, H, dh, 0.0, st()))
-    q = qkv[:, :, 0].double().permute(0, 2, 1, 3); k = qkv[:, :, 1].double().permute(0, 2, 1, 3)
-    v = qkv[:, :, 2].double().permute(0, 2, 1, 3)
-    sc = (q @ k.transpose(-1, -2)) * 0.6931471805599453
-    ref = (torch.softmax(sc, -1) @ v).permute(0, 2, 1, 3).reshape(B, N, H * dh)
-    assert torch.isfinite(out.float()).all()
-    assert relerr(out, ref) < FA_OUT[fl]
-    assert relerr(lse, torch.logsumexp(sc, -1)) < 1e-4
+    attn_forward_checks(fl, AR.reference_of(inp), out, lse, "pre-scaled q")      # softmax over 2^(q' k)
     # unsupported shapes are refused, not silently computed with another scale
     assert hip.countr_attn_fwd(P(qd), P(out), P(lse), B, N, H * 2, 32, 0.0, st()) != 0
 
 
-FA_FAR = [(576, 12, 64, False, 40.0), (576, 12, 64, True, 40.0), (576, 12, 64, True, 250.0), (576, 16, 32, False, 60.0),
-          (200, 3, 64, False, 60.0), (288, 12, 64, False, 250.0)]
+FA_FAR = AR.FAR_SHAPES
 
 
 @pytest.mark.parametrize("N,H,dh,pre,spike", FA_FAR)
@@ -757,64 +767,44 @@ def test_flash_attention_fwd_scores_far_above_the_first_key_tile(hip, N, H, dh, 
 
 def _flash_attention_fwd_far_above(hip, fl, N, H, dh, pre, spike):
     B = 2
-    c = dh ** -0.5 * 1.4426950408889634
-    qkv = rnd((B, N, 3, H, dh), 57, 1.0)
-    g = torch.Generator().manual_seed(58)
-    sign = (torch.randint(0, 2, (dh,), generator=g) * 2 - 1).float()
-    for j in (70, N // 2 + 5, N - 2):                       # all behind key tile 0
-        qkv[0, j, 1, 1] = spike * sign
-    qkv[1, N - 1, 1, H - 1] = spike * sign                  # ... and the very last key of another (batch, head)
-    if pre:
-        qkv[:, :, 0] *= c
-    qkv = qkv.to(fl.dtype)
-    qd = qkv.cuda()
+    inp = AR.inputs_fwd_far_above(fl, N, H, dh, pre, spike)   # keys 70, N / 2 + 5, N - 2 of (0, 1) and the last key of (1, H - 1)
+    qd = inp.qkv.cuda()
     out = torch.full((B, N, H * dh), float("nan"), device="cuda", dtype=fl.dtype)
     lse = torch.empty((B, H, N), device="cuda")
-    _lib.check(hip.countr_attn_fwd(P(qd), P(out), P(lse), B, N, H, dh, 0.0 if pre else dh ** -0.5, st()))
-    q = qkv[:, :, 0].double().permute(0, 2, 1, 3); k = qkv[:, :, 1].double().permute(0, 2, 1, 3)
-    v = qkv[:, :, 2].double().permute(0, 2, 1, 3)
-    sc = (q @ k.transpose(-1, -2)) * (0.6931471805599453 if pre else dh ** -0.5)
+    _lib.check(hip.countr_attn_fwd(P(qd), P(out), P(lse), B, N, H, dh, inp.scale, st()))
+    ref = AR.reference_of(inp)
+    sc = ref.sc
     top = (sc[0, 1].max(-1).values - sc[0, 1, :, :64].max(-1).values) * 1.4426950408889634
     assert (top > 64).sum() > 8 and (top < 1).sum() > 8        # rows that need the exact path, rows that do not
-    ref = (torch.softmax(sc, -1) @ v).permute(0, 2, 1, 3).reshape(B, N, H * dh)
-    assert torch.isfinite(out.float()).all()
-    assert relerr(out, ref) < FA_OUT[fl]
-    assert relerr(lse, torch.logsumexp(sc, -1)) < 1e-4
+    attn_forward_checks(fl, ref, out, lse, "far above")
 
 
-@pytest.mark.parametrize("N,H,dh", [(200, 3, 64), (729, 16, 32)])
+@pytest.mark.parametrize("N,H,dh", AR.RAGGED_SPIKE_SHAPES)
 def test_flash_attention_fwd_fp16_spike_on_the_last_key_of_a_ragged_sequence(N, H, dh):
     """fp16 library only (its forward is the running-max loop): in ONE head the very last key of a ragged sequence (N % 64 = 8 and 25)
     scores 40 dh^-0.5 |q|_1-ish above everything for the query rows on one side of a sign pattern -- their running max jumps on the
     final PARTIAL key tile, and the O accumulated over every earlier tile must be rescaled there -- while key 10 (first tile) carries
     the mirrored pattern, so the other rows of the same head have their maximum in the first tile and never rescale afterwards."""
     hip, fl, B = HP.library(HP.FP16), HP.FP16, 2
-    qkv = rnd((B, N, 3, H, dh), 59, 1.0)
-    sign = (torch.randint(0, 2, (dh,), generator=torch.Generator().manual_seed(60)) * 2 - 1).float()
-    qkv[0, N - 1, 1, 1] = 40.0 * sign
-    qkv[0, 10, 1, 1] = -6.0 * sign
-    qkv = qkv.to(fl.dtype)
-    qd = qkv.cuda()
+    inp = AR.inputs_fwd_ragged_spike(fl, N, H, dh)
+    qd = inp.qkv.cuda()
     out = torch.full((B, N, H * dh), float("nan"), device="cuda", dtype=fl.dtype)
     lse = torch.empty((B, H, N), device="cuda")
     _lib.check(hip.countr_attn_fwd(P(qd), P(out), P(lse), B, N, H, dh, dh ** -0.5, st()))
-    q = qkv[:, :, 0].double().permute(0, 2, 1, 3); k = qkv[:, :, 1].double().permute(0, 2, 1, 3)
-    v = qkv[:, :, 2].double().permute(0, 2, 1, 3)
-    sc = (q @ k.transpose(-1, -2)) * dh ** -0.5
+    full = AR.reference_of(inp)
+    sc = full.sc
     arg = sc[0, 1].argmax(-1)
     jump = (sc[0, 1, :, N - 1] - sc[0, 1, :, :N - 1].max(-1).values) * 1.4426950408889634
     assert ((arg == N - 1) & (jump > 16)).sum() > 8 and (arg < 64).sum() > 8       # rows that rescale on the last tile, rows that never do
-    ref = (torch.softmax(sc, -1) @ v).permute(0, 2, 1, 3).reshape(B, N, H * dh)
-    assert torch.isfinite(out.float()).all()
-    assert relerr(out, ref) < FA_OUT[fl]
-    assert relerr(lse, torch.logsumexp(sc, -1)) < 1e-4
+    attn_forward_checks(fl, full, out, lse, "ragged spike")
+    ref = AR.to_rows(full.out).reshape(B, N, H * dh)
     # the rows in question on their own: the max norm above is set by whichever head is largest
     rows = (arg == N - 1).nonzero().reshape(-1)
     o1, r1 = out[0, rows, dh:2 * dh], ref[0, rows, dh:2 * dh]
     assert relerr(o1, r1) < FA_OUT[fl]
 
 
-FA_BWD_SHAPES = [(2, 576, 16, 32), (1, 576, 12, 64), (1, 200, 3, 32), (2, 64, 2, 64)]
+FA_BWD_SHAPES = AR.BWD_SHAPES
 
 
 @pytest.mark.parametrize("B,N,H,dh", FA_BWD_SHAPES)
@@ -829,9 +819,8 @@ def test_flash_attention_bwd(hip, B, N, H, dh):
 
 
 def _flash_attention_bwd(hip, fl, B, N, H, dh):
-    qkv = (rnd((B, N, 3, H, dh), 60, 1.0)).to(fl.dtype)
-    qkv[0, N // 3, 1, 0] = 5.0
-    do = rnd((B, N, H * dh), 61, 1.0).to(fl.dtype)
+    inp = AR.inputs_bwd_spiked(fl, B, N, H, dh)
+    qkv, do = inp.qkv, inp.do
     qd, dod = qkv.cuda(), do.cuda()
     out = torch.empty((B, N, H * dh), device="cuda", dtype=fl.dtype)
     lse = torch.empty((B, H, N), device="cuda")
@@ -847,6 +836,7 @@ def _flash_attention_bwd(hip, fl, B, N, H, dh):
     assert torch.isfinite(dqkv.float()).all()
     for slot, name in enumerate(("dq", "dk", "dv")):
         assert relerr(dqkv[:, :, slot], x.grad[:, :, slot]) < FA_GRAD[fl], name   # 16-bit P/dS operands and 16-bit outputs
+    AR.assert_self_attention_rows(AR.reference_of(inp), fl, out=out, dqkv=dqkv, what="bwd")   # row by row, each output with its own K
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32, torch.float16])
