@@ -6,6 +6,8 @@ import ctypes as C
 import os
 import re
 
+from .build import TAGS
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COUNTR_LIB", os.path.join(_HERE, "libcountr_hip.so"))
 # the same sources built with IEEE fp16 as the 16-bit storage / matrix-operand type (precision="fp16"; csrc/common.hpp, build.py)
@@ -94,24 +96,29 @@ ReportPatch, ReportImage, ReportStrip, PeakMap, MatchSet = (STRUCTS["countr_" + 
 _libs = {}
 
 
+def _load(path, protos, version, want):
+    """The ctypes handle of the library at `path`, bound from its header's prototypes; raises CountrError if it is not built or was
+    built from another version of the header (its `version` export does not return `want`)."""
+    if not os.path.exists(path):
+        raise CountrError(
+            "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
+            "the HIP path has no CPU fallback" % os.path.basename(path))
+    L = C.CDLL(path)
+    for name, (restype, argtypes) in protos.items():
+        fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
+        fn.restype, fn.argtypes = restype, argtypes
+    if getattr(L, version)() != want:      # a stale build: its structs (countr_gemm_args, ...) are not the header's
+        raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
+                          % (os.path.basename(path), getattr(L, version)(), want))
+    return L
+
+
 def lib(variant=""):
     """Load (once) and return the ctypes handle of a library variant ("" = bf16 build, "f16" = fp16 build); raises CountrError if it
     is not built."""
     L = _libs.get(variant)
     if L is None:
-        path = LIB_PATH_F16 if variant == "f16" else LIB_PATH
-        if not os.path.exists(path):
-            raise CountrError(
-                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
-                "the HIP path has no CPU fallback" % os.path.basename(path))
-        L = C.CDLL(path)
-        for name, (restype, argtypes) in PROTOS.items():
-            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
-            fn.restype, fn.argtypes = restype, argtypes
-        if L.countr_version() != ABI_VERSION:      # a stale build: its countr_gemm_args is shorter than GemmArgs
-            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
-                              % (os.path.basename(path), L.countr_version(), ABI_VERSION))
-        _libs[variant] = L
+        L = _libs[variant] = _load(LIB_PATH_F16 if variant == "f16" else LIB_PATH, PROTOS, "countr_version", ABI_VERSION)
     return L
 
 
@@ -130,276 +137,46 @@ def exported_symbols():
     return sorted(PROTOS)
 
 
-# ---- the extension library: exports that came after the ABI of countr_hip.h was closed.  include/countr_hip_ext.h is its one statement,
-# in the same dialect; nothing of it enters CONSTS / STRUCTS / PROTOS or this module's COUNTR_* globals.
-EXT_LIB_PATH = os.environ.get("COUNTR_LIB_EXT", os.path.join(_HERE, "libcountr_hip_ext.so"))
-EXT_HEADER = os.path.join(_HERE, "..", "include", "countr_hip_ext.h")
-EXT_CONSTS, EXT_STRUCTS, EXT_PROTOS = parse_header(open(EXT_HEADER).read())
+# ---- the side libraries: exports that came after the ABI of countr_hip.h was closed.  Each is stated by its tag alone (build.py builds
+# them by the same rule): header include/countr_hip_<tag>.h, in the same dialect, is its one statement; nothing of it enters CONSTS /
+# STRUCTS / PROTOS or this module's COUNTR_* globals.
+class Library:
+    """The binding of libcountr_hip_<tag>.so (COUNTR_LIB_<TAG> overrides the path), read from its header."""
+
+    def __init__(self, tag):
+        self.tag = tag
+        self.path = os.environ.get("COUNTR_LIB_" + tag.upper(), os.path.join(_HERE, "libcountr_hip_%s.so" % tag))
+        self.header = os.path.join(_HERE, "..", "include", "countr_hip_%s.h" % tag)
+        self.consts, self.structs, self.protos = parse_header(open(self.header).read())
+        self._handle = None
+
+    def load(self):
+        """Load (once) and return the ctypes handle, bound from the header; raises CountrError if the library is not built or was built
+        from another version of the header."""
+        if self._handle is None:
+            self._handle = _load(self.path, self.protos, "countr_%s_version" % self.tag,
+                                 self.consts["COUNTR_%s_ABI_VERSION" % self.tag.upper()])
+        return self._handle
+
+    def check(self, rc, what=""):
+        if rc != 0:
+            text = getattr(self.load(), "countr_%s_last_error" % self.tag)() or b""
+            raise CountrError("%s failed (rc=%d): %s" % (what or "countr_%s call" % self.tag, rc, text.decode()))
+
+    def exported_symbols(self):
+        """Names declared in the header, which are the names the library exports."""
+        return sorted(self.protos)
+
+
+# build.TAGS, in the order they were added: regional counts, the fold of class maps into a label map, frames counted on a 2-D grid of
+# tiles, 4:2:0 decoder surfaces to packed RGB, annotated frames, points joined into tracks, line counts from density flux
+LIBRARIES = {tag: Library(tag) for tag in TAGS}
+# what the wrappers read: EXT_LIB_PATH, EXT_HEADER, EXT_CONSTS, EXT_STRUCTS, EXT_PROTOS, ext_lib(), ext_check(rc, what), ext_exported_symbols()
+# and the same for every other tag
+for _tag, _l in LIBRARIES.items():
+    globals().update({_tag.upper() + "_LIB_PATH": _l.path, _tag.upper() + "_HEADER": _l.header, _tag.upper() + "_CONSTS": _l.consts,
+                      _tag.upper() + "_STRUCTS": _l.structs, _tag.upper() + "_PROTOS": _l.protos, _tag + "_lib": _l.load,
+                      _tag + "_check": _l.check, _tag + "_exported_symbols": _l.exported_symbols})
 RegionMap, Region = EXT_STRUCTS["countr_region_map"], EXT_STRUCTS["countr_region"]
-_ext = None
-
-
-def ext_lib():
-    """Load (once) and return the ctypes handle of libcountr_hip_ext.so, bound from its header; raises CountrError if it is not built or
-    was built from another version of the header."""
-    global _ext
-    if _ext is None:
-        if not os.path.exists(EXT_LIB_PATH):
-            raise CountrError(
-                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
-                "the HIP path has no CPU fallback" % os.path.basename(EXT_LIB_PATH))
-        L = C.CDLL(EXT_LIB_PATH)
-        for name, (restype, argtypes) in EXT_PROTOS.items():
-            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
-            fn.restype, fn.argtypes = restype, argtypes
-        if L.countr_ext_version() != EXT_CONSTS["COUNTR_EXT_ABI_VERSION"]:
-            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
-                              % (os.path.basename(EXT_LIB_PATH), L.countr_ext_version(), EXT_CONSTS["COUNTR_EXT_ABI_VERSION"]))
-        _ext = L
-    return _ext
-
-
-def ext_check(rc, what=""):
-    if rc != 0:
-        raise CountrError("%s failed (rc=%d): %s" % (what or "countr_ext call", rc, (ext_lib().countr_ext_last_error() or b"").decode()))
-
-
-def ext_exported_symbols():
-    """Names declared in include/countr_hip_ext.h, which are the names the extension library exports."""
-    return sorted(EXT_PROTOS)
-
-
-# ---- the classes library: the fold of a frame's class maps into a label map.  include/countr_hip_classes.h is its one statement, in
-# the same dialect; nothing of it enters the bindings above or this module's COUNTR_* globals.
-CLASSES_LIB_PATH = os.environ.get("COUNTR_LIB_CLASSES", os.path.join(_HERE, "libcountr_hip_classes.so"))
-CLASSES_HEADER = os.path.join(_HERE, "..", "include", "countr_hip_classes.h")
-CLASSES_CONSTS, CLASSES_STRUCTS, CLASSES_PROTOS = parse_header(open(CLASSES_HEADER).read())
-ClassSet = CLASSES_STRUCTS["countr_class_set"]
-_classes = None
-
-
-def classes_lib():
-    """Load (once) and return the ctypes handle of libcountr_hip_classes.so, bound from its header; raises CountrError if it is not built
-    or was built from another version of the header."""
-    global _classes
-    if _classes is None:
-        if not os.path.exists(CLASSES_LIB_PATH):
-            raise CountrError(
-                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
-                "the HIP path has no CPU fallback" % os.path.basename(CLASSES_LIB_PATH))
-        L = C.CDLL(CLASSES_LIB_PATH)
-        for name, (restype, argtypes) in CLASSES_PROTOS.items():
-            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
-            fn.restype, fn.argtypes = restype, argtypes
-        if L.countr_classes_version() != CLASSES_CONSTS["COUNTR_CLASSES_ABI_VERSION"]:
-            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
-                              % (os.path.basename(CLASSES_LIB_PATH), L.countr_classes_version(), CLASSES_CONSTS["COUNTR_CLASSES_ABI_VERSION"]))
-        _classes = L
-    return _classes
-
-
-def classes_check(rc, what=""):
-    if rc != 0:
-        raise CountrError("%s failed (rc=%d): %s" % (what or "countr_classes call", rc, (classes_lib().countr_classes_last_error() or b"").decode()))
-
-
-def classes_exported_symbols():
-    """Names declared in include/countr_hip_classes.h, which are the names the classes library exports."""
-    return sorted(CLASSES_PROTOS)
-
-
-# ---- the tiles library: a frame counted on a 2-D grid of 384 x 384 tiles (count_frames(zoom=k)).  include/countr_hip_tiles.h is its one
-# statement, in the same dialect; nothing of it enters the bindings above or this module's COUNTR_* globals.
-TILES_LIB_PATH = os.environ.get("COUNTR_LIB_TILES", os.path.join(_HERE, "libcountr_hip_tiles.so"))
-TILES_HEADER = os.path.join(_HERE, "..", "include", "countr_hip_tiles.h")
-TILES_CONSTS, TILES_STRUCTS, TILES_PROTOS = parse_header(open(TILES_HEADER).read())
-_tiles = None
-
-
-def tiles_lib():
-    """Load (once) and return the ctypes handle of libcountr_hip_tiles.so, bound from its header; raises CountrError if it is not built
-    or was built from another version of the header."""
-    global _tiles
-    if _tiles is None:
-        if not os.path.exists(TILES_LIB_PATH):
-            raise CountrError(
-                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
-                "the HIP path has no CPU fallback" % os.path.basename(TILES_LIB_PATH))
-        L = C.CDLL(TILES_LIB_PATH)
-        for name, (restype, argtypes) in TILES_PROTOS.items():
-            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
-            fn.restype, fn.argtypes = restype, argtypes
-        if L.countr_tiles_version() != TILES_CONSTS["COUNTR_TILES_ABI_VERSION"]:
-            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
-                              % (os.path.basename(TILES_LIB_PATH), L.countr_tiles_version(), TILES_CONSTS["COUNTR_TILES_ABI_VERSION"]))
-        _tiles = L
-    return _tiles
-
-
-def tiles_check(rc, what=""):
-    if rc != 0:
-        raise CountrError("%s failed (rc=%d): %s" % (what or "countr_tiles call", rc, (tiles_lib().countr_tiles_last_error() or b"").decode()))
-
-
-def tiles_exported_symbols():
-    """Names declared in include/countr_hip_tiles.h, which are the names the tiles library exports."""
-    return sorted(TILES_PROTOS)
-
-
-# ---- the yuv library: 4:2:0 decoder surfaces (NV12, NV21, I420, P010) converted to the packed RGB the raw-frame entry points take.
-# include/countr_hip_yuv.h is its one statement, in the same dialect; nothing of it enters the bindings above or this module's COUNTR_*
-# globals.
-YUV_LIB_PATH = os.environ.get("COUNTR_LIB_YUV", os.path.join(_HERE, "libcountr_hip_yuv.so"))
-YUV_HEADER = os.path.join(_HERE, "..", "include", "countr_hip_yuv.h")
-YUV_CONSTS, YUV_STRUCTS, YUV_PROTOS = parse_header(open(YUV_HEADER).read())
-_yuv = None
-
-
-def yuv_lib():
-    """Load (once) and return the ctypes handle of libcountr_hip_yuv.so, bound from its header; raises CountrError if it is not built or
-    was built from another version of the header."""
-    global _yuv
-    if _yuv is None:
-        if not os.path.exists(YUV_LIB_PATH):
-            raise CountrError(
-                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
-                "the HIP path has no CPU fallback" % os.path.basename(YUV_LIB_PATH))
-        L = C.CDLL(YUV_LIB_PATH)
-        for name, (restype, argtypes) in YUV_PROTOS.items():
-            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
-            fn.restype, fn.argtypes = restype, argtypes
-        if L.countr_yuv_version() != YUV_CONSTS["COUNTR_YUV_ABI_VERSION"]:
-            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
-                              % (os.path.basename(YUV_LIB_PATH), L.countr_yuv_version(), YUV_CONSTS["COUNTR_YUV_ABI_VERSION"]))
-        _yuv = L
-    return _yuv
-
-
-def yuv_check(rc, what=""):
-    if rc != 0:
-        raise CountrError("%s failed (rc=%d): %s" % (what or "countr_yuv call", rc, (yuv_lib().countr_yuv_last_error() or b"").decode()))
-
-
-def yuv_exported_symbols():
-    """Names declared in include/countr_hip_yuv.h, which are the names the yuv library exports."""
-    return sorted(YUV_PROTOS)
-
-
-# ---- the overlay library: annotated frames composed on the device (density overlay, marks, RGB or 4:2:0 out).
-# include/countr_hip_overlay.h is its one statement, in the same dialect; nothing of it enters the bindings above or this module's
-# COUNTR_* globals.
-OVERLAY_LIB_PATH = os.environ.get("COUNTR_LIB_OVERLAY", os.path.join(_HERE, "libcountr_hip_overlay.so"))
-OVERLAY_HEADER = os.path.join(_HERE, "..", "include", "countr_hip_overlay.h")
-OVERLAY_CONSTS, OVERLAY_STRUCTS, OVERLAY_PROTOS = parse_header(open(OVERLAY_HEADER).read())
-OverlayFrame = OVERLAY_STRUCTS["countr_overlay_frame"]
-_overlay = None
-
-
-def overlay_lib():
-    """Load (once) and return the ctypes handle of libcountr_hip_overlay.so, bound from its header; raises CountrError if it is not built
-    or was built from another version of the header."""
-    global _overlay
-    if _overlay is None:
-        if not os.path.exists(OVERLAY_LIB_PATH):
-            raise CountrError(
-                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
-                "the HIP path has no CPU fallback" % os.path.basename(OVERLAY_LIB_PATH))
-        L = C.CDLL(OVERLAY_LIB_PATH)
-        for name, (restype, argtypes) in OVERLAY_PROTOS.items():
-            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
-            fn.restype, fn.argtypes = restype, argtypes
-        if L.countr_overlay_version() != OVERLAY_CONSTS["COUNTR_OVERLAY_ABI_VERSION"]:
-            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
-                              % (os.path.basename(OVERLAY_LIB_PATH), L.countr_overlay_version(), OVERLAY_CONSTS["COUNTR_OVERLAY_ABI_VERSION"]))
-        _overlay = L
-    return _overlay
-
-
-def overlay_check(rc, what=""):
-    if rc != 0:
-        raise CountrError("%s failed (rc=%d): %s" % (what or "countr_overlay call", rc, (overlay_lib().countr_overlay_last_error() or b"").decode()))
-
-
-def overlay_exported_symbols():
-    """Names declared in include/countr_hip_overlay.h, which are the names the overlay library exports."""
-    return sorted(OVERLAY_PROTOS)
-
-
-# ---- the tracks library: the frames' points joined over time (track ids, line crossings, distinct count).
-# include/countr_hip_tracks.h is its one statement, in the same dialect; nothing of it enters the bindings above or this module's
-# COUNTR_* globals.
-TRACKS_LIB_PATH = os.environ.get("COUNTR_LIB_TRACKS", os.path.join(_HERE, "libcountr_hip_tracks.so"))
-TRACKS_HEADER = os.path.join(_HERE, "..", "include", "countr_hip_tracks.h")
-TRACKS_CONSTS, TRACKS_STRUCTS, TRACKS_PROTOS = parse_header(open(TRACKS_HEADER).read())
-TracksStream = TRACKS_STRUCTS["countr_tracks_stream"]
-_tracks = None
-
-
-def tracks_lib():
-    """Load (once) and return the ctypes handle of libcountr_hip_tracks.so, bound from its header; raises CountrError if it is not built
-    or was built from another version of the header."""
-    global _tracks
-    if _tracks is None:
-        if not os.path.exists(TRACKS_LIB_PATH):
-            raise CountrError(
-                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
-                "the HIP path has no CPU fallback" % os.path.basename(TRACKS_LIB_PATH))
-        L = C.CDLL(TRACKS_LIB_PATH)
-        for name, (restype, argtypes) in TRACKS_PROTOS.items():
-            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
-            fn.restype, fn.argtypes = restype, argtypes
-        if L.countr_tracks_version() != TRACKS_CONSTS["COUNTR_TRACKS_ABI_VERSION"]:
-            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
-                              % (os.path.basename(TRACKS_LIB_PATH), L.countr_tracks_version(), TRACKS_CONSTS["COUNTR_TRACKS_ABI_VERSION"]))
-        _tracks = L
-    return _tracks
-
-
-def tracks_check(rc, what=""):
-    if rc != 0:
-        raise CountrError("%s failed (rc=%d): %s" % (what or "countr_tracks call", rc, (tracks_lib().countr_tracks_last_error() or b"").decode()))
-
-
-def tracks_exported_symbols():
-    """Names declared in include/countr_hip_tracks.h, which are the names the tracks library exports."""
-    return sorted(TRACKS_PROTOS)
-
-
-# ---- the flow library: line counts from density flux (luma, block-matching motion, flux of a density map through counting lines).
-# include/countr_hip_flow.h is its one statement, in the same dialect; nothing of it enters the bindings above or this module's
-# COUNTR_* globals.
-FLOW_LIB_PATH = os.environ.get("COUNTR_LIB_FLOW", os.path.join(_HERE, "libcountr_hip_flow.so"))
-FLOW_HEADER = os.path.join(_HERE, "..", "include", "countr_hip_flow.h")
-FLOW_CONSTS, FLOW_STRUCTS, FLOW_PROTOS = parse_header(open(FLOW_HEADER).read())
-FlowMap = FLOW_STRUCTS["countr_flow_map"]
-_flow = None
-
-
-def flow_lib():
-    """Load (once) and return the ctypes handle of libcountr_hip_flow.so, bound from its header; raises CountrError if it is not built or
-    was built from another version of the header."""
-    global _flow
-    if _flow is None:
-        if not os.path.exists(FLOW_LIB_PATH):
-            raise CountrError(
-                "%s is not built (run `python -m countr_amd.build` or __graft_entry__.build()); "
-                "the HIP path has no CPU fallback" % os.path.basename(FLOW_LIB_PATH))
-        L = C.CDLL(FLOW_LIB_PATH)
-        for name, (restype, argtypes) in FLOW_PROTOS.items():
-            fn = getattr(L, name)  # AttributeError here means the .so is stale: rebuild
-            fn.restype, fn.argtypes = restype, argtypes
-        if L.countr_flow_version() != FLOW_CONSTS["COUNTR_FLOW_ABI_VERSION"]:
-            raise CountrError("%s has ABI version %d, this package needs %d: rebuild (python -m countr_amd.build)"
-                              % (os.path.basename(FLOW_LIB_PATH), L.countr_flow_version(), FLOW_CONSTS["COUNTR_FLOW_ABI_VERSION"]))
-        _flow = L
-    return _flow
-
-
-def flow_check(rc, what=""):
-    if rc != 0:
-        raise CountrError("%s failed (rc=%d): %s" % (what or "countr_flow call", rc, (flow_lib().countr_flow_last_error() or b"").decode()))
-
-
-def flow_exported_symbols():
-    """Names declared in include/countr_hip_flow.h, which are the names the flow library exports."""
-    return sorted(FLOW_PROTOS)
+ClassSet, OverlayFrame = CLASSES_STRUCTS["countr_class_set"], OVERLAY_STRUCTS["countr_overlay_frame"]
+TracksStream, FlowMap = TRACKS_STRUCTS["countr_tracks_stream"], FLOW_STRUCTS["countr_flow_map"]

@@ -14,6 +14,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "../csrc/common.hpp"
+#include "../csrc/host_api.hpp"
 #include "../../include/countr_hip_classes.h"
 
 namespace {
@@ -160,21 +161,9 @@ __global__ __launch_bounds__(64) void class_fold_sum_kernel(const FoldArgs a, co
   }
 }
 
-thread_local char g_err[512] = "";
-
-int fail(int rc, const char* msg) {
-  strncpy(g_err, msg, sizeof(g_err) - 1);
-  g_err[sizeof(g_err) - 1] = 0;
-  return rc;
-}
-
 // the part of a call that its sizes decide: strips and the four-pixel path.  -> the number of blocks (= partials), or < 0
 int layout(const countr_class_set* sets, int nsets, FoldArgs* a, const char* who) {
-  char buf[256];
-  if (!sets || nsets < 1 || nsets > MAX_SETS) {
-    snprintf(buf, sizeof(buf), "%s: bad args (1..16 sets a call)", who);
-    return fail(-1, buf);
-  }
+  if (!sets || nsets < 1 || nsets > MAX_SETS) return failf(-1, "%s: bad args (1..16 sets a call)", who);
   int blocks = 0;
   for (int s = 0; s < MAX_SETS; ++s) {
     if (s >= nsets) {
@@ -182,14 +171,9 @@ int layout(const countr_class_set* sets, int nsets, FoldArgs* a, const char* who
       continue;
     }
     const countr_class_set& d = sets[s];
-    if (d.nc < 1 || d.nc > NC) {
-      snprintf(buf, sizeof(buf), "%s: set %d: a set has 1..16 classes, got %d", who, s, d.nc);
-      return fail(-1, buf);
-    }
-    if (d.h < 1 || d.w < 1 || (int64_t)d.h * d.w > (int64_t)1 << 28) {
-      snprintf(buf, sizeof(buf), "%s: set %d: a map has 1 .. 2^28 pixels, got %d x %d", who, s, d.h, d.w);
-      return fail(-1, buf);
-    }
+    if (d.nc < 1 || d.nc > NC) return failf(-1, "%s: set %d: a set has 1..16 classes, got %d", who, s, d.nc);
+    if (d.h < 1 || d.w < 1 || (int64_t)d.h * d.w > (int64_t)1 << 28)
+      return failf(-1, "%s: set %d: a map has 1 .. 2^28 pixels, got %d x %d", who, s, d.h, d.w);
     const int per = (d.h + MAX_STRIPS - 1) / MAX_STRIPS;
     const int rows = per > MIN_ROWS ? per : MIN_ROWS;
     int vec = (((int64_t)rows * d.w) & 3) == 0 && (((uintptr_t)d.labels) & 3) == 0;
@@ -224,29 +208,17 @@ extern "C" int countr_class_fold(const countr_class_set* sets, int nsets, const 
       (((uintptr_t)won) & 3) || (((uintptr_t)total) & 3) || (((uintptr_t)area) & 3))
     return fail(-1, "countr_class_fold: sets_dev (8-byte aligned), won, total, area and a workspace are required");
   if (!__builtin_isfinite(floor)) return fail(-1, "countr_class_fold: floor is finite");
-  char buf[256];
   for (int s = 0; s < nsets; ++s) {
     const countr_class_set& d = sets[s];
-    if (!d.labels) { snprintf(buf, sizeof(buf), "countr_class_fold: set %d: no label map", s); return fail(-1, buf); }
+    if (!d.labels) return failf(-1, "countr_class_fold: set %d: no label map", s);
     for (int c = 0; c < d.nc; ++c) {
-      if (!d.map[c] || (((uintptr_t)d.map[c]) & 3)) {
-        snprintf(buf, sizeof(buf), "countr_class_fold: set %d: map %d: null or misaligned", s, c);
-        return fail(-1, buf);
-      }
-      if (!__builtin_isfinite(d.scale[c])) {
-        snprintf(buf, sizeof(buf), "countr_class_fold: set %d: scale %d is not finite", s, c);
-        return fail(-1, buf);
-      }
+      if (!d.map[c] || (((uintptr_t)d.map[c]) & 3)) return failf(-1, "countr_class_fold: set %d: map %d: null or misaligned", s, c);
+      if (!__builtin_isfinite(d.scale[c])) return failf(-1, "countr_class_fold: set %d: scale %d is not finite", s, c);
     }
   }
   float* part = (float*)workspace;
   hipLaunchKernelGGL(class_fold_strip_kernel, dim3((unsigned)blocks), dim3(256), 0, STREAM(stream), a,
                      (const countr_class_set*)sets_dev, floor, part, nsets);
   hipLaunchKernelGGL(class_fold_sum_kernel, dim3((unsigned)nsets), dim3(64), 0, STREAM(stream), a, part, won, total, area);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(buf, sizeof(buf), "countr_class_fold: launch failed: %s", hipGetErrorString(e));
-    return fail(-10, buf);
-  }
-  return 0;
+  return launched("countr_class_fold");
 }

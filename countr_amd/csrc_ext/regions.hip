@@ -16,6 +16,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "../csrc/common.hpp"
+#include "../csrc/host_api.hpp"
 #include "../../include/countr_hip_ext.h"
 
 namespace {
@@ -270,21 +271,10 @@ __global__ __launch_bounds__(256) void regions_fold_kernel(const RegionArgs a, c
   else { mass[a.slot0[s] + k] = sm_; area[a.slot0[s] + k] = sa; }
 }
 
-thread_local char g_err[512] = "";
-
-int fail(int rc, const char* msg) {
-  strncpy(g_err, msg, sizeof(g_err) - 1);
-  g_err[sizeof(g_err) - 1] = 0;
-  return rc;
-}
-
 // the part of a call that its sizes decide: strips, partial offsets, slots.  -> the number of partials, or < 0
 int64_t layout(const countr_region_map* maps, int n, const countr_region* regions, int nregions, int nsets, RegionArgs* a, const char* who) {
-  char buf[256];
-  if (!maps || n < 1 || n > MAX_MAPS || nsets < 1 || nsets > MAX_MAPS || nregions < 0 || nregions > MAX_REG || (nregions && !regions)) {
-    snprintf(buf, sizeof(buf), "%s: bad args (1..16 maps, 1..16 sets, at most 64 polygons and 16 grids)", who);
-    return fail(-1, buf);
-  }
+  if (!maps || n < 1 || n > MAX_MAPS || nsets < 1 || nsets > MAX_MAPS || nregions < 0 || nregions > MAX_REG || (nregions && !regions))
+    return failf(-1, "%s: bad args (1..16 maps, 1..16 sets, at most 64 polygons and 16 grids)", who);
   int polys = 0, grids = 0, slots = 0, r = 0;
   for (int s = 0; s <= MAX_MAPS; ++s) {
     a->first[s] = r; a->slot0[s] = slots;
@@ -293,28 +283,18 @@ int64_t layout(const countr_region_map* maps, int n, const countr_region* region
       const countr_region& d = regions[r];
       a->nv[r] = d.nv; a->gy[r] = d.gy; a->gx[r] = d.gx; a->data[r] = d.data; a->slot[r] = slots;
       if (d.nv == 0) {
-        if (d.gy < 1 || d.gx < 1 || (int64_t)d.gy * d.gx > MAX_CELLS) {
-          snprintf(buf, sizeof(buf), "%s: region %d: a grid has gy, gx >= 1 and at most 256 cells", who, r);
-          return fail(-1, buf);
-        }
+        if (d.gy < 1 || d.gx < 1 || (int64_t)d.gy * d.gx > MAX_CELLS)
+          return failf(-1, "%s: region %d: a grid has gy, gx >= 1 and at most 256 cells", who, r);
         ++grids; slots += d.gy * d.gx;
       } else {
-        if (d.nv < 3 || d.nv > MAX_NV) {
-          snprintf(buf, sizeof(buf), "%s: region %d: a polygon has 3..64 vertices, got %d", who, r, d.nv);
-          return fail(-1, buf);
-        }
+        if (d.nv < 3 || d.nv > MAX_NV) return failf(-1, "%s: region %d: a polygon has 3..64 vertices, got %d", who, r, d.nv);
         ++polys; slots += 1;
       }
     }
   }
-  if (r != nregions) {
-    snprintf(buf, sizeof(buf), "%s: region %d: the regions are sorted by set, sets are 0..%d", who, r, nsets - 1);
-    return fail(-1, buf);
-  }
-  if (polys > MAX_POLY || grids > MAX_MAPS) {
-    snprintf(buf, sizeof(buf), "%s: %d polygons and %d grids: a call takes at most 64 and 16", who, polys, grids);
-    return fail(-1, buf);
-  }
+  if (r != nregions) return failf(-1, "%s: region %d: the regions are sorted by set, sets are 0..%d", who, r, nsets - 1);
+  if (polys > MAX_POLY || grids > MAX_MAPS)
+    return failf(-1, "%s: %d polygons and %d grids: a call takes at most 64 and 16", who, polys, grids);
   for (int r2 = nregions; r2 < MAX_REG; ++r2) a->nv[r2] = a->gy[r2] = a->gx[r2] = a->data[r2] = a->slot[r2] = 0;
   int64_t parts = 0;
   int blocks = 0;
@@ -324,10 +304,8 @@ int64_t layout(const countr_region_map* maps, int n, const countr_region* region
       continue;
     }
     const countr_region_map& d = maps[i];
-    if (d.h < 1 || d.w < 1 || (int64_t)d.h * d.w > (int64_t)1 << 28 || d.set < 0 || d.set >= nsets) {
-      snprintf(buf, sizeof(buf), "%s: map %d: a map has 1 .. 2^28 pixels and a set in 0..%d", who, i, nsets - 1);
-      return fail(-1, buf);
-    }
+    if (d.h < 1 || d.w < 1 || (int64_t)d.h * d.w > (int64_t)1 << 28 || d.set < 0 || d.set >= nsets)
+      return failf(-1, "%s: map %d: a map has 1 .. 2^28 pixels and a set in 0..%d", who, i, nsets - 1);
     const int per = (d.h + MAX_STRIPS - 1) / MAX_STRIPS;
     const int rows = per > MIN_ROWS ? per : MIN_ROWS;
     const int strips = (d.h + rows - 1) / rows;
@@ -362,30 +340,24 @@ extern "C" int countr_region_sums(const countr_region_map* maps, int n, const co
   if (!data_host || !data || ndata < 4 || !mass || !area || !total || !workspace || (((uintptr_t)data) & 7) || (((uintptr_t)workspace) & 3) ||
       (((uintptr_t)mass) & 3) || (((uintptr_t)area) & 3) || (((uintptr_t)total) & 3))
     return fail(-1, "countr_region_sums: data_host, data (8-byte aligned), mass, area, total and a workspace are required");
-  char buf[256];
   for (int i = 0; i < n; ++i) {
     const countr_region_map& d = maps[i];
-    if (!d.map || (((uintptr_t)d.map) & 3)) { snprintf(buf, sizeof(buf), "countr_region_sums: map %d: null or misaligned", i); return fail(-1, buf); }
-    if (d.place < 0 || d.place > ndata - 4) { snprintf(buf, sizeof(buf), "countr_region_sums: map %d: its placement lies outside data", i); return fail(-1, buf); }
+    if (!d.map || (((uintptr_t)d.map) & 3)) return failf(-1, "countr_region_sums: map %d: null or misaligned", i);
+    if (d.place < 0 || d.place > ndata - 4) return failf(-1, "countr_region_sums: map %d: its placement lies outside data", i);
     const double* p = data_host + d.place;
-    if (!(p[0] > 0.0 && p[2] > 0.0 && __builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) && __builtin_isfinite(p[2]) && __builtin_isfinite(p[3]))) {
-      snprintf(buf, sizeof(buf), "countr_region_sums: map %d: a placement is finite with ax > 0 and ay > 0", i);
-      return fail(-1, buf);
-    }
+    if (!(p[0] > 0.0 && p[2] > 0.0 && __builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) && __builtin_isfinite(p[2]) && __builtin_isfinite(p[3])))
+      return failf(-1, "countr_region_sums: map %d: a placement is finite with ax > 0 and ay > 0", i);
   }
   for (int r = 0; r < nregions; ++r) {
     const countr_region& d = regions[r];
     const int len = d.nv ? 2 * d.nv : d.gy + d.gx + 2;
-    if (d.data < 0 || d.data > ndata - len) { snprintf(buf, sizeof(buf), "countr_region_sums: region %d: its data lies outside data", r); return fail(-1, buf); }
+    if (d.data < 0 || d.data > ndata - len) return failf(-1, "countr_region_sums: region %d: its data lies outside data", r);
     const double* p = data_host + d.data;
     for (int k = 0; k < len; ++k)
-      if (!__builtin_isfinite(p[k])) { snprintf(buf, sizeof(buf), "countr_region_sums: region %d: a coordinate is not finite", r); return fail(-1, buf); }
+      if (!__builtin_isfinite(p[k])) return failf(-1, "countr_region_sums: region %d: a coordinate is not finite", r);
     if (d.nv == 0) {
       for (int k = 0; k < len - 1; ++k)
-        if (k != d.gy && !(p[k] < p[k + 1])) {
-          snprintf(buf, sizeof(buf), "countr_region_sums: region %d: grid boundaries are strictly increasing", r);
-          return fail(-1, buf);
-        }
+        if (k != d.gy && !(p[k] < p[k + 1])) return failf(-1, "countr_region_sums: region %d: grid boundaries are strictly increasing", r);
     }
   }
   float* pmass = (float*)workspace;
@@ -395,10 +367,5 @@ extern "C" int countr_region_sums(const countr_region_map* maps, int n, const co
     if (a.slot0[s + 1] - a.slot0[s] + 1 > maxS) maxS = a.slot0[s + 1] - a.slot0[s] + 1;
   hipLaunchKernelGGL(regions_strip_kernel, dim3((unsigned)a.blk_off[MAX_MAPS]), dim3(256), 0, STREAM(stream), a, data, pmass, parea, n);
   hipLaunchKernelGGL(regions_fold_kernel, dim3((maxS + 255) / 256, nsets), dim3(256), 0, STREAM(stream), a, pmass, parea, mass, area, total, n);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(buf, sizeof(buf), "countr_region_sums: launch failed: %s", hipGetErrorString(e));
-    return fail(-10, buf);
-  }
-  return 0;
+  return launched("countr_region_sums");
 }

@@ -20,6 +20,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "../csrc/common.hpp"
+#include "../csrc/host_api.hpp"
 #include "../../include/countr_hip_flow.h"
 
 #pragma clang fp contract(off)
@@ -245,37 +246,14 @@ __global__ __launch_bounds__(64) void flow_fold_kernel(const FluxArgs a, const f
   a.out[f][k] = s;
 }
 
-thread_local char g_err[512] = "";
-
-int fail(int rc, const char* msg) {
-  strncpy(g_err, msg, sizeof(g_err) - 1);
-  g_err[sizeof(g_err) - 1] = 0;
-  return rc;
-}
-
-inline bool misaligned(const void* p, uintptr_t a) { return (((uintptr_t)p) & (a - 1)) != 0; }
 inline bool bad_side(int v) { return v < CELL || v > MAX_SIDE || v % CELL != 0; }
 
 // the checks every call shares: the count and the sizes
 int check_sizes(const char* who, int n, int h, int w) {
-  char buf[256];
-  if (n < 1 || n > MAXF) {
-    snprintf(buf, sizeof(buf), "%s: 1..%d frames a call, got %d", who, MAXF, n);
-    return fail(-1, buf);
-  }
-  if (bad_side(h) || bad_side(w)) {
-    snprintf(buf, sizeof(buf), "%s: h and w are multiples of %d in %d..%d, got %d x %d", who, CELL, CELL, MAX_SIDE, h, w);
-    return fail(-3, buf);
-  }
+  if (n < 1 || n > MAXF) return failf(-1, "%s: 1..%d frames a call, got %d", who, MAXF, n);
+  if (bad_side(h) || bad_side(w))
+    return failf(-3, "%s: h and w are multiples of %d in %d..%d, got %d x %d", who, CELL, CELL, MAX_SIDE, h, w);
   return 0;
-}
-
-int launched(const char* who) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return 0;
-  char buf[256];
-  snprintf(buf, sizeof(buf), "%s: launch failed: %s", who, hipGetErrorString(e));
-  return fail(-10, buf);
 }
 
 }  // namespace
@@ -285,31 +263,22 @@ extern "C" int countr_flow_version(void) { return COUNTR_FLOW_ABI_VERSION; }
 extern "C" const char* countr_flow_last_error(void) { return g_err; }
 
 extern "C" int countr_flow_workspace(int n, int h) {
-  char buf[256];
-  if (n < 1 || n > MAXF || bad_side(h)) {
-    snprintf(buf, sizeof(buf), "countr_flow_workspace: 1..%d maps of a height that is a multiple of %d in %d..%d, got %d of %d", MAXF, CELL, CELL,
-             MAX_SIDE, n, h);
-    return fail(-1, buf);
-  }
+  if (n < 1 || n > MAXF || bad_side(h))
+    return failf(-1, "countr_flow_workspace: 1..%d maps of a height that is a multiple of %d in %d..%d, got %d of %d", MAXF, CELL, CELL,
+                 MAX_SIDE, n, h);
   return n * (h / CELL) * OUTF * 4;
 }
 
 extern "C" int countr_flow_luma(const void* const* images, void* const* lumas, int n, int h, int w, void* stream) {
-  char buf[256];
   const int rc = check_sizes("countr_flow_luma", n, h, w);
   if (rc) return rc;
   if (!images || !lumas) return fail(-2, "countr_flow_luma: the images and lumas arrays are required");
   LumaArgs a;
   memset(&a, 0, sizeof(a));
   for (int k = 0; k < n; ++k) {
-    if (!images[k] || !lumas[k]) {
-      snprintf(buf, sizeof(buf), "countr_flow_luma: frame %d has a null pointer", k);
-      return fail(-2, buf);
-    }
-    if (misaligned(images[k], 16) || misaligned(lumas[k], 4)) {
-      snprintf(buf, sizeof(buf), "countr_flow_luma: frame %d: the image is 16-byte aligned, the luma 4-byte aligned", k);
-      return fail(-5, buf);
-    }
+    if (!images[k] || !lumas[k]) return failf(-2, "countr_flow_luma: frame %d has a null pointer", k);
+    if (misaligned(images[k], 16) || misaligned(lumas[k], 4))
+      return failf(-5, "countr_flow_luma: frame %d: the image is 16-byte aligned, the luma 4-byte aligned", k);
     a.img[k] = (const float*)images[k];
     a.luma[k] = (unsigned char*)lumas[k];
   }
@@ -320,29 +289,16 @@ extern "C" int countr_flow_luma(const void* const* images, void* const* lumas, i
 
 extern "C" int countr_flow_motion(const void* const* current, const void* const* earlier, void* const* motion, int n, int h, int w,
                                   int search, int min_gain, void* stream) {
-  char buf[256];
   const int rc = check_sizes("countr_flow_motion", n, h, w);
   if (rc) return rc;
-  if (search < 1 || search > MAXR) {
-    snprintf(buf, sizeof(buf), "countr_flow_motion: search is 1..%d, got %d", MAXR, search);
-    return fail(-3, buf);
-  }
-  if (min_gain < 0) {
-    snprintf(buf, sizeof(buf), "countr_flow_motion: min_gain is >= 0, got %d", min_gain);
-    return fail(-3, buf);
-  }
+  if (search < 1 || search > MAXR) return failf(-3, "countr_flow_motion: search is 1..%d, got %d", MAXR, search);
+  if (min_gain < 0) return failf(-3, "countr_flow_motion: min_gain is >= 0, got %d", min_gain);
   if (!current || !earlier || !motion) return fail(-2, "countr_flow_motion: the current, earlier and motion arrays are required");
   MotionArgs a;
   memset(&a, 0, sizeof(a));
   for (int k = 0; k < n; ++k) {
-    if (!current[k] || !earlier[k] || !motion[k]) {
-      snprintf(buf, sizeof(buf), "countr_flow_motion: pair %d has a null pointer", k);
-      return fail(-2, buf);
-    }
-    if (misaligned(motion[k], 4)) {
-      snprintf(buf, sizeof(buf), "countr_flow_motion: pair %d: the motion field is 4-byte aligned", k);
-      return fail(-5, buf);
-    }
+    if (!current[k] || !earlier[k] || !motion[k]) return failf(-2, "countr_flow_motion: pair %d has a null pointer", k);
+    if (misaligned(motion[k], 4)) return failf(-5, "countr_flow_motion: pair %d: the motion field is 4-byte aligned", k);
     a.cur[k] = (const unsigned char*)current[k];
     a.old[k] = (const unsigned char*)earlier[k];
     a.mv[k] = (unsigned*)motion[k];
@@ -354,17 +310,11 @@ extern "C" int countr_flow_motion(const void* const* current, const void* const*
 
 extern "C" int countr_flow_flux(const countr_flow_map* maps, int n, int h, int w, const double* lines, int L, double band, int interval,
                                 void* workspace, void* stream) {
-  char buf[256];
   const int rc = check_sizes("countr_flow_flux", n, h, w);
   if (rc) return rc;
-  if (L < 0 || L > MAXL) {
-    snprintf(buf, sizeof(buf), "countr_flow_flux: 0..%d lines, got %d", MAXL, L);
-    return fail(-3, buf);
-  }
-  if (interval < 1 || interval > COUNTR_FLOW_MAX_INTERVAL) {
-    snprintf(buf, sizeof(buf), "countr_flow_flux: interval is 1..%d, got %d", COUNTR_FLOW_MAX_INTERVAL, interval);
-    return fail(-3, buf);
-  }
+  if (L < 0 || L > MAXL) return failf(-3, "countr_flow_flux: 0..%d lines, got %d", MAXL, L);
+  if (interval < 1 || interval > COUNTR_FLOW_MAX_INTERVAL)
+    return failf(-3, "countr_flow_flux: interval is 1..%d, got %d", COUNTR_FLOW_MAX_INTERVAL, interval);
   if (!(band > 0.0) || !__builtin_isfinite(band)) return fail(-4, "countr_flow_flux: band is finite and > 0");
   if (!maps) return fail(-2, "countr_flow_flux: the maps array is required");
   if (L > 0 && !lines) return fail(-2, "countr_flow_flux: the lines array is required");
@@ -373,27 +323,18 @@ extern "C" int countr_flow_flux(const countr_flow_map* maps, int n, int h, int w
   memset(&a, 0, sizeof(a));
   for (int k = 0; k < n; ++k) {
     const countr_flow_map& d = maps[k];
-    if (!d.map || !d.motion || !d.out) {
-      snprintf(buf, sizeof(buf), "countr_flow_flux: map %d has a null pointer", k);
-      return fail(-2, buf);
-    }
-    if (misaligned(d.map, 4) || misaligned(d.motion, 4) || misaligned(d.out, 4)) {
-      snprintf(buf, sizeof(buf), "countr_flow_flux: map %d: map, motion and out are 4-byte aligned", k);
-      return fail(-5, buf);
-    }
-    if (!(d.sx > 0.0 && d.sy > 0.0 && __builtin_isfinite(d.sx) && __builtin_isfinite(d.tx) && __builtin_isfinite(d.sy) && __builtin_isfinite(d.ty))) {
-      snprintf(buf, sizeof(buf), "countr_flow_flux: map %d: a placement is finite with sx > 0 and sy > 0", k);
-      return fail(-4, buf);
-    }
+    if (!d.map || !d.motion || !d.out) return failf(-2, "countr_flow_flux: map %d has a null pointer", k);
+    if (misaligned(d.map, 4) || misaligned(d.motion, 4) || misaligned(d.out, 4))
+      return failf(-5, "countr_flow_flux: map %d: map, motion and out are 4-byte aligned", k);
+    if (!(d.sx > 0.0 && d.sy > 0.0 && __builtin_isfinite(d.sx) && __builtin_isfinite(d.tx) && __builtin_isfinite(d.sy) && __builtin_isfinite(d.ty)))
+      return failf(-4, "countr_flow_flux: map %d: a placement is finite with sx > 0 and sy > 0", k);
     a.map[k] = (const float*)d.map; a.mv[k] = (const short2*)d.motion; a.out[k] = (float*)d.out;
     a.sx[k] = d.sx; a.tx[k] = d.tx; a.sy[k] = d.sy; a.ty[k] = d.ty;
   }
   for (int k = 0; k < L; ++k) {
     const double* p = lines + 4 * k;
-    if (!(__builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) && __builtin_isfinite(p[2]) && __builtin_isfinite(p[3]))) {
-      snprintf(buf, sizeof(buf), "countr_flow_flux: line %d: a coordinate is not finite", k);
-      return fail(-4, buf);
-    }
+    if (!(__builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) && __builtin_isfinite(p[2]) && __builtin_isfinite(p[3])))
+      return failf(-4, "countr_flow_flux: line %d: a coordinate is not finite", k);
     // the header's e, len2, len and hw: fp64, one operation per statement
     const double ex = p[2] - p[0], ey = p[3] - p[1];
     const double xx = ex * ex, yy = ey * ey;
@@ -401,10 +342,8 @@ extern "C" int countr_flow_flux(const countr_flow_map* maps, int n, int h, int w
     const double len = sqrt(len2);
     const double half = band / 2.0;
     const double hw = half * len;
-    if (!__builtin_isfinite(len2) || !__builtin_isfinite(hw)) {
-      snprintf(buf, sizeof(buf), "countr_flow_flux: line %d: its squared length and band are finite", k);
-      return fail(-4, buf);
-    }
+    if (!__builtin_isfinite(len2) || !__builtin_isfinite(hw))
+      return failf(-4, "countr_flow_flux: line %d: its squared length and band are finite", k);
     a.ax[k] = p[0]; a.ay[k] = p[1]; a.ex[k] = ex; a.ey[k] = ey; a.len[k] = len; a.len2[k] = len2; a.hw[k] = hw;
   }
   a.band = band;

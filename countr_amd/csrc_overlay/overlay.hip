@@ -21,6 +21,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "../csrc/common.hpp"
+#include "../csrc/host_api.hpp"
 #include "../../include/countr_hip_overlay.h"
 
 namespace {
@@ -351,14 +352,6 @@ __global__ __launch_bounds__(BX * BY) void yuv_kernel(const OvArgs a) {
   }
 }
 
-thread_local char g_err[512] = "";
-
-int fail(int rc, const char* msg) {
-  strncpy(g_err, msg, sizeof(g_err) - 1);
-  g_err[sizeof(g_err) - 1] = 0;
-  return rc;
-}
-
 // yr, yg, yb, yoff, ur, ug, ub, vr, vg, vb of [matrix][range] (the header's table)
 const int COEF[2][2][10] = {{{66, 129, 25, 16, -38, -74, 112, 112, -94, -18}, {77, 150, 29, 0, -43, -85, 128, 128, -107, -21}},
                             {{47, 157, 16, 16, -26, -86, 112, 112, -102, -10}, {54, 184, 18, 0, -29, -99, 128, 128, -116, -12}}};
@@ -375,100 +368,56 @@ extern "C" const char* countr_overlay_last_error(void) { return g_err; }
 extern "C" int countr_overlay_render(const countr_overlay_frame* frames, int n, int H, int W, int mh, int mw, const void* pack, int pack_bytes,
                                      int point_radius, int point_rgb, int edge_rgb, int format, int matrix, int range, void* maxbits,
                                      void* stream) {
-  char buf[256];
-  if (n < 1 || n > MAXF) {
-    snprintf(buf, sizeof(buf), "countr_overlay_render: 1..%d frames a call, got %d", MAXF, n);
-    return fail(-1, buf);
-  }
-  if (format < COUNTR_OVERLAY_RGB || format > COUNTR_OVERLAY_I420) {
-    snprintf(buf, sizeof(buf), "countr_overlay_render: unknown format %d", format);
-    return fail(-1, buf);
-  }
-  if (matrix != COUNTR_OVERLAY_BT601 && matrix != COUNTR_OVERLAY_BT709) {
-    snprintf(buf, sizeof(buf), "countr_overlay_render: unknown matrix %d", matrix);
-    return fail(-1, buf);
-  }
-  if (range != COUNTR_OVERLAY_LIMITED && range != COUNTR_OVERLAY_FULL) {
-    snprintf(buf, sizeof(buf), "countr_overlay_render: unknown range %d", range);
-    return fail(-1, buf);
-  }
-  if (H < 1 || H > COUNTR_OVERLAY_MAX_SIDE || W < 1 || W > COUNTR_OVERLAY_MAX_SIDE) {
-    snprintf(buf, sizeof(buf), "countr_overlay_render: H and W are 1..%d, got %d x %d", COUNTR_OVERLAY_MAX_SIDE, H, W);
-    return fail(-1, buf);
-  }
-  if (mh < 1 || mh > COUNTR_OVERLAY_MAX_SIDE || mw < 1 || mw > COUNTR_OVERLAY_MAX_SIDE) {
-    snprintf(buf, sizeof(buf), "countr_overlay_render: mh and mw are 1..%d, got %d x %d", COUNTR_OVERLAY_MAX_SIDE, mh, mw);
-    return fail(-1, buf);
-  }
-  if (point_radius < 0 || point_radius > COUNTR_OVERLAY_MAX_RADIUS) {
-    snprintf(buf, sizeof(buf), "countr_overlay_render: point_radius is 0..%d, got %d", COUNTR_OVERLAY_MAX_RADIUS, point_radius);
-    return fail(-1, buf);
-  }
+  if (n < 1 || n > MAXF) return failf(-1, "countr_overlay_render: 1..%d frames a call, got %d", MAXF, n);
+  if (format < COUNTR_OVERLAY_RGB || format > COUNTR_OVERLAY_I420) return failf(-1, "countr_overlay_render: unknown format %d", format);
+  if (matrix != COUNTR_OVERLAY_BT601 && matrix != COUNTR_OVERLAY_BT709)
+    return failf(-1, "countr_overlay_render: unknown matrix %d", matrix);
+  if (range != COUNTR_OVERLAY_LIMITED && range != COUNTR_OVERLAY_FULL) return failf(-1, "countr_overlay_render: unknown range %d", range);
+  if (H < 1 || H > COUNTR_OVERLAY_MAX_SIDE || W < 1 || W > COUNTR_OVERLAY_MAX_SIDE)
+    return failf(-1, "countr_overlay_render: H and W are 1..%d, got %d x %d", COUNTR_OVERLAY_MAX_SIDE, H, W);
+  if (mh < 1 || mh > COUNTR_OVERLAY_MAX_SIDE || mw < 1 || mw > COUNTR_OVERLAY_MAX_SIDE)
+    return failf(-1, "countr_overlay_render: mh and mw are 1..%d, got %d x %d", COUNTR_OVERLAY_MAX_SIDE, mh, mw);
+  if (point_radius < 0 || point_radius > COUNTR_OVERLAY_MAX_RADIUS)
+    return failf(-1, "countr_overlay_render: point_radius is 0..%d, got %d", COUNTR_OVERLAY_MAX_RADIUS, point_radius);
   if (!frames) return fail(-1, "countr_overlay_render: the frames array is required");
   if (!pack || ((uintptr_t)pack & 15)) return fail(-1, "countr_overlay_render: the packed upload is required, 16-byte aligned");
-  if (pack_bytes < COUNTR_OVERLAY_PACK_HEAD) {
-    snprintf(buf, sizeof(buf), "countr_overlay_render: the packed upload has at least %d bytes, got %d", COUNTR_OVERLAY_PACK_HEAD, pack_bytes);
-    return fail(-1, buf);
-  }
+  if (pack_bytes < COUNTR_OVERLAY_PACK_HEAD)
+    return failf(-1, "countr_overlay_render: the packed upload has at least %d bytes, got %d", COUNTR_OVERLAY_PACK_HEAD, pack_bytes);
   OvArgs a;
   memset(&a, 0, sizeof(a));
   uintptr_t bits = (uintptr_t)W;
   int max_points = 0, max_edges = 0, max_patch = 0;
   for (int j = 0; j < n; ++j) {
     const countr_overlay_frame& fr = frames[j];
-    if (!fr.rgb || !fr.map || !fr.out || (format != COUNTR_OVERLAY_RGB && !fr.yuv)) {
-      snprintf(buf, sizeof(buf), "countr_overlay_render: frame %d has a null pointer", j);
-      return fail(-1, buf);
-    }
-    if (format == COUNTR_OVERLAY_RGB && fr.yuv) {
-      snprintf(buf, sizeof(buf), "countr_overlay_render: frame %d: yuv must be NULL when the format is RGB", j);
-      return fail(-1, buf);
-    }
-    if ((uintptr_t)fr.map & 3) {
-      snprintf(buf, sizeof(buf), "countr_overlay_render: frame %d: the map is 4-byte aligned", j);
-      return fail(-1, buf);
-    }
-    if (fr.n_points < 0 || fr.n_points > COUNTR_OVERLAY_MAX_POINTS) {
-      snprintf(buf, sizeof(buf), "countr_overlay_render: frame %d: 0..%d points, got %d", j, COUNTR_OVERLAY_MAX_POINTS, fr.n_points);
-      return fail(-1, buf);
-    }
-    if (fr.n_polys < 0 || fr.n_polys > COUNTR_OVERLAY_MAX_POLYGONS) {
-      snprintf(buf, sizeof(buf), "countr_overlay_render: frame %d: 0..%d polygons, got %d", j, COUNTR_OVERLAY_MAX_POLYGONS, fr.n_polys);
-      return fail(-1, buf);
-    }
-    if (fr.n_polys > 0 && !fr.poly_verts) {
-      snprintf(buf, sizeof(buf), "countr_overlay_render: frame %d has polygons and no poly_verts", j);
-      return fail(-1, buf);
-    }
+    if (!fr.rgb || !fr.map || !fr.out || (format != COUNTR_OVERLAY_RGB && !fr.yuv))
+      return failf(-1, "countr_overlay_render: frame %d has a null pointer", j);
+    if (format == COUNTR_OVERLAY_RGB && fr.yuv)
+      return failf(-1, "countr_overlay_render: frame %d: yuv must be NULL when the format is RGB", j);
+    if ((uintptr_t)fr.map & 3) return failf(-1, "countr_overlay_render: frame %d: the map is 4-byte aligned", j);
+    if (fr.n_points < 0 || fr.n_points > COUNTR_OVERLAY_MAX_POINTS)
+      return failf(-1, "countr_overlay_render: frame %d: 0..%d points, got %d", j, COUNTR_OVERLAY_MAX_POINTS, fr.n_points);
+    if (fr.n_polys < 0 || fr.n_polys > COUNTR_OVERLAY_MAX_POLYGONS)
+      return failf(-1, "countr_overlay_render: frame %d: 0..%d polygons, got %d", j, COUNTR_OVERLAY_MAX_POLYGONS, fr.n_polys);
+    if (fr.n_polys > 0 && !fr.poly_verts) return failf(-1, "countr_overlay_render: frame %d has polygons and no poly_verts", j);
     int edges = 0;
     for (int p = 0; p < fr.n_polys; ++p) {
       const int nv = static_cast<const int*>(fr.poly_verts)[p];
-      if (nv < 1 || nv > COUNTR_OVERLAY_MAX_VERTICES) {
-        snprintf(buf, sizeof(buf), "countr_overlay_render: frame %d polygon %d: 1..%d vertices, got %d", j, p, COUNTR_OVERLAY_MAX_VERTICES, nv);
-        return fail(-1, buf);
-      }
+      if (nv < 1 || nv > COUNTR_OVERLAY_MAX_VERTICES)
+        return failf(-1, "countr_overlay_render: frame %d polygon %d: 1..%d vertices, got %d", j, p, COUNTR_OVERLAY_MAX_VERTICES, nv);
       edges += nv;
     }
-    if (fr.n_edges != edges) {
-      snprintf(buf, sizeof(buf), "countr_overlay_render: frame %d: n_edges %d, its polygons have %d vertices", j, fr.n_edges, edges);
-      return fail(-1, buf);
-    }
-    if (fr.lh < 0 || fr.lh > COUNTR_OVERLAY_PATCH_H || fr.lw < 0 || fr.lw > COUNTR_OVERLAY_PATCH_W || (fr.lh == 0) != (fr.lw == 0)) {
-      snprintf(buf, sizeof(buf), "countr_overlay_render: frame %d: a label patch is at most %d x %d (0 x 0: none), got %d x %d", j,
-               COUNTR_OVERLAY_PATCH_H, COUNTR_OVERLAY_PATCH_W, fr.lh, fr.lw);
-      return fail(-1, buf);
-    }
-    if (fr.lh && (fr.lx < -COORD || fr.lx > COORD || fr.ly < -COORD || fr.ly > COORD)) {
-      snprintf(buf, sizeof(buf), "countr_overlay_render: frame %d: the label's position is within +-%d, got (%d, %d)", j, COORD, fr.lx, fr.ly);
-      return fail(-1, buf);
-    }
+    if (fr.n_edges != edges)
+      return failf(-1, "countr_overlay_render: frame %d: n_edges %d, its polygons have %d vertices", j, fr.n_edges, edges);
+    if (fr.lh < 0 || fr.lh > COUNTR_OVERLAY_PATCH_H || fr.lw < 0 || fr.lw > COUNTR_OVERLAY_PATCH_W || (fr.lh == 0) != (fr.lw == 0))
+      return failf(-1, "countr_overlay_render: frame %d: a label patch is at most %d x %d (0 x 0: none), got %d x %d", j,
+                   COUNTR_OVERLAY_PATCH_H, COUNTR_OVERLAY_PATCH_W, fr.lh, fr.lw);
+    if (fr.lh && (fr.lx < -COORD || fr.lx > COORD || fr.ly < -COORD || fr.ly > COORD))
+      return failf(-1, "countr_overlay_render: frame %d: the label's position is within +-%d, got (%d, %d)", j, COORD, fr.lx, fr.ly);
     if ((fr.n_points && (!inside(fr.points_off, 8ll * fr.n_points, pack_bytes) || (fr.points_off & 3))) ||
         (fr.n_edges && (!inside(fr.edges_off, 16ll * fr.n_edges, pack_bytes) || (fr.edges_off & 3))) ||
-        (fr.lh && !inside(fr.patch_off, (int64_t)fr.lh * fr.lw, pack_bytes))) {
-      snprintf(buf, sizeof(buf), "countr_overlay_render: frame %d: an offset lies outside the packed upload of %d bytes (or is not 4-byte aligned)",
-               j, pack_bytes);
-      return fail(-1, buf);
-    }
+        (fr.lh && !inside(fr.patch_off, (int64_t)fr.lh * fr.lw, pack_bytes)))
+      return failf(-1, "countr_overlay_render: frame %d: an offset lies outside the packed upload of %d bytes (or is not 4-byte aligned)",
+                   j, pack_bytes);
     if (fr.gain_max) {
       if (!maxbits || ((uintptr_t)maxbits & 3)) return fail(-1, "countr_overlay_render: maxbits (n device uint32) is required when a frame has gain_max");
       a.gain_max |= 1u << j;
@@ -496,10 +445,7 @@ extern "C" int countr_overlay_render(const countr_overlay_frame* frames, int n, 
   hipError_t e = hipSuccess;
   if (a.gain_max) {
     e = hipMemsetAsync(maxbits, 0, sizeof(uint32_t) * n, st);
-    if (e != hipSuccess) {
-      snprintf(buf, sizeof(buf), "countr_overlay_render: memset failed: %s", hipGetErrorString(e));
-      return fail(-10, buf);
-    }
+    if (e != hipSuccess) return failf(-10, "countr_overlay_render: memset failed: %s", hipGetErrorString(e));
     const int64_t total = (int64_t)mh * mw;
     const unsigned blocks = (unsigned)(total / 1024 < 1 ? 1 : total / 1024 > 256 ? 256 : total / 1024);
     hipLaunchKernelGGL(max_kernel, dim3(blocks, (unsigned)n), dim3(256), 0, st, a);
@@ -513,10 +459,5 @@ extern "C" int countr_overlay_render(const countr_overlay_frame* frames, int n, 
   if (format == COUNTR_OVERLAY_NV12) hipLaunchKernelGGL((yuv_kernel<COUNTR_OVERLAY_NV12>), grid, dim3(BX, BY), 0, st, a);
   else if (format == COUNTR_OVERLAY_NV21) hipLaunchKernelGGL((yuv_kernel<COUNTR_OVERLAY_NV21>), grid, dim3(BX, BY), 0, st, a);
   else if (format == COUNTR_OVERLAY_I420) hipLaunchKernelGGL((yuv_kernel<COUNTR_OVERLAY_I420>), grid, dim3(BX, BY), 0, st, a);
-  e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(buf, sizeof(buf), "countr_overlay_render: launch failed: %s", hipGetErrorString(e));
-    return fail(-10, buf);
-  }
-  return 0;
+  return launched("countr_overlay_render");
 }

@@ -16,6 +16,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "../csrc/common.hpp"
+#include "../csrc/host_api.hpp"
 #include "../../include/countr_hip_tiles.h"
 
 namespace {
@@ -134,21 +135,10 @@ __global__ __launch_bounds__(64) void tile_sums_kernel(const float* __restrict__
   if (threadIdx.x == 0) sums[q] = t;
 }
 
-thread_local char g_err[512] = "";
-
-int fail(int rc, const char* msg) {
-  strncpy(g_err, msg, sizeof(g_err) - 1);
-  g_err[sizeof(g_err) - 1] = 0;
-  return rc;
-}
-
 // the number of workgroups (= partials) of a blend of an [hk, wk] map, or < 0
 int blend_blocks(int hk, int wk, const char* who, int* gx, int* gy) {
-  char buf[256];
-  if (hk < T || wk < T || hk > MAX_SIDE || wk > MAX_SIDE || (wk & 3)) {
-    snprintf(buf, sizeof(buf), "%s: a map is 384 .. %d on a side and its width a multiple of 4, got %d x %d", who, MAX_SIDE, hk, wk);
-    return fail(-1, buf);
-  }
+  if (hk < T || wk < T || hk > MAX_SIDE || wk > MAX_SIDE || (wk & 3))
+    return failf(-1, "%s: a map is 384 .. %d on a side and its width a multiple of 4, got %d x %d", who, MAX_SIDE, hk, wk);
   *gx = (wk + BLOCK_COLS - 1) / BLOCK_COLS;
   *gy = (hk + BLOCK_ROWS - 1) / BLOCK_ROWS;
   return *gx * *gy;                                              // <= 24 * 6144
@@ -156,23 +146,14 @@ int blend_blocks(int hk, int wk, const char* who, int* gx, int* gy) {
 
 // a list of starts is a full cover of [0, size): begins at 0, increases strictly, leaves no gap, ends at size - 384
 int check_starts(const int* s, int n, int size, int mult, const char* who, const char* axis) {
-  char buf[256];
-  if (!s || n < 1 || n > MAX_STARTS) {
-    snprintf(buf, sizeof(buf), "%s: 1..%d %s starts, got %d", who, MAX_STARTS, axis, n);
-    return fail(-1, buf);
-  }
+  if (!s || n < 1 || n > MAX_STARTS) return failf(-1, "%s: 1..%d %s starts, got %d", who, MAX_STARTS, axis, n);
   for (int i = 0; i < n; ++i) {
     const int lo = i ? s[i - 1] + 1 : 0, hi = i ? s[i - 1] + T : 0;
-    if (s[i] < lo || s[i] > hi || s[i] + T > size || (s[i] % mult)) {
-      snprintf(buf, sizeof(buf), "%s: %s start %d = %d: the starts begin at 0, increase, leave no gap, are multiples of %d and keep "
-               "their tiles inside %d", who, axis, i, s[i], mult, size);
-      return fail(-1, buf);
-    }
+    if (s[i] < lo || s[i] > hi || s[i] + T > size || (s[i] % mult))
+      return failf(-1, "%s: %s start %d = %d: the starts begin at 0, increase, leave no gap, are multiples of %d and keep "
+                   "their tiles inside %d", who, axis, i, s[i], mult, size);
   }
-  if (s[n - 1] + T != size) {
-    snprintf(buf, sizeof(buf), "%s: the last %s tile ends at %d, the map at %d", who, axis, s[n - 1] + T, size);
-    return fail(-1, buf);
-  }
+  if (s[n - 1] + T != size) return failf(-1, "%s: the last %s tile ends at %d, the map at %d", who, axis, s[n - 1] + T, size);
   return 0;
 }
 
@@ -191,53 +172,34 @@ extern "C" int countr_tiles_workspace(int hk, int wk) {
 
 extern "C" int countr_tile_gather(const float* img, int hk, int wk, const int* rows, const int* cols, int nt, float* wins,
                                   void* stream) {
-  char buf[256];
-  if (!rows || !cols || nt < 1 || nt > MAX_STARTS) {
-    snprintf(buf, sizeof(buf), "countr_tile_gather: 1..%d tiles a call, got %d", MAX_STARTS, nt);
-    return fail(-1, buf);
-  }
+  if (!rows || !cols || nt < 1 || nt > MAX_STARTS) return failf(-1, "countr_tile_gather: 1..%d tiles a call, got %d", MAX_STARTS, nt);
   if (!img || !wins || (((uintptr_t)img) & 15) || (((uintptr_t)wins) & 15))
     return fail(-1, "countr_tile_gather: img and wins are required, 16-byte aligned");
-  if (hk < T || wk < T || hk > MAX_SIDE || wk > MAX_SIDE || (wk & 3)) {
-    snprintf(buf, sizeof(buf), "countr_tile_gather: an image is 384 .. %d on a side and its width a multiple of 4, got %d x %d", MAX_SIDE,
+  if (hk < T || wk < T || hk > MAX_SIDE || wk > MAX_SIDE || (wk & 3))
+    return failf(-1, "countr_tile_gather: an image is 384 .. %d on a side and its width a multiple of 4, got %d x %d", MAX_SIDE,
              hk, wk);
-    return fail(-1, buf);
-  }
   GatherArgs a;
   memset(&a, 0, sizeof(a));
   for (int j = 0; j < nt; ++j) {
-    if (rows[j] < 0 || rows[j] > hk - T || cols[j] < 0 || cols[j] > wk - T) {
-      snprintf(buf, sizeof(buf), "countr_tile_gather: tile %d at (%d, %d) lies outside the %d x %d image", j, rows[j], cols[j], hk, wk);
-      return fail(-1, buf);
-    }
-    if (cols[j] & 3) {
-      snprintf(buf, sizeof(buf), "countr_tile_gather: tile %d: column start %d is not a multiple of 4", j, cols[j]);
-      return fail(-1, buf);
-    }
+    if (rows[j] < 0 || rows[j] > hk - T || cols[j] < 0 || cols[j] > wk - T)
+      return failf(-1, "countr_tile_gather: tile %d at (%d, %d) lies outside the %d x %d image", j, rows[j], cols[j], hk, wk);
+    if (cols[j] & 3) return failf(-1, "countr_tile_gather: tile %d: column start %d is not a multiple of 4", j, cols[j]);
     a.rows[j] = rows[j];
     a.cols[j] = cols[j];
   }
   hipLaunchKernelGGL(tile_gather_kernel, dim3(GROUPS / 256, (unsigned)nt), dim3(256), 0, STREAM(stream), a, img, hk, wk, wins);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(buf, sizeof(buf), "countr_tile_gather: launch failed: %s", hipGetErrorString(e));
-    return fail(-10, buf);
-  }
-  return 0;
+  return launched("countr_tile_gather");
 }
 
 extern "C" int countr_tile_blend(const float* outs, int nrows, int ncols, const int* row_starts, const int* col_starts, int hk, int wk,
                                  const int* rects, int nrects, float* dm, float* sums, void* workspace, void* stream) {
-  char buf[256];
   int gx, gy;
   const int blocks = blend_blocks(hk, wk, "countr_tile_blend", &gx, &gy);
   if (blocks < 0) return blocks;
   if (check_starts(row_starts, nrows, hk, 1, "countr_tile_blend", "row")) return -1;
   if (check_starts(col_starts, ncols, wk, 4, "countr_tile_blend", "column")) return -1;
-  if (nrects < 0 || nrects > MAX_RECTS || (nrects && !rects)) {
-    snprintf(buf, sizeof(buf), "countr_tile_blend: 0..%d rectangles, got %d", MAX_RECTS, nrects);
-    return fail(-1, buf);
-  }
+  if (nrects < 0 || nrects > MAX_RECTS || (nrects && !rects))
+    return failf(-1, "countr_tile_blend: 0..%d rectangles, got %d", MAX_RECTS, nrects);
   if (!outs || !dm || !sums || !workspace || (((uintptr_t)outs) & 15) || (((uintptr_t)dm) & 15) || (((uintptr_t)sums) & 3) ||
       (((uintptr_t)workspace) & 3))
     return fail(-1, "countr_tile_blend: outs and dm (16-byte aligned), sums and a workspace are required");
@@ -247,10 +209,8 @@ extern "C" int countr_tile_blend(const float* outs, int nrows, int ncols, const 
   for (int i = 0; i < ncols; ++i) a.cols[i] = col_starts[i];
   for (int q = 0; q < nrects; ++q) {
     const int y1 = rects[4 * q], x1 = rects[4 * q + 1], y2 = rects[4 * q + 2], x2 = rects[4 * q + 3];
-    if (y2 < y1 || x2 < x1) {
-      snprintf(buf, sizeof(buf), "countr_tile_blend: rectangle %d (%d, %d, %d, %d): corners are (y1, x1) <= (y2, x2)", q, y1, x1, y2, x2);
-      return fail(-1, buf);
-    }
+    if (y2 < y1 || x2 < x1)
+      return failf(-1, "countr_tile_blend: rectangle %d (%d, %d, %d, %d): corners are (y1, x1) <= (y2, x2)", q, y1, x1, y2, x2);
     a.rect[q][0] = y1 < 0 ? 0 : y1;
     a.rect[q][1] = x1 < 0 ? 0 : x1;
     a.rect[q][2] = y2 > hk - 1 ? hk - 1 : y2;
@@ -261,10 +221,5 @@ extern "C" int countr_tile_blend(const float* outs, int nrows, int ncols, const 
   float* part = (float*)workspace;
   hipLaunchKernelGGL(tile_blend_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, STREAM(stream), a, outs, dm, part);
   hipLaunchKernelGGL(tile_sums_kernel, dim3((unsigned)(1 + nrects)), dim3(64), 0, STREAM(stream), part, blocks, sums);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(buf, sizeof(buf), "countr_tile_blend: launch failed: %s", hipGetErrorString(e));
-    return fail(-10, buf);
-  }
-  return 0;
+  return launched("countr_tile_blend");
 }

@@ -25,6 +25,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "../csrc/common.hpp"
+#include "../csrc/host_api.hpp"
 #include "../../include/countr_hip_tracks.h"
 
 namespace {
@@ -356,17 +357,8 @@ __global__ __launch_bounds__(STEP_THREADS) void tracks_step_kernel(const TrArgs 
   }
 }
 
-thread_local char g_err[512] = "";
-
-int fail(int rc, const char* msg) {
-  strncpy(g_err, msg, sizeof(g_err) - 1);
-  g_err[sizeof(g_err) - 1] = 0;
-  return rc;
-}
-
 inline int round8(int v) { return (v + 7) & ~7; }
 inline int scratch_bytes(int N) { return WS_BEST_D + 2 * round8(N); }      // of one tracker: a multiple of 16
-inline bool misaligned(const void* p, uintptr_t a) { return (((uintptr_t)p) & (a - 1)) != 0; }
 
 }  // namespace
 
@@ -377,42 +369,26 @@ extern "C" const char* countr_tracks_last_error(void) { return g_err; }
 extern "C" int countr_tracks_state_bytes(void) { return 4 * (HEAD + COUNTR_TRACKS_FIELDS * MAXT); }
 
 extern "C" int countr_tracks_workspace(int n, int max_points) {
-  char buf[256];
-  if (n < 1 || n > MAXS || max_points < 0 || max_points > MAXP) {
-    snprintf(buf, sizeof(buf), "countr_tracks_workspace: 1..%d trackers of 0..%d points, got %d of %d", MAXS, MAXP, n, max_points);
-    return fail(-1, buf);
-  }
+  if (n < 1 || n > MAXS || max_points < 0 || max_points > MAXP)
+    return failf(-1, "countr_tracks_workspace: 1..%d trackers of 0..%d points, got %d of %d", MAXS, MAXP, n, max_points);
   return n * scratch_bytes(max_points);
 }
 
 extern "C" int countr_tracks_reset(const void* const* states, int n, void* stream) {
-  char buf[256];
-  if (n < 1 || n > MAXS) {
-    snprintf(buf, sizeof(buf), "countr_tracks_reset: 1..%d trackers a call, got %d", MAXS, n);
-    return fail(-1, buf);
-  }
+  if (n < 1 || n > MAXS) return failf(-1, "countr_tracks_reset: 1..%d trackers a call, got %d", MAXS, n);
   if (!states) return fail(-2, "countr_tracks_reset: the states array is required");
   for (int k = 0; k < n; ++k)
-    if (!states[k] || misaligned(states[k], 16)) {
-      snprintf(buf, sizeof(buf), "countr_tracks_reset: tracker %d: the state is required and 16-byte aligned", k);
-      return fail(-2, buf);
-    }
+    if (!states[k] || misaligned(states[k], 16))
+      return failf(-2, "countr_tracks_reset: tracker %d: the state is required and 16-byte aligned", k);
   for (int k = 0; k < n; ++k) {
     const hipError_t e = hipMemsetAsync(const_cast<void*>(states[k]), 0, (size_t)countr_tracks_state_bytes(), STREAM(stream));
-    if (e != hipSuccess) {
-      snprintf(buf, sizeof(buf), "countr_tracks_reset: memset failed: %s", hipGetErrorString(e));
-      return fail(-10, buf);
-    }
+    if (e != hipSuccess) return failf(-10, "countr_tracks_reset: memset failed: %s", hipGetErrorString(e));
   }
   return 0;
 }
 
 extern "C" int countr_tracks_step(const countr_tracks_stream* streams, int n, void* workspace, void* stream) {
-  char buf[256];
-  if (n < 1 || n > MAXS) {
-    snprintf(buf, sizeof(buf), "countr_tracks_step: 1..%d trackers a call, got %d", MAXS, n);
-    return fail(-1, buf);
-  }
+  if (n < 1 || n > MAXS) return failf(-1, "countr_tracks_step: 1..%d trackers a call, got %d", MAXS, n);
   if (!streams) return fail(-2, "countr_tracks_step: the streams array is required");
   if (!workspace || misaligned(workspace, 16)) return fail(-2, "countr_tracks_step: the workspace is required and 16-byte aligned");
   TrArgs a;
@@ -420,48 +396,23 @@ extern "C" int countr_tracks_step(const countr_tracks_stream* streams, int n, vo
   int ws = 0;
   for (int k = 0; k < n; ++k) {
     const countr_tracks_stream& d = streams[k];
-    if (d.N < 0 || d.N > MAXP) {
-      snprintf(buf, sizeof(buf), "countr_tracks_step: tracker %d: 0..%d points, got %d", k, MAXP, d.N);
-      return fail(-3, buf);
-    }
-    if (d.L < 0 || d.L > MAXL) {
-      snprintf(buf, sizeof(buf), "countr_tracks_step: tracker %d: 0..%d lines, got %d", k, MAXL, d.L);
-      return fail(-3, buf);
-    }
-    if (d.max_missed < 0 || d.max_missed > 255) {
-      snprintf(buf, sizeof(buf), "countr_tracks_step: tracker %d: max_missed is 0..255, got %d", k, d.max_missed);
-      return fail(-3, buf);
-    }
-    if (d.min_hits < 1 || d.min_hits > 255) {
-      snprintf(buf, sizeof(buf), "countr_tracks_step: tracker %d: min_hits is 1..255, got %d", k, d.min_hits);
-      return fail(-3, buf);
-    }
+    if (d.N < 0 || d.N > MAXP) return failf(-3, "countr_tracks_step: tracker %d: 0..%d points, got %d", k, MAXP, d.N);
+    if (d.L < 0 || d.L > MAXL) return failf(-3, "countr_tracks_step: tracker %d: 0..%d lines, got %d", k, MAXL, d.L);
+    if (d.max_missed < 0 || d.max_missed > 255)
+      return failf(-3, "countr_tracks_step: tracker %d: max_missed is 0..255, got %d", k, d.max_missed);
+    if (d.min_hits < 1 || d.min_hits > 255) return failf(-3, "countr_tracks_step: tracker %d: min_hits is 1..255, got %d", k, d.min_hits);
     const float md2 = d.max_dist * d.max_dist;   // one fp32 multiply (the host compiler contracts nothing here: no addition follows)
-    if (!(d.max_dist > 0.f) || !__builtin_isfinite(d.max_dist) || !__builtin_isfinite(md2)) {
-      snprintf(buf, sizeof(buf), "countr_tracks_step: tracker %d: max_dist is finite and > 0 and so is its fp32 square", k);
-      return fail(-4, buf);
-    }
-    if (!(d.beta >= 0.f && d.beta <= 1.f)) {
-      snprintf(buf, sizeof(buf), "countr_tracks_step: tracker %d: beta is 0..1", k);
-      return fail(-4, buf);
-    }
-    if (!d.state || !d.summary || (d.N > 0 && (!d.points || !d.ids || !d.events)) || (d.L > 0 && !d.lines)) {
-      snprintf(buf, sizeof(buf), "countr_tracks_step: tracker %d has a null pointer", k);
-      return fail(-2, buf);
-    }
-    if (misaligned(d.state, 16) || misaligned(d.lines, 16)) {
-      snprintf(buf, sizeof(buf), "countr_tracks_step: tracker %d: the state and the lines are 16-byte aligned", k);
-      return fail(-5, buf);
-    }
-    if (misaligned(d.points, 8) || misaligned(d.ids, 4) || misaligned(d.events, 4) || misaligned(d.summary, 4)) {
-      snprintf(buf, sizeof(buf), "countr_tracks_step: tracker %d: the points are 8-byte aligned, ids, events and summary 4-byte aligned", k);
-      return fail(-5, buf);
-    }
+    if (!(d.max_dist > 0.f) || !__builtin_isfinite(d.max_dist) || !__builtin_isfinite(md2))
+      return failf(-4, "countr_tracks_step: tracker %d: max_dist is finite and > 0 and so is its fp32 square", k);
+    if (!(d.beta >= 0.f && d.beta <= 1.f)) return failf(-4, "countr_tracks_step: tracker %d: beta is 0..1", k);
+    if (!d.state || !d.summary || (d.N > 0 && (!d.points || !d.ids || !d.events)) || (d.L > 0 && !d.lines))
+      return failf(-2, "countr_tracks_step: tracker %d has a null pointer", k);
+    if (misaligned(d.state, 16) || misaligned(d.lines, 16))
+      return failf(-5, "countr_tracks_step: tracker %d: the state and the lines are 16-byte aligned", k);
+    if (misaligned(d.points, 8) || misaligned(d.ids, 4) || misaligned(d.events, 4) || misaligned(d.summary, 4))
+      return failf(-5, "countr_tracks_step: tracker %d: the points are 8-byte aligned, ids, events and summary 4-byte aligned", k);
     for (int q = 0; q < k; ++q)
-      if (streams[q].state == d.state) {
-        snprintf(buf, sizeof(buf), "countr_tracks_step: trackers %d and %d share a state", q, k);
-        return fail(-6, buf);
-      }
+      if (streams[q].state == d.state) return failf(-6, "countr_tracks_step: trackers %d and %d share a state", q, k);
     a.state[k] = (int*)d.state; a.points[k] = (const float2*)d.points; a.ids[k] = (int*)d.ids; a.events[k] = (unsigned*)d.events;
     a.summary[k] = (int*)d.summary; a.lines[k] = (const float4*)d.lines;
     a.N[k] = d.N; a.L[k] = d.L; a.md2[k] = md2; a.beta[k] = d.beta; a.max_missed[k] = d.max_missed; a.min_hits[k] = d.min_hits;
@@ -470,10 +421,5 @@ extern "C" int countr_tracks_step(const countr_tracks_stream* streams, int n, vo
   unsigned char* w = (unsigned char*)workspace;
   hipLaunchKernelGGL(tracks_init_kernel, dim3(INIT_BLOCKS, n), dim3(256), 0, STREAM(stream), a, w);
   hipLaunchKernelGGL(tracks_step_kernel, dim3(n), dim3(STEP_THREADS), 0, STREAM(stream), a, (const unsigned char*)w);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(buf, sizeof(buf), "countr_tracks_step: launch failed: %s", hipGetErrorString(e));
-    return fail(-10, buf);
-  }
-  return 0;
+  return launched("countr_tracks_step");
 }

@@ -13,6 +13,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "../csrc/common.hpp"
+#include "../csrc/host_api.hpp"
 #include "../../include/countr_hip_yuv.h"
 
 namespace {
@@ -192,14 +193,6 @@ __global__ __launch_bounds__(BX * BY) void yuv_kernel(const YuvArgs a) {
   }
 }
 
-thread_local char g_err[512] = "";
-
-int fail(int rc, const char* msg) {
-  strncpy(g_err, msg, sizeof(g_err) - 1);
-  g_err[sizeof(g_err) - 1] = 0;
-  return rc;
-}
-
 // cy, yoff, rv, gu, gv, bu of [matrix][range] (the header's table)
 const int COEF[2][2][6] = {{{298, 16, 409, -100, -208, 516}, {256, 0, 359, -88, -183, 454}},
                            {{298, 16, 459, -55, -136, 541}, {256, 0, 403, -48, -120, 475}}};
@@ -218,44 +211,23 @@ extern "C" const char* countr_yuv_last_error(void) { return g_err; }
 
 extern "C" int countr_yuv_to_rgb(const void* const* y, const void* const* c0, const void* const* c1, void* const* rgb, int n, int H, int W,
                                  int pitch_y, int pitch_c, int format, int matrix, int range, int chroma, void* stream) {
-  char buf[256];
-  if (n < 1 || n > MAXF) {
-    snprintf(buf, sizeof(buf), "countr_yuv_to_rgb: 1..%d frames a call, got %d", MAXF, n);
-    return fail(-1, buf);
-  }
-  if (format < COUNTR_YUV_NV12 || format > COUNTR_YUV_P010) {
-    snprintf(buf, sizeof(buf), "countr_yuv_to_rgb: unknown format %d", format);
-    return fail(-1, buf);
-  }
-  if (matrix != COUNTR_YUV_BT601 && matrix != COUNTR_YUV_BT709) {
-    snprintf(buf, sizeof(buf), "countr_yuv_to_rgb: unknown matrix %d", matrix);
-    return fail(-1, buf);
-  }
-  if (range != COUNTR_YUV_LIMITED && range != COUNTR_YUV_FULL) {
-    snprintf(buf, sizeof(buf), "countr_yuv_to_rgb: unknown range %d", range);
-    return fail(-1, buf);
-  }
-  if (chroma != COUNTR_YUV_NEAREST && chroma != COUNTR_YUV_LINEAR) {
-    snprintf(buf, sizeof(buf), "countr_yuv_to_rgb: unknown chroma reconstruction %d", chroma);
-    return fail(-1, buf);
-  }
-  if (H < 1 || H > COUNTR_YUV_MAX_SIDE || W < 1 || W > COUNTR_YUV_MAX_SIDE) {
-    snprintf(buf, sizeof(buf), "countr_yuv_to_rgb: H and W are 1..%d, got %d x %d", COUNTR_YUV_MAX_SIDE, H, W);
-    return fail(-1, buf);
-  }
+  if (n < 1 || n > MAXF) return failf(-1, "countr_yuv_to_rgb: 1..%d frames a call, got %d", MAXF, n);
+  if (format < COUNTR_YUV_NV12 || format > COUNTR_YUV_P010) return failf(-1, "countr_yuv_to_rgb: unknown format %d", format);
+  if (matrix != COUNTR_YUV_BT601 && matrix != COUNTR_YUV_BT709) return failf(-1, "countr_yuv_to_rgb: unknown matrix %d", matrix);
+  if (range != COUNTR_YUV_LIMITED && range != COUNTR_YUV_FULL) return failf(-1, "countr_yuv_to_rgb: unknown range %d", range);
+  if (chroma != COUNTR_YUV_NEAREST && chroma != COUNTR_YUV_LINEAR)
+    return failf(-1, "countr_yuv_to_rgb: unknown chroma reconstruction %d", chroma);
+  if (H < 1 || H > COUNTR_YUV_MAX_SIDE || W < 1 || W > COUNTR_YUV_MAX_SIDE)
+    return failf(-1, "countr_yuv_to_rgb: H and W are 1..%d, got %d x %d", COUNTR_YUV_MAX_SIDE, H, W);
   const bool wide = format == COUNTR_YUV_P010;
   const int Hc = (H + 1) / 2, Wc = (W + 1) / 2;
   const int row_y = W * (wide ? 2 : 1);
   const int row_c = format == COUNTR_YUV_I420 ? Wc : 2 * Wc * (wide ? 2 : 1);
-  if (pitch_y < row_y || (wide && (pitch_y & 1))) {
-    snprintf(buf, sizeof(buf), "countr_yuv_to_rgb: pitch_y %d: a Y row has %d bytes%s", pitch_y, row_y, wide ? " and a P010 pitch is even" : "");
-    return fail(-1, buf);
-  }
-  if (pitch_c < row_c || (wide && (pitch_c & 1))) {
-    snprintf(buf, sizeof(buf), "countr_yuv_to_rgb: pitch_c %d: a chroma row has %d bytes%s", pitch_c, row_c,
-             wide ? " and a P010 pitch is even" : "");
-    return fail(-1, buf);
-  }
+  if (pitch_y < row_y || (wide && (pitch_y & 1)))
+    return failf(-1, "countr_yuv_to_rgb: pitch_y %d: a Y row has %d bytes%s", pitch_y, row_y, wide ? " and a P010 pitch is even" : "");
+  if (pitch_c < row_c || (wide && (pitch_c & 1)))
+    return failf(-1, "countr_yuv_to_rgb: pitch_c %d: a chroma row has %d bytes%s", pitch_c, row_c,
+                 wide ? " and a P010 pitch is even" : "");
   if (!y || !c0 || !rgb) return fail(-1, "countr_yuv_to_rgb: the pointer arrays y, c0 and rgb are required");
   if (format == COUNTR_YUV_I420 && !c1) return fail(-1, "countr_yuv_to_rgb: c1 (the V planes) is required for I420");
   if (format != COUNTR_YUV_I420 && c1) return fail(-1, "countr_yuv_to_rgb: c1 must be NULL unless the format is I420");
@@ -263,15 +235,9 @@ extern "C" int countr_yuv_to_rgb(const void* const* y, const void* const* c0, co
   memset(&a, 0, sizeof(a));
   uintptr_t bits_in = (uintptr_t)pitch_y | (uintptr_t)pitch_c, bits_out = (uintptr_t)W;
   for (int j = 0; j < n; ++j) {
-    if (!y[j] || !c0[j] || !rgb[j] || (c1 && !c1[j])) {
-      snprintf(buf, sizeof(buf), "countr_yuv_to_rgb: frame %d has a null pointer", j);
-      return fail(-1, buf);
-    }
+    if (!y[j] || !c0[j] || !rgb[j] || (c1 && !c1[j])) return failf(-1, "countr_yuv_to_rgb: frame %d has a null pointer", j);
     const uintptr_t in = (uintptr_t)y[j] | (uintptr_t)c0[j] | (c1 ? (uintptr_t)c1[j] : 0);
-    if (wide && (in & 1)) {
-      snprintf(buf, sizeof(buf), "countr_yuv_to_rgb: frame %d: a P010 plane is 2-byte aligned", j);
-      return fail(-1, buf);
-    }
+    if (wide && (in & 1)) return failf(-1, "countr_yuv_to_rgb: frame %d: a P010 plane is 2-byte aligned", j);
     bits_in |= in;
     bits_out |= (uintptr_t)rgb[j];
     a.y[j] = (const uint8_t*)y[j];
@@ -291,10 +257,5 @@ extern "C" int countr_yuv_to_rgb(const void* const* y, const void* const* c0, co
   else if (format == COUNTR_YUV_NV21) launch<COUNTR_YUV_NV21>(linear, grid, STREAM(stream), a);
   else if (format == COUNTR_YUV_I420) launch<COUNTR_YUV_I420>(linear, grid, STREAM(stream), a);
   else launch<COUNTR_YUV_P010>(linear, grid, STREAM(stream), a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(buf, sizeof(buf), "countr_yuv_to_rgb: launch failed: %s", hipGetErrorString(e));
-    return fail(-10, buf);
-  }
-  return 0;
+  return launched("countr_yuv_to_rgb");
 }

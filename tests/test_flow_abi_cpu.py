@@ -50,12 +50,11 @@ def test_every_prototype_is_defined_extern_c_in_the_sources():
               for p in glob.glob(os.path.join(ROOT, "countr_amd", d, "*.hip"))]
     assert paths and not set(os.path.basename(p) for p in paths) & set(others)
     from countr_amd import build
-    # pinned by the older tests: left alone
-    assert list(build.SINGLE) == ["ext", "classes", "tiles"] and list(build.SINGLE_LATER) == ["yuv"] and list(build.SINGLE_OVERLAY) == ["overlay"]
-    assert list(build.SINGLE_TRACKS) == ["tracks"]
-    assert list(build.SINGLE_FLOW) == ["flow"] and build.SINGLE_FLOW["flow"][1]() == sorted(paths)
-    assert build.SINGLE_FLOW["flow"][0] == os.path.join(ROOT, "countr_amd", "libcountr_hip_flow.so")
-    assert os.path.samefile(build.SINGLE_FLOW["flow"][2], _lib.FLOW_HEADER)
+    # the one table of the side libraries, whole and in the order they were added
+    assert list(build.SINGLE) == ["ext", "classes", "tiles", "yuv", "overlay", "tracks", "flow"]
+    assert build.SINGLE["flow"][1]() == sorted(paths)
+    assert build.SINGLE["flow"][0] == os.path.join(ROOT, "countr_amd", "libcountr_hip_flow.so")
+    assert os.path.samefile(build.SINGLE["flow"][2], _lib.FLOW_HEADER)
 
 
 def test_version_limits_binding_and_errors():

@@ -45,7 +45,7 @@ def test_every_prototype_is_defined_extern_c_in_the_sources():
     others = [os.path.basename(p) for d in ("csrc", "csrc_ext", "csrc_classes") for p in glob.glob(os.path.join(ROOT, "countr_amd", d, "*.hip"))]
     assert paths and not set(os.path.basename(p) for p in paths) & set(others)
     from countr_amd import build
-    assert list(build.SINGLE) == ["ext", "classes", "tiles"] and build.SINGLE["tiles"][1]() == sorted(paths)
+    assert list(build.SINGLE)[:3] == ["ext", "classes", "tiles"] and build.SINGLE["tiles"][1]() == sorted(paths)
 
 
 def test_version_limits_binding_and_errors():
