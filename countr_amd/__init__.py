@@ -10,6 +10,9 @@ def __getattr__(name):
     if name in ("flow_host", "FlowCounter", "FlowCounts", "blob_scene"):
         from . import flow
         return getattr(flow, name)
+    if name in ("camera_host", "texture_host", "estimate_host", "compensate_host", "CameraEstimator", "CameraPath", "pan_scene"):
+        from . import cam
+        return getattr(cam, name)
     if name in ("Overlay", "overlay_host"):
         from . import overlay
         return getattr(overlay, name)

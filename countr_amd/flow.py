@@ -17,13 +17,18 @@ passes to its count.
 
 The defaults min_gain = 256 (one grey level per window pixel), band = 8 H / 384 frame pixels and search = 4 are unmeasured: there is
 neither a checkpoint nor an annotated clip to tune them on, and no accuracy figure on real video exists.  What exists is the instrument,
-pinned on synthetic scenes with known answers.  Motion below about half a map pixel per interval is underestimated: use interval > 1."""
+pinned on synthetic scenes with known answers.  Motion below about half a map pixel per interval is underestimated: use interval > 1.
+
+All of this assumes a camera that stands still.  camera="translation" (flow_host, FlowCounter) puts the rule of countr_amd/cam.py
+between motion and flux: the camera's own move is estimated from the field, the field is compensated for it and every map is placed at
+the camera's position, so that lines and flux are in pixels of the first frame.  camera=None is the rule above and nothing else."""
 import collections
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
+from . import cam as cam_
 
 _K = {k[len("COUNTR_FLOW_"):]: v for k, v in _lib.FLOW_CONSTS.items()}
 MAX_FRAMES, MAX_LINES, MAX_SEARCH, MAX_INTERVAL = _K["MAX_FRAMES"], _K["MAX_LINES"], _K["MAX_SEARCH"], _K["MAX_INTERVAL"]
@@ -171,26 +176,40 @@ def frame_scale(count, total):
     return np.float64(count) / (np.float64(total) / 60) if total > 0 else np.float64(1.0)
 
 
-def flow_host(lumas, maps, *, lines, placement=(1.0, 0.0, 1.0, 0.0), search=4, interval=1, min_gain=256, band=8.0, counts=None):
+def flow_host(lumas, maps, *, lines, placement=(1.0, 0.0, 1.0, 0.0), search=4, interval=1, min_gain=256, band=8.0, counts=None,
+              camera=None, min_texture=128, cam_tol=8, min_voters=16, fields=None):
     """The rule over a clip.  lumas: uint8 [h, w] per frame, in time order; maps: fp32 [h, w] per frame, or None for a frame without a
     frame map (the 3 x 3 split); placement: the maps' (sx, tx, sy, ty); counts: the frames' counts, or None for scale 1 -> ([(flux float64
     [L, 2] or None, motion int16 [h / 8, w / 8, 2] or None, total or None), ...], FlowCounts).  The first `interval` frames count nothing
-    (flux and motion None); a frame without a map has flux None, and its luma still is the earlier luma of a later frame."""
+    (flux and motion None); a frame without a map has flux None, and its luma still is the earlier luma of a later frame.
+    camera="translation": the rule of countr_amd/cam.py runs between motion and flux -- every frame's field is compensated for the
+    camera's estimated move and its map is placed at (sx, tx + sx * Gx / 16, sy, ty + sy * Gy / 16), so lines and flux are in pixels of
+    the FIRST frame; the motion returned stays the raw field, and a third result is the CameraPath.  camera=None is the rule above and
+    nothing else.  fields: the frames' motion fields if they are at hand (None entries for the first `interval` frames)."""
     search, interval, min_gain, band = _settings(search, interval, min_gain, band)
+    min_texture, cam_tol, min_voters = cam_.settings(camera, min_texture, cam_tol, min_voters)
     lines = _lines(lines)
     out, acc, counted = [], np.zeros((len(lines), 2)), 0
+    records, path = np.zeros((len(lumas), cam_.RECORD_INTS), np.int32), np.zeros((len(lumas), 2), np.int64)
     for t, (L, M) in enumerate(zip(lumas, maps)):
         if t < interval:
             out.append((None, None, None))
             continue
-        V = motion_host(L, lumas[t - interval], search, min_gain)
+        V = fields[t] if fields is not None else motion_host(L, lumas[t - interval], search, min_gain)
+        moved, placed = V, placement
+        if camera is not None:
+            records[t], flags = cam_.estimate_host(V, L, min_texture, cam_tol, min_voters)
+            path[t] = path[t - interval] + records[t, :2]
+            moved, placed = cam_.compensate_host(V, records[t], flags), cam_.shifted_placement(path[t], placement)
         if M is None:
             out.append((None, V, None))
             continue
-        flux, total = flux_host(M, V, placement, lines, band, interval)
+        flux, total = flux_host(M, moved, placed, lines, band, interval)
         acc += frame_scale(counts[t], total) * flux if counts is not None else flux
         counted += 1
         out.append((flux, V, total))
+    if camera is not None:
+        return out, FlowCounts(acc, len(out), counted), cam_.CameraPath(path, cam_.lost_frames(records), records)
     return out, FlowCounts(acc, len(out), counted)
 
 
@@ -252,9 +271,15 @@ class FlowCounter:
     and the 16 of a launch, as one ring), the motion fields, the flux workspace, the packed result buffer and its pinned mirror: all made
     by the first run, so a steady stream allocates nothing but its (host) results.  Lines and placements travel as kernel arguments: a
     run uploads nothing.  Calls follow each other on the current stream; a call on another stream waits for the previous call's event
-    first.  The defaults of search, min_gain and band (8 H / 384 frame pixels) are unmeasured."""
+    first.  The defaults of search, min_gain and band (8 H / 384 frame pixels) are unmeasured.
+    camera="translation": a chunk runs luma, motion, the camera estimate (countr_amd/cam.py), a download of its records and a wait,
+    the compensation into a second field buffer, and the flux of the compensated fields with every map placed at the camera's position:
+    lines and flux are then in pixels of the first frame.  The placement is a host-side kernel argument, so that is TWO waits per chunk
+    instead of one.  min_texture, cam_tol and min_voters are the estimate's settings, unmeasured on real video.  camera=None is the
+    path above, launch for launch."""
 
-    def __init__(self, device="cuda", *, lines, search=4, interval=1, min_gain=256, band=None):
+    def __init__(self, device="cuda", *, lines, search=4, interval=1, min_gain=256, band=None, camera=None, min_texture=128, cam_tol=8,
+                 min_voters=16):
         import torch
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -263,7 +288,13 @@ class FlowCounter:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.search, self.interval, self.min_gain, self.band = _settings(search, interval, min_gain, band)
         self.lines = _lines(lines)
+        self.camera = camera
+        cam_set = cam_.settings(camera, min_texture, cam_tol, min_voters)
         self.L = _lib.flow_lib()
+        self._cam = None
+        if camera is not None:
+            self._cam = cam_.CameraEstimator(self.device, min_texture=cam_set[0], tol=cam_set[1], min_voters=cam_set[2])
+        self._path, self._records = [], []          # per frame since the counter was made: G int64 (x, y), record int32 [8]
         self.shape = None           # (W, H, h, w): the original frame and its map
         self.placement = None
         self.frames = self.counted = 0
@@ -281,6 +312,13 @@ class FlowCounter:
     def counts(self):
         """What the frames so far add up to."""
         return FlowCounts(self.line_counts.copy(), self.frames, self.counted)
+
+    def camera_path(self):
+        """The CameraPath of the frames so far (camera="translation" only)."""
+        if self._cam is None:
+            raise ValueError("FlowCounter.camera_path: the counter was made with camera=None")
+        return cam_.CameraPath(np.array(self._path, np.int64).reshape(-1, 2), cam_.lost_frames(self._records),
+                               np.array(self._records, np.int32).reshape(-1, cam_.RECORD_INTS))
 
     def luma(self, back=0):
         """The luma plane uint8 [h, w] (a view of the device ring) of the frame `back` frames before the latest, 0 <= back <= interval."""
@@ -306,6 +344,9 @@ class FlowCounter:
             self._out = torch.zeros(self._mv_at + MAX_FRAMES * cells * 4, dtype=torch.uint8, device=self.device)
             self._out_host = torch.zeros(self._out.numel(), dtype=torch.uint8).pin_memory()
             self._ws = torch.empty(ws, dtype=torch.uint8, device=self.device)
+            if self._cam is not None:
+                self._comp = torch.zeros(MAX_FRAMES * cells * 4, dtype=torch.uint8, device=self.device)      # the compensated fields
+                self._rec_host = torch.zeros(MAX_FRAMES, cam_.RECORD_INTS, dtype=torch.int32).pin_memory()
         elif self.shape != (W, H, h, w):
             raise ValueError("FlowCounter serves one frame shape: it holds %r, got %r" % (self.shape, (W, H, h, w)))
 
@@ -325,7 +366,8 @@ class FlowCounter:
         (fp32 or a 16-bit type, [h, w], on the device) or None for a frame without a frame map; sizes: (W, H) of the original frames;
         counts: the frames' counts (scale = count / (total / 60)), or None for scale 1 -> [(flux float32 [L, 2] or None, motion int16
         [h / 8, w / 8, 2] or None, total or None), ...]: the unscaled device sums; scale * flux adds into line_counts in float64.  The
-        motion fields are downloaded only with motion=True.  Per 16 frames: four launches at most, one download, one synchronisation."""
+        motion fields are downloaded only with motion=True.  Per 16 frames: four launches at most, one download, one synchronisation
+        (with a camera: the estimate and the compensation on top, two downloads, two synchronisations)."""
         import torch
         n = len(images)
         if len(maps) != n or len(sizes) != n or (counts is not None and len(counts) != n):
@@ -367,6 +409,24 @@ class FlowCounter:
             if moved:
                 _lib.flow_check(self.L.countr_flow_motion(self._a, self._b, self._c, len(moved), h, w, self.search, self.min_gain, st),
                                 "countr_flow_motion")
+            fields, place = out + self._mv_at, {}
+            if self._cam is not None:
+                recs = np.zeros((0, cam_.RECORD_INTS), np.int32)
+                if moved:
+                    raw = [out + self._mv_at + 4 * cells * k for k in moved]
+                    self._cam.launch(raw, [plane(g0 + k) for k in moved], h, w, st)
+                    self._rec_host[:len(moved)].copy_(self._cam.records[:len(moved)], non_blocking=True)
+                    self._event.record(cur)
+                    self._event.synchronize()        # the wait the camera adds: the placements below are host-side kernel arguments
+                    recs = self._rec_host[:len(moved)].numpy().copy()
+                    fields = self._comp.data_ptr()
+                    self._cam.compensate(raw, [fields + 4 * cells * k for k in moved], h, w, st)
+                first = n - len(moved)               # (the frames that moved are the chunk's tail)
+                for k in range(n):
+                    rec = recs[k - first] if k >= first else np.zeros(cam_.RECORD_INTS, np.int32)
+                    self._path.append(self._path[g0 + k - s] + rec[:2] if k >= first else np.zeros(2, np.int64))
+                    self._records.append(rec)
+                    place[k] = cam_.shifted_placement(self._path[g0 + k], self.placement)
             flowed = [k for k in moved if maps[k] is not None]
             for q, k in enumerate(flowed):
                 m = maps[k]
@@ -374,8 +434,8 @@ class FlowCounter:
                     m = m.float().contiguous()
                     keep.append(m)
                 d = self._maps[q]
-                d.map, d.motion, d.out = m.data_ptr(), out + self._mv_at + 4 * cells * k, out + 4 * OUT_FLOATS * k
-                d.sx, d.tx, d.sy, d.ty = self.placement
+                d.map, d.motion, d.out = m.data_ptr(), fields + 4 * cells * k, out + 4 * OUT_FLOATS * k
+                d.sx, d.tx, d.sy, d.ty = place.get(k, self.placement)
             if flowed:
                 _lib.flow_check(self.L.countr_flow_flux(self._maps, len(flowed), h, w, self._lines_c if nl else None, nl, self.band, s,
                                                         self._ws.data_ptr(), st), "countr_flow_flux")

@@ -578,7 +578,8 @@ def _is_shared(boxes):
 
 @torch.no_grad()
 def count_clip(model, frames, boxes=None, *, max_dist, lines=None, group=8, max_missed=2, min_hits=3, beta=0.5, tracker=None, radius=4,
-               threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all", normalization=True, max_s_cnt=1, max_batch=32, summaries=False):
+               threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all", normalization=True, max_s_cnt=1, max_batch=32, summaries=False,
+               camera=None, search=4, interval=1, min_gain=256, min_texture=128, cam_tol=8, min_voters=16, counter=None):
     """locate_frames over a clip, its points joined over time: ([(count, density map, points, score, ids int32 [P], events uint32 [P]),
     ...] per frame, ClipCounts(started, confirmed, dropped, line_counts int [L, 2] as (forward, backward), live)).  frames: whatever
     count_frames takes, YuvFrames included, in time order.  Consecutive groups of `group` frames go through locate_frames' path -- count,
@@ -592,8 +593,14 @@ def count_clip(model, frames, boxes=None, *, max_dist, lines=None, group=8, max_
     tracker=: a Tracker(streams=1) to continue -- the live-stream case; max_dist, lines, max_missed, min_hits and beta are then the
     tracker's own and lines must be left None.  summaries=True: each frame's tuple ends with its step's summary int32 [40] (live,
     started, confirmed, matched, born, died, dropped, frame, counts[16][2]).  zoom is not taken: the clip is tracked at zoom 1.  The defaults of max_missed, min_hits
-    and beta, like radius and rel_threshold, are unmeasured: no accuracy figure exists."""
-    from . import tracks as tracks_
+    and beta, like radius and rel_threshold, are unmeasured: no accuracy figure exists.
+    camera="translation": the clip is tracked in scene coordinates under a panning camera (countr_amd/cam.py states the rule).  The
+    luma, motion (search, interval, min_gain) and camera estimate (min_texture, cam_tol, min_voters: unmeasured on real video) of each
+    group's prepared images run through a line-less FlowCounter, and the detections go to the Tracker as fl32(p + C_t), one fp64 add per
+    coordinate, rounded once: max_dist and the lines are then in pixels of the FIRST frame.  The returned points stay locate_frames'
+    bytes, and each frame's tuple ends with C_t float64 (x, y).  counter=: a FlowCounter(lines=(), camera=...) to continue with
+    tracker=; camera and its settings are then the counter's own."""
+    from . import flow as flow_, tracks as tracks_
     device = next(model.parameters()).device
     if int(group) != group or group < 1:
         raise ValueError("count_clip: group is >= 1")
@@ -601,6 +608,11 @@ def count_clip(model, frames, boxes=None, *, max_dist, lines=None, group=8, max_
         tracker = tracks_.Tracker(device, max_dist=max_dist, max_missed=max_missed, min_hits=min_hits, beta=beta, lines=lines if lines is not None else ())
     elif tracker.streams != 1 or lines is not None:
         raise ValueError("count_clip: tracker= is a Tracker of one stream, and the lines are its own")
+    if counter is not None and (camera is not None or counter.camera is None or counter.lines.shape[0]):
+        raise ValueError("count_clip: counter= is a line-less FlowCounter with a camera, and the camera is its own")
+    if counter is None and camera is not None:
+        counter = flow_.FlowCounter(device, lines=(), search=search, interval=interval, min_gain=min_gain, camera=camera,
+                                    min_texture=min_texture, cam_tol=cam_tol, min_voters=min_voters)
     frames = list(frames)
     cut = None
     if _is_shared(boxes):
@@ -618,8 +630,15 @@ def count_clip(model, frames, boxes=None, *, max_dist, lines=None, group=8, max_
             items = prepare_items(device, part, boxes[g0:g0 + int(group)] if boxes is not None else None)
         res = locate_items(model, items, sizes, radius=radius, threshold=threshold, rel_threshold=rel_threshold, max_points=max_points,
                            keep=keep, normalization=normalization, max_s_cnt=max_s_cnt, max_batch=max_batch)
-        for r, (ids, events, summary) in zip(res, tracker.run([r[2] for r in res])):
-            out.append(r[:4] + (ids, events) + ((summary,) if summaries else ()))
+        points, where = [r[2] for r in res], [()] * len(res)
+        if counter is not None:
+            t0 = counter.frames
+            counter.run([it[0] for it in items], [None] * len(items), sizes)
+            path = counter.camera_path()
+            where = [(path.position(t0 + k, counter.placement),) for k in range(len(res))]
+            points = [(p.astype(np.float64) + c).astype(np.float32) for p, (c,) in zip(points, where)]
+        for r, c, (ids, events, summary) in zip(res, where, tracker.run(points)):
+            out.append(r[:4] + (ids, events) + ((summary,) if summaries else ()) + c)
             last = summary
     L = tracker.lines.shape[0]
     if last is None:
@@ -630,7 +649,7 @@ def count_clip(model, frames, boxes=None, *, max_dist, lines=None, group=8, max_
 
 @torch.no_grad()
 def count_flow(model, frames, boxes=None, *, lines, search=4, interval=1, min_gain=256, band=None, group=8, counter=None, motion=False,
-               normalization=True, max_s_cnt=1, max_batch=32):
+               normalization=True, max_s_cnt=1, max_batch=32, camera=None, min_texture=128, cam_tol=8, min_voters=16):
     """count_frames over a clip, with the number of objects that crossed each line read from the flux of the density map -- the
     peak-free counterpart of count_clip's line counts: ([(count, density map, flux float32 [L, 2] as (forward, backward) or None), ...]
     per frame, FlowCounts(line_counts float64 [L, 2], frames, counted)); with motion=True each tuple ends with the frame's motion field
@@ -646,15 +665,21 @@ def count_flow(model, frames, boxes=None, *, lines, search=4, interval=1, min_ga
     8 H / 384).  boxes: None, one list per frame, or (k, boxes) as in count_clip.  counter=: a FlowCounter to continue -- the live-stream
     case; lines, search, interval, min_gain and band are then the counter's own and lines must be None.  zoom is not taken.  The defaults
     of search, min_gain and band are unmeasured and no accuracy figure exists; motion under about half a map pixel per interval is
-    underestimated, which is what interval is for."""
+    underestimated, which is what interval is for.
+    camera="translation": the lines are counted in scene coordinates under a panning camera (countr_amd/cam.py states the rule;
+    FlowCounter the order of a chunk): the lines are in pixels of the FIRST frame, each frame's tuple ends with the camera's position
+    C_t float64 (x, y) in frame pixels, and a group costs two synchronisations instead of one.  count and map are untouched.  min_texture,
+    cam_tol and min_voters are unmeasured on real video.  With counter= the camera is the counter's own.  motion=True still returns the
+    raw field."""
     from . import flow as flow_
     device = next(model.parameters()).device
     if int(group) != group or group < 1:
         raise ValueError("count_flow: group is >= 1")
     if counter is None:
-        counter = flow_.FlowCounter(device, lines=lines if lines is not None else (), search=search, interval=interval, min_gain=min_gain, band=band)
-    elif lines is not None:
-        raise ValueError("count_flow: counter= is a FlowCounter, and the lines are its own")
+        counter = flow_.FlowCounter(device, lines=lines if lines is not None else (), search=search, interval=interval, min_gain=min_gain, band=band,
+                                    camera=camera, min_texture=min_texture, cam_tol=cam_tol, min_voters=min_voters)
+    elif lines is not None or camera is not None:
+        raise ValueError("count_flow: counter= is a FlowCounter, and the lines are its own" + (", and so is the camera" if lines is None else ""))
     frames = list(frames)
     cut = None
     if _is_shared(boxes):
@@ -671,14 +696,16 @@ def count_flow(model, frames, boxes=None, *, lines, search=4, interval=1, min_ga
         else:
             items = prepare_items(device, part, boxes[g0:g0 + int(group)] if boxes is not None else None)
         res = count_items_crops(model, items, normalization, max_s_cnt, max_batch)
+        t0 = counter.frames
         got = counter.run([it[0] for it in items], [None if cr is not None else dm for _c, dm, cr in res], sizes,
                           counts=[c for c, _dm, _cr in res], motion=motion)
-        for (c, dm, _cr), (flux, mv, total) in zip(res, got):
+        path = counter.camera_path() if counter.camera is not None else None
+        for k, ((c, dm, _cr), (flux, mv, total)) in enumerate(zip(res, got)):
             if flux is not None:
                 flux = (flow_.frame_scale(c, total) * flux.astype(np.float64)).astype(np.float32)
             if motion and mv is None:
                 mv = np.zeros((dm.shape[0] // flow_.CELL, dm.shape[1] // flow_.CELL, 2), np.int16)
-            out.append((c, dm, flux) + ((mv,) if motion else ()))
+            out.append((c, dm, flux) + ((mv,) if motion else ()) + ((path.position(t0 + k, counter.placement),) if path is not None else ()))
     return out, counter.counts()
 
 

@@ -43,6 +43,10 @@ crossings of the same lines from the flux of the density map instead (countr_amd
 and no tracks.  Each frame's line gains ` - flux: {name: [forward, backward]}` (that frame's share; null for the first S frames) and at
 the end {"clip": {"flux": {name: [forward, backward]}}} is printed and written to flow_<stem>.json.  The defaults of --flow_search and
 --flow_band are unmeasured; slow motion needs --flow_interval.  Without --flow nothing changes.
+`--camera translation` (with --flow or --track) counts in scene coordinates under a panning camera (countr_amd/cam.py,
+include/countr_hip_cam.h): the lines, and --track_dist, are in pixels of the FIRST frame.  Each frame's line gains ` - cam: [x, y]`, the
+camera's position in frame pixels, and the clip JSON gains "camera": {"end": [x, y], "lost": n} (n frames without a valid estimate).
+Rotation and zoom are not modelled, and the estimate's settings are unmeasured on real video.  Without --camera nothing changes.
 demo.py is the few-shot counterpart (exemplar boxes)."""
 import json
 import time
@@ -315,6 +319,19 @@ def load_lines(path):
     return list(named), [(float(a[0]), float(a[1]), float(b[0]), float(b[1])) for a, b in named.values()]
 
 
+def cam_text(where):
+    """` - cam: [x, y]` of a frame counted with --camera, nothing without."""
+    return " - cam: %s" % json.dumps([float(v) for v in where[0]]) if where else ""
+
+
+def add_camera(doc, counter):
+    """"camera": {"end": [x, y], "lost": n} of a clip counted with --camera."""
+    if counter is not None and counter.camera is not None:
+        path = counter.camera_path()
+        end = path.position(-1, counter.placement) if len(path.path) else (0.0, 0.0)
+        doc["camera"] = {"end": [float(v) for v in end], "lost": path.lost}
+
+
 def run_track(args, model, device, clip):
     """--yuv --track: the clip's frames, --group_images at a time, through frames.count_clip with one tracker kept over the groups."""
     from countr_amd.tracks import Tracker
@@ -325,25 +342,30 @@ def run_track(args, model, device, clip):
     names, lines = load_lines(args.lines_json)
     tracker = Tracker(device, max_dist=args.track_dist, max_missed=args.track_missed, min_hits=args.track_hits, lines=lines)
     peak = dict(radius=args.points_radius, rel_threshold=args.points_rel_threshold, keep=args.points_keep)
-    clip_counts = None
+    clip_counts, counter = None, None
+    if args.camera:
+        from countr_amd.flow import FlowCounter
+        counter = FlowCounter(device, lines=(), search=args.flow_search, interval=args.flow_interval, camera=args.camera)
     for g0 in range(0, len(clip), group):
         raw = clip[g0:g0 + group]
         t0 = time.perf_counter()
         got, clip_counts = frames.count_clip(model, raw, max_dist=args.track_dist, group=group, tracker=tracker, normalization=False,
-                                             summaries=True, **peak)
+                                             summaries=True, counter=counter, **peak)
         dt = (time.perf_counter() - t0) / len(raw)
         # the number of peaks found, for points_<stem>.json: the peak finder once more, no forward
         totals = [t for _p, _s, t in frames.locate_maps([(r[0], r[1]) for r in got], [(w, h)] * len(raw), **peak)]
-        for k, (f, (pred_cnt, dm, pts, score, ids, events, summary), total) in enumerate(zip(raw, got, totals)):
+        for k, (f, (pred_cnt, dm, pts, score, ids, events, summary, *where), total) in enumerate(zip(raw, got, totals)):
             name = "%s_%d" % (stem, g0 + k)
             write_points(args.output_path / ("points_%s.json" % name), pred_cnt, total, pts, score, ids)
             if not args.no_viz:
                 sample = prep.prepare([yuv.yuv_host(f)])[0][0]
                 save_visualisation(sample, dm.float(), pred_cnt, args.output_path / ("viz_%s.jpg" % name), w, h, points=pts, lines=lines)
             crossed = {n: [int(((events >> j) & 1).sum()), int(((events >> (16 + j)) & 1).sum())] for j, n in enumerate(names)}
-            print("%s#%d: Count: %s - Time: %s - tracks: %d - crossed: %s" % (stem, g0 + k, pred_cnt, dt, int(summary[0]), json.dumps(crossed)))
+            print("%s#%d: Count: %s - Time: %s - tracks: %d - crossed: %s%s" % (stem, g0 + k, pred_cnt, dt, int(summary[0]), json.dumps(crossed),
+                                                                               cam_text(where)))
     doc = {"clip": {"started": clip_counts.started, "confirmed": clip_counts.confirmed,
                     "lines": {n: [int(v) for v in clip_counts.line_counts[j]] for j, n in enumerate(names)}}}
+    add_camera(doc, counter)
     print(json.dumps(doc))
     with open(args.output_path / ("tracks_%s.json" % stem), "w") as f:
         json.dump(doc, f)
@@ -357,21 +379,22 @@ def run_flow(args, model, device, clip):
     prep = frames.frame_prep(device)
     group = max(args.group_images, 1)
     names, lines = load_lines(args.lines_json)
-    counter = FlowCounter(device, lines=lines, search=args.flow_search, interval=args.flow_interval, band=args.flow_band)
+    counter = FlowCounter(device, lines=lines, search=args.flow_search, interval=args.flow_interval, band=args.flow_band, camera=args.camera)
     for g0 in range(0, len(clip), group):
         raw = clip[g0:g0 + group]
         t0 = time.perf_counter()
         got, _counts = frames.count_flow(model, raw, lines=None, group=group, counter=counter, normalization=False)
         dt = (time.perf_counter() - t0) / len(raw)
-        for k, (f, (pred_cnt, dm, flux)) in enumerate(zip(raw, got)):
+        for k, (f, (pred_cnt, dm, flux, *where)) in enumerate(zip(raw, got)):
             name = "%s_%d" % (stem, g0 + k)
             if not args.no_viz:
                 sample = prep.prepare([yuv.yuv_host(f)])[0][0]
                 save_visualisation(sample, dm.float(), pred_cnt, args.output_path / ("viz_%s.jpg" % name), w, h, lines=lines)
             share = None if flux is None else {n: [float(flux[j, 0]), float(flux[j, 1])] for j, n in enumerate(names)}
-            print("%s#%d: Count: %s - Time: %s - flux: %s" % (stem, g0 + k, pred_cnt, dt, json.dumps(share)))
+            print("%s#%d: Count: %s - Time: %s - flux: %s%s" % (stem, g0 + k, pred_cnt, dt, json.dumps(share), cam_text(where)))
     total = counter.counts().line_counts
     doc = {"clip": {"flux": {n: [float(total[j, 0]), float(total[j, 1])] for j, n in enumerate(names)}}}
+    add_camera(doc, counter)
     print(json.dumps(doc))
     with open(args.output_path / ("flow_%s.json" % stem), "w") as f:
         json.dump(doc, f)
@@ -405,7 +428,11 @@ def main():
     p.add_argument("--flow_search", type=int, default=4, help="with --flow: the motion search radius in map pixels (the default is unmeasured)")
     p.add_argument("--flow_interval", type=int, default=1, help="with --flow: match against the frame this many frames back (slow motion needs > 1)")
     p.add_argument("--flow_band", type=float, default=None, help="with --flow: the counting band in pixels of the frame (default 8 H / 384, unmeasured)")
+    p.add_argument("--camera", default=None, choices=["translation"],
+                   help="with --flow or --track: count in scene coordinates under a panning camera (the estimate's settings are unmeasured)")
     args = p.parse_args()
+    if args.camera is not None and not (args.flow or args.track):
+        p.error("--camera is for --flow or --track")
     if args.out_yuv is not None and not args.yuv:
         p.error("--out_yuv is for --yuv")
     zoom = parse_zoom(args)
