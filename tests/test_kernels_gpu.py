@@ -8,6 +8,7 @@ import torch
 
 import attnref as AR
 import halfprec as HP
+import kedges as KE
 import stagecheck as SC
 from countr_amd import _lib
 from oracle import countr_ref as R
@@ -40,19 +41,32 @@ def P(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-@pytest.mark.parametrize("D", [768, 512, 1024])
+@pytest.mark.parametrize("D", [768, 512, 1024] + KE.LN_D)   # KE.LN_D: a part-filled last 256-column group, tiny D, the 1024 < D <= 2048 instance
 @pytest.mark.parametrize("tdt,code,tol", DT)
 def test_layernorm_fwd_bwd(hip, D, tdt, code, tol):
+    _layernorm_fwd_bwd(hip, 1157, D, tdt, code, tol)
+
+
+@pytest.mark.parametrize("D", KE.LN_ROWS_D)
+@pytest.mark.parametrize("rows", KE.LN_ROWS)
+@pytest.mark.parametrize("tdt,code,tol", DT)
+def test_layernorm_fwd_bwd_row_counts(hip, rows, D, tdt, code, tol):
+    """Fewer rows than one grid pass of the backward (256 blocks x 8 waves, two rows per trip): only the first row of a wave's trip exists,
+    most waves have none and contribute zeros to dgamma / dbeta; 2049: one wave has a second row.  D = 1280: the > 64 KiB LDS instance."""
+    _layernorm_fwd_bwd(hip, rows, D, tdt, code, tol)
+
+
+def _layernorm_fwd_bwd(hip, rows, D, tdt, code, tol):
+    """Every output sits between guard bands (tests/kedges.py): a store outside it fails an assertion instead of faulting."""
     hip = HP.library(tdt, hip)
-    rows = 1157
     x = rnd((rows, D), 1, 2.0) + 0.3
     g = 1 + 0.1 * rnd((D,), 2)
     b = 0.1 * rnd((D,), 3)
     dy = rnd((rows, D), 4).to(tdt)
     xd, gd, bd = x.cuda(), g.cuda(), b.cuda()
-    y = torch.empty((rows, D), device="cuda", dtype=tdt)
-    mean = torch.empty(rows, device="cuda")
-    rstd = torch.empty(rows, device="cuda")
+    yG = KE.Guarded((rows, D), tdt, "cuda")
+    meanG, rstdG = KE.Guarded(rows, device="cuda"), KE.Guarded(rows, device="cuda")
+    y, mean, rstd = yG.t, meanG.t, rstdG.t
     _lib.check(hip.countr_layernorm_fwd(P(xd), P(gd), P(bd), P(y), P(mean), P(rstd), rows, D, 1e-6, code, st()))
     xr = x.double().requires_grad_(True)
     gr = g.double().requires_grad_(True)
@@ -63,11 +77,12 @@ def test_layernorm_fwd_bwd(hip, D, tdt, code, tol):
         HP.assert_elementwise(y, yr, HP.BY_DTYPE[tdt], F32_TOL, "layernorm y")
     h16 = tdt if code else torch.bfloat16            # the 16-bit type of the library this case runs on
     nb = hip.countr_layernorm_bwd_nblocks()
-    ws = torch.empty((nb, 2, D), device="cuda")
-    dx = torch.full((rows, D), 0.5, device="cuda")
-    dgb = torch.zeros((2, D), device="cuda")
+    wsG = KE.Guarded((nb, 2, D), device="cuda")
+    dxG = KE.Guarded((rows, D), device="cuda", body=torch.full((rows, D), 0.5))
+    dgbG = KE.Guarded((2, D), device="cuda", body=torch.zeros((2, D)))
+    dxbG = KE.Guarded((rows, D), h16, "cuda")
+    ws, dx, dgb, dxb = wsG.t, dxG.t, dgbG.t, dxbG.t
     dyd = dy.cuda()
-    dxb = torch.empty((rows, D), device="cuda", dtype=h16)
     _lib.check(hip.countr_layernorm_bwd(P(dyd), P(xd), P(gd), P(mean), P(rstd), P(dx), P(dgb[0]), P(dgb[1]), P(ws), rows, D,
                                         code, 1, 0, P(dxb), st()))   # adjacent dgamma/dbeta: single finisher launch
     yr.backward(dy.double())
@@ -76,11 +91,13 @@ def test_layernorm_fwd_bwd(hip, D, tdt, code, tol):
     assert relerr(dgb[1], br.grad) < 1e-4
     assert torch.equal(dxb, dx.to(h16))             # the optional 16-bit copy is the RNE rounding of the updated dx
     # separate (non-adjacent) outputs, accumulate into existing values, no bf16 copy
-    dg2, db2 = torch.ones(D, device="cuda"), torch.ones(D, device="cuda")
+    dg2G, db2G = KE.Guarded(D, device="cuda", body=torch.ones(D)), KE.Guarded(D, device="cuda", body=torch.ones(D))
+    dg2, db2 = dg2G.t, db2G.t
     _lib.check(hip.countr_layernorm_bwd(P(dyd), P(xd), P(gd), P(mean), P(rstd), P(dx), P(dg2), P(db2), P(ws), rows, D,
                                         code, 0, 1, None, st()))
     assert relerr(dg2 - 1, gr.grad) < 1e-4 and relerr(db2 - 1, br.grad) < 1e-4
     assert relerr(dx, xr.grad) < 1e-4
+    assert KE.all_intact(yG, meanG, rstdG, wsG, dxG, dgbG, dxbG, dg2G, db2G)
 
 
 @pytest.mark.parametrize("HW", [24 * 24, 96 * 96, 35 * 35, 100])   # incl. pixel counts that do not divide into the splits
@@ -357,7 +374,7 @@ def test_softmax_fwd_bwd(hip, tdt, code, tol):
     assert relerr(ds, ref) < tol
 
 
-@pytest.mark.parametrize("S", [1, 3, 8, 9, 14, 37])
+@pytest.mark.parametrize("S", [1, 3, 8, 9, 14, 37] + KE.XATTN_S)   # KE.XATTN_S: the KS = 2 backward, masked key slots of the KS = 8 one
 @pytest.mark.parametrize("tdt,code,tol", DT)
 def test_cross_attention_fwd_bwd(hip, S, tdt, code, tol):
     """S <= 8: keys in registers; more (models_crossvit.py:111-128 has no limit, FSC_test_cross(few-shot).py --box_bound -1 passes every
@@ -365,7 +382,7 @@ def test_cross_attention_fwd_bwd(hip, S, tdt, code, tol):
     _cross_attention_fwd_bwd(hip, 576, S, tdt, code, tol)
 
 
-@pytest.mark.parametrize("N,S", [(1, 1), (1, 9), (65, 1), (65, 9)])
+@pytest.mark.parametrize("N,S", [(1, 1), (1, 9), (65, 1), (65, 9)] + KE.XATTN_SHORT)
 @pytest.mark.parametrize("tdt,code,tol", DT)
 def test_cross_attention_fwd_bwd_short_sequences(hip, N, S, tdt, code, tol):
     """One query row (three waves of the forward's only block idle, one partial block of the backward) and 65 (a last block of one
@@ -381,7 +398,8 @@ def _cross_attention_fwd_bwd(hip, N, S, tdt, code, tol):
     v = rnd((B, S, D), 17).to(tdt)
     do = rnd((B, N, D), 18).to(tdt)
     qd, kd, vd, dod = q.cuda(), k.cuda(), v.cuda(), do.cuda()
-    o = torch.empty_like(qd)
+    oG = KE.Guarded((B, N, D), tdt, "cuda")         # every output between guard bands (tests/kedges.py)
+    o = oG.t
     scale = 32 ** -0.5
     _lib.check(hip.countr_xattn_fwd(P(qd), P(kd), P(vd), P(o), B, N, S, D, Hh, D, scale, code, st()))
     qr = q.double().requires_grad_(True); kr = k.double().requires_grad_(True); vr = v.double().requires_grad_(True)
@@ -391,13 +409,15 @@ def _cross_attention_fwd_bwd(hip, N, S, tdt, code, tol):
     a = torch.softmax(qh @ kh.transpose(-1, -2) * scale, -1)
     oref = (a @ vh).transpose(1, 2).reshape(B, N, D)
     assert relerr(o, oref) < tol
-    dq = torch.empty_like(qd)
-    dk = torch.empty((B, S, D), device="cuda"); dv = torch.empty((B, S, D), device="cuda")
-    ws = torch.empty(hip.countr_xattn_bwd_workspace_floats(B, N, S, D), device="cuda")
+    dqG = KE.Guarded((B, N, D), tdt, "cuda")
+    dkG, dvG = KE.Guarded((B, S, D), device="cuda"), KE.Guarded((B, S, D), device="cuda")
+    wsG = KE.Guarded(hip.countr_xattn_bwd_workspace_floats(B, N, S, D), device="cuda")
     h16 = tdt if code else torch.bfloat16
-    dkb = torch.empty((B, S, D), device="cuda", dtype=h16); dvb = torch.empty_like(dkb)
+    dkbG, dvbG = KE.Guarded((B, S, D), h16, "cuda"), KE.Guarded((B, S, D), h16, "cuda")
+    dq, dk, dv, ws, dkb, dvb = dqG.t, dkG.t, dvG.t, wsG.t, dkbG.t, dvbG.t
     _lib.check(hip.countr_xattn_bwd(P(qd), P(kd), P(vd), P(dod), P(dq), P(dk), P(dv), P(ws), B, N, S, D, Hh, D, scale, code, P(dkb), P(dvb), st()))
     torch.cuda.synchronize()
+    assert KE.all_intact(oG, dqG, dkG, dvG, wsG, dkbG, dvbG)
     assert torch.equal(dkb, dk.to(h16)) and torch.equal(dvb, dv.to(h16))     # the optional 16-bit copies
     oref.backward(do.double())
     assert relerr(dq, qr.grad) < tol
