@@ -6,7 +6,7 @@ import ctypes as C
 import os
 import re
 
-from .build import LATER_TAGS, TAGS
+from .build import TAGS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COUNTR_LIB", os.path.join(_HERE, "libcountr_hip.so"))
@@ -169,13 +169,12 @@ class Library:
 
 
 # build.TAGS, in the order they were added: regional counts, the fold of class maps into a label map, frames counted on a 2-D grid of
-# tiles, 4:2:0 decoder surfaces to packed RGB, annotated frames, points joined into tracks, line counts from density flux
+# tiles, 4:2:0 decoder surfaces to packed RGB, annotated frames, points joined into tracks, line counts from density flux, the camera's
+# motion from the flow field
 LIBRARIES = {tag: Library(tag) for tag in TAGS}
-# build.LATER_TAGS: a second list by the same rule, because the tests of the seven above pin LIBRARIES whole: the camera's motion
-LATER_LIBRARIES = {tag: Library(tag) for tag in LATER_TAGS}
 # what the wrappers read: EXT_LIB_PATH, EXT_HEADER, EXT_CONSTS, EXT_STRUCTS, EXT_PROTOS, ext_lib(), ext_check(rc, what), ext_exported_symbols()
 # and the same for every other tag
-for _tag, _l in list(LIBRARIES.items()) + list(LATER_LIBRARIES.items()):
+for _tag, _l in LIBRARIES.items():
     globals().update({_tag.upper() + "_LIB_PATH": _l.path, _tag.upper() + "_HEADER": _l.header, _tag.upper() + "_CONSTS": _l.consts,
                       _tag.upper() + "_STRUCTS": _l.structs, _tag.upper() + "_PROTOS": _l.protos, _tag + "_lib": _l.load,
                       _tag + "_check": _l.check, _tag + "_exported_symbols": _l.exported_symbols})

@@ -22,7 +22,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _owned
 
 _K = {k[len("COUNTR_CAM_"):]: v for k, v in _lib.CAM_CONSTS.items()}
 MAX_FRAMES, CELL, MAX_SIDE, RANGE, BINS, RECORD_INTS = (_K[k] for k in ("MAX_FRAMES", "CELL", "MAX_SIDE", "RANGE", "BINS", "RECORD_INTS"))
@@ -216,10 +216,7 @@ class CameraEstimator:
     nothing; run() is the whole rule on tensors, in chunks of 16, with one wait per chunk.  The defaults are unmeasured on real video."""
 
     def __init__(self, device="cuda", *, min_texture=128, tol=8, min_voters=16):
-        import torch
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.CountrError("CameraEstimator needs a GPU device: the HIP path has no CPU fallback")
+        self.device = _owned.resolve(device, "CameraEstimator")
         self.min_texture, self.tol, self.min_voters = settings(None, min_texture, tol, min_voters)
         self.L = _lib.cam_lib()
         self.shape = None
@@ -264,7 +261,7 @@ class CameraEstimator:
             raise ValueError("CameraEstimator.run: one luma per field")
         recs, flags, comps = [], [], []
         with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            st = _owned.stream_handle(self.device)
             for c0 in range(0, len(fields), MAX_FRAMES):
                 fs, ls = fields[c0:c0 + MAX_FRAMES], lumas[c0:c0 + MAX_FRAMES]
                 for f, l in zip(fs, ls):

@@ -11,7 +11,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib, inference
+from . import _lib, _owned, inference
 from .data import carpk as D
 from .frames import FramePrep, _Slot, _is_u8, _stream
 
@@ -125,18 +125,9 @@ class CarpkPrep(FramePrep):
         return img, ex.unsqueeze(0), self.train_target(boxes)
 
 
-_PREPS = {}
-
-
 def carpk_prep(device):
     """The CarpkPrep of a device, made on first use (count_carpk keeps its buffers here between calls)."""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    p = _PREPS.get(device)
-    if p is None:
-        p = _PREPS[device] = CarpkPrep(device)
-    return p
+    return _owned.instance(CarpkPrep, device)
 
 
 def _stacked(dms):

@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _owned
 
 MAX_SETS, MAX_CLASSES = _lib.CLASSES_CONSTS["COUNTR_CLASSES_MAX_SETS"], _lib.CLASSES_CONSTS["COUNTR_CLASSES_MAX"]
 NONE = 255                  # the label of a pixel whose largest v_c is <= floor
@@ -43,32 +43,18 @@ class ClassFolder:
     pinned); they grow monotonically, so a steady stream of calls allocates nothing but its results (the label maps and host arrays)."""
 
     def __init__(self, device="cuda"):
-        import torch
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.CountrError("ClassFolder needs a GPU device: the HIP path has no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _owned.resolve(device, "ClassFolder")
         self.L = _lib.classes_lib()
         self._ws = None             # uint8, one chunk's scratch (the chunks of a call follow each other on one stream)
         self._sets = self._sets_host = None         # uint8: the countr_class_set structs of every chunk of a call
         self._out = self._out_host = None           # int32: per set won [16] (float bits) | total [16] (float bits) | area [16]
-        self._event = None
-        self._last = None           # the stream of the previous call: another stream waits for its event before it reuses the buffers
+        self._guard = _owned.Guard(self.device)     # a call on another stream than the previous one waits before it reuses the buffers
 
     def _reserve(self, ws_bytes, nsets):
         import torch
-        if self._ws is None or self._ws.numel() < ws_bytes:
-            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-        size = C.sizeof(_lib.ClassSet)
-        if self._sets is None or self._sets.numel() < nsets * size:
-            self._sets = torch.empty(nsets * size, dtype=torch.uint8, device=self.device)
-            self._sets_host = torch.empty(nsets * size, dtype=torch.uint8).pin_memory()
-        if self._out is None or self._out.numel() < nsets * 3 * MAX_CLASSES:
-            self._out = torch.empty(nsets * 3 * MAX_CLASSES, dtype=torch.int32, device=self.device)
-            self._out_host = torch.empty(nsets * 3 * MAX_CLASSES, dtype=torch.int32).pin_memory()
-        if self._event is None:
-            self._event = torch.cuda.Event()
+        _owned.grow(self, "_ws", ws_bytes, torch.uint8)
+        _owned.grow(self, "_sets", nsets * C.sizeof(_lib.ClassSet), torch.uint8, pinned=True)
+        _owned.grow(self, "_out", nsets * 3 * MAX_CLASSES, torch.int32, pinned=True)
 
     def fold(self, sets, floor=0.0):
         """sets: [(maps, scale), ...], a set = one frame: maps = nc contiguous fp32 [h, w] device tensors of one shape, scale = nc numbers
@@ -114,9 +100,7 @@ class ClassFolder:
                 _lib.classes_check(min(b, 0), "countr_classes_workspace")
                 ws_bytes = max(ws_bytes, b)
             self._reserve(ws_bytes, n)
-            cur = torch.cuda.current_stream(self.device)
-            if self._last is not None and self._last != cur:
-                cur.wait_event(self._event)
+            cur = self._guard.enter()
             self._sets[:n * size].copy_(self._sets_host[:n * size], non_blocking=True)        # the one upload
             st = C.c_void_p(cur.cuda_stream)
             out, per = self._out.data_ptr(), 4 * MAX_CLASSES
@@ -126,9 +110,8 @@ class ClassFolder:
                     out + (2 * n + k) * per, self._ws.data_ptr(), st), who)
             ints = 3 * n * MAX_CLASSES
             self._out_host[:ints].copy_(self._out[:ints], non_blocking=True)                  # the one download
-            self._event.record(cur)
-            self._last = cur
-        self._event.synchronize()                    # the one wait of the call
+            self._guard.leave(cur)
+        self._guard.event.synchronize()              # the one wait of the call
         got = self._out_host[:ints].numpy().reshape(3, n, MAX_CLASSES)
         res = []
         for s, (maps, _scale) in enumerate(sets):
@@ -137,16 +120,6 @@ class ClassFolder:
         return res
 
 
-_FOLDERS = {}
-
-
 def class_folder(device):
     """The ClassFolder of a device, made on first use (count_classes keeps its buffers here between calls)."""
-    import torch
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    f = _FOLDERS.get(device)
-    if f is None:
-        f = _FOLDERS[device] = ClassFolder(device)
-    return f
+    return _owned.instance(ClassFolder, device)

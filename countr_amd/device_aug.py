@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _owned
 from .data import fsc147
 from .frames import FramePrep, MAX_BATCHED
 
@@ -94,11 +94,7 @@ class DeviceAug:
     matches next_imgs by identity."""
 
     def __init__(self, device="cuda", batch=8, noise_seed=0):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.CountrError("DeviceAug needs a GPU device: the HIP path has no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _owned.resolve(device, "DeviceAug")
         self.L = _lib.lib()
         self.batch_hint = int(batch)
         self.noise_seed = int(noise_seed) & 0xFFFFFFFFFFFFFFFF
@@ -114,13 +110,6 @@ class DeviceAug:
         ts = [self._clean, self._ping, self._pong, self._tmp, self._partials] + [t for s in self._stages for t in (s.host, s.dev)]
         ts += [t for pair in self.prep._tables.values() for t in pair]
         return sum(t.numel() * t.element_size() for t in ts if t is not None)
-
-    def _grow(self, name, n, dtype):
-        t = getattr(self, name)
-        if t is None or t.numel() < n:
-            t = torch.empty(n, dtype=dtype, device=self.device)
-            setattr(self, name, t)
-        return t
 
     @staticmethod
     def _frame(fr):
@@ -213,15 +202,15 @@ class DeviceAug:
             # (only the B own frames can go through the chain: ping / pong end where the foreign frames begin)
             sizes = [_pad4(3 * nh * nw) for nh, nw in shapes]
             w_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-            clean = self._grow("_clean", int(w_off[-1]), torch.float32)
-            ping = self._grow("_ping", int(w_off[B]), torch.float32)
-            pong = self._grow("_pong", int(w_off[B]), torch.float32)
+            clean = _owned.grow(self, "_clean", int(w_off[-1]), torch.float32)
+            ping = _owned.grow(self, "_ping", int(w_off[B]), torch.float32)
+            pong = _owned.grow(self, "_pong", int(w_off[B]), torch.float32)
             # ---- resize + ToTensor: frames of one (H, W) share a launch pair
             by_shape = {}
             for s, fr in enumerate(frames):
                 by_shape.setdefault((int(fr.shape[0]), int(fr.shape[1])) + tuple(shapes[s]), []).append(s)
             need = max(min(len(ix), MAX_BATCHED) * H * nw * 3 for (H, W, nh, nw), ix in by_shape.items())
-            tmp = self._grow("_tmp", need, torch.uint8)
+            tmp = _owned.grow(self, "_tmp", need, torch.uint8)
             for (H, W, nh, nw), idxs in by_shape.items():
                 hbt, hwt = self.prep.tables(W, nw)
                 vbt, vwt = self.prep.tables(H, nh)

@@ -27,7 +27,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _owned
 from . import cam as cam_
 
 _K = {k[len("COUNTR_FLOW_"):]: v for k, v in _lib.FLOW_CONSTS.items()}
@@ -280,12 +280,7 @@ class FlowCounter:
 
     def __init__(self, device="cuda", *, lines, search=4, interval=1, min_gain=256, band=None, camera=None, min_texture=128, cam_tol=8,
                  min_voters=16):
-        import torch
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.CountrError("FlowCounter needs a GPU device: the HIP path has no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _owned.resolve(device, "FlowCounter")
         self.search, self.interval, self.min_gain, self.band = _settings(search, interval, min_gain, band)
         self.lines = _lines(lines)
         self.camera = camera
@@ -303,10 +298,9 @@ class FlowCounter:
         self._maps = (_lib.FlowMap * MAX_FRAMES)()
         self._a, self._b, self._c = ((C.c_void_p * MAX_FRAMES)() for _ in range(3))
         self._lines_c = (C.c_double * max(4 * self.lines.shape[0], 1))(*self.lines.reshape(-1))
+        import torch
         with torch.cuda.device(self.device):
-            self._event = torch.cuda.Event()
-            self._last = torch.cuda.current_stream(self.device)
-            self._event.record(self._last)
+            self._guard = _owned.Guard(self.device, recorded=True)      # the first call on another stream waits for the constructing one
         self._planes = self._out = self._out_host = self._ws = None
 
     def counts(self):
@@ -350,17 +344,6 @@ class FlowCounter:
         elif self.shape != (W, H, h, w):
             raise ValueError("FlowCounter serves one frame shape: it holds %r, got %r" % (self.shape, (W, H, h, w)))
 
-    def _enter(self):
-        import torch
-        cur = torch.cuda.current_stream(self.device)
-        if self._last != cur:
-            cur.wait_event(self._event)
-        return cur
-
-    def _leave(self, cur):
-        self._event.record(cur)
-        self._last = cur
-
     def run(self, images, maps, sizes, counts=None, motion=False):
         """images: the prepared images fp32 [1, 3, h, w] on the device (FramePrep.prepare), in time order; maps: each frame's density map
         (fp32 or a 16-bit type, [h, w], on the device) or None for a frame without a frame map; sizes: (W, H) of the original frames;
@@ -393,7 +376,7 @@ class FlowCounter:
         cells = (h // CELL) * (w // CELL)
         keep = []                                    # (converted maps stay alive until the call is waited for)
         with torch.cuda.device(self.device):
-            cur = self._enter()
+            cur = self._guard.enter()
             st = C.c_void_p(cur.cuda_stream)
             g0 = self.frames                         # the index of the chunk's first frame since the counter was made
             plane = lambda g: self._planes[g % self._ring].data_ptr()
@@ -416,8 +399,8 @@ class FlowCounter:
                     raw = [out + self._mv_at + 4 * cells * k for k in moved]
                     self._cam.launch(raw, [plane(g0 + k) for k in moved], h, w, st)
                     self._rec_host[:len(moved)].copy_(self._cam.records[:len(moved)], non_blocking=True)
-                    self._event.record(cur)
-                    self._event.synchronize()        # the wait the camera adds: the placements below are host-side kernel arguments
+                    self._guard.event.record(cur)
+                    self._guard.event.synchronize()  # the wait the camera adds: the placements below are host-side kernel arguments
                     recs = self._rec_host[:len(moved)].numpy().copy()
                     fields = self._comp.data_ptr()
                     self._cam.compensate(raw, [fields + 4 * cells * k for k in moved], h, w, st)
@@ -442,8 +425,8 @@ class FlowCounter:
             nbytes = self._mv_at + (4 * cells * n if motion else 0)
             if flowed or (motion and moved):
                 self._out_host[:nbytes].copy_(self._out[:nbytes], non_blocking=True)      # the one download
-            self._leave(cur)
-        self._event.synchronize()                    # the one wait of the call
+            self._guard.leave(cur)
+        self._guard.event.synchronize()              # the one wait of the call
         got = self._out_host.numpy()
         res = []
         for k in range(n):

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, classes as classes_, inference, overlay as overlay_, peaks, regions as regions_, tiles as tiles_, yuv as yuv_
+from . import _lib, _owned, classes as classes_, inference, overlay as overlay_, peaks, regions as regions_, tiles as tiles_, yuv as yuv_
 
 NEW_H = 384
 BOX = 64                    # exemplar crops are 64 x 64 (demo.py:67)
@@ -57,7 +57,7 @@ def pil_filter_tables(filter, in_size, out_size):
 
 
 def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    return _owned.stream_handle(device)
 
 
 def crop_resize(image, rects, oh, ow):
@@ -119,11 +119,7 @@ class FramePrep:
     buffers and device uint8 buffers (one per frame of that shape in a call).  Only the returned fp32 tensors are new."""
 
     def __init__(self, device="cuda"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.CountrError("FramePrep needs a GPU device: the HIP path has no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _owned.resolve(device, "FramePrep")
         self.L = _lib.lib()
         self._tables = {}      # (in, out) -> (bounds, weights) on the device
         self._slots = {}       # (H, W) -> [_Slot, ...]
@@ -248,18 +244,9 @@ class FramePrep:
         return out
 
 
-_PREPS = {}
-
-
 def frame_prep(device):
     """The FramePrep of a device, made on first use (count_frames keeps its tables and workspaces here between calls)."""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    p = _PREPS.get(device)
-    if p is None:
-        p = _PREPS[device] = FramePrep(device)
-    return p
+    return _owned.instance(FramePrep, device)
 
 
 def prepare_items(device, frames, boxes=None, prep=None, new_h=NEW_H):

@@ -16,7 +16,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _owned
 
 MAX_SETS, MAX_POINTS = _lib.MATCH_MAX_SETS, _lib.MATCH_MAX_POINTS
 
@@ -137,32 +137,19 @@ class PointMatcher:
     mirrors; they grow monotonically, so a steady stream of calls allocates nothing but its (host) results."""
 
     def __init__(self, device="cuda"):
-        import torch
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.CountrError("PointMatcher needs a GPU device: the HIP path has no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _owned.resolve(device, "PointMatcher")
         self.L = _lib.lib()
         self._descs = (_lib.MatchSet * MAX_SETS)()
         self._ws = None             # uint8, one chunk's scratch (the chunks of a call follow each other on one stream)
         self._pts = self._pts_host = None           # float32: every set's pred then gt, as (x, y) pairs
         self._out = self._out_host = None           # int32: match [sum P] | match_d2 [sum P] (float bits) | counts [n]
-        self._event = None
-        self._last = None           # the stream of the previous call: another stream waits for its event before it reuses the buffers
+        self._guard = _owned.Guard(self.device)     # a call on another stream than the previous one waits before it reuses the buffers
 
     def _reserve(self, ws_bytes, floats, ints):
         import torch
-        if self._ws is None or self._ws.numel() < ws_bytes:
-            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-        if self._pts is None or self._pts.numel() < floats:
-            self._pts = torch.empty(floats, dtype=torch.float32, device=self.device)
-            self._pts_host = torch.empty(floats, dtype=torch.float32).pin_memory()
-        if self._out is None or self._out.numel() < ints:
-            self._out = torch.empty(ints, dtype=torch.int32, device=self.device)
-            self._out_host = torch.empty(ints, dtype=torch.int32).pin_memory()
-        if self._event is None:
-            self._event = torch.cuda.Event()
+        _owned.grow(self, "_ws", ws_bytes, torch.uint8)
+        _owned.grow(self, "_pts", floats, torch.float32, pinned=True)
+        _owned.grow(self, "_out", ints, torch.int32, pinned=True)
 
     def match(self, sets):
         """sets: [(pred [P, 2], gt [G, 2], max_dist), ...] on the host -> [(match int32 [P], d2 float32 [P], matched), ...] as numpy
@@ -185,9 +172,7 @@ class PointMatcher:
         ints = 2 * total_p + n
         with torch.cuda.device(self.device):
             self._reserve(ws_bytes, floats, ints)
-            cur = torch.cuda.current_stream(self.device)
-            if self._last is not None and self._last != cur:
-                cur.wait_event(self._event)
+            cur = self._guard.enter()
             stage = self._pts_host.numpy()
             at, where = 0, []
             for p, g, _m in sets:
@@ -208,9 +193,8 @@ class PointMatcher:
                 _lib.check(self.L.countr_match_points(self._descs, len(part), out, out + 4 * total_p, out + 4 * (2 * total_p + c0),
                                                       self._ws.data_ptr(), st), "countr_match_points")
             self._out_host[:ints].copy_(self._out[:ints], non_blocking=True)              # the one download
-            self._event.record(cur)
-            self._last = cur
-        self._event.synchronize()                    # the one wait of the call
+            self._guard.leave(cur)
+        self._guard.event.synchronize()              # the one wait of the call
         got = self._out_host[:ints].numpy()
         res, off = [], 0
         for s, (p, _g, _m) in enumerate(sets):
@@ -220,16 +204,6 @@ class PointMatcher:
         return res
 
 
-_MATCHERS = {}
-
-
 def point_matcher(device):
     """The PointMatcher of a device, made on first use (the evaluation CLI keeps its buffers here between groups)."""
-    import torch
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    m = _MATCHERS.get(device)
-    if m is None:
-        m = _MATCHERS[device] = PointMatcher(device)
-    return m
+    return _owned.instance(PointMatcher, device)

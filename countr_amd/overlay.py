@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _owned
 
 K = {k[len("COUNTR_OVERLAY_"):]: v for k, v in _lib.OVERLAY_CONSTS.items()}
 OUTPUTS = {"rgb": K["RGB"], "nv12": K["NV12"], "nv21": K["NV21"], "i420": K["I420"]}
@@ -285,11 +285,7 @@ class Overlay:
 
     def __init__(self, device="cuda"):
         import torch
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.CountrError("Overlay needs a GPU device: the HIP path has no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _owned.resolve(device, "Overlay")
         self.L = _lib.overlay_lib()
         self._packs = []       # [_Pack, ...], one per call of a render
         self._rgb = {}         # (H, W) -> [uint8 [H, W, 3], ...]
@@ -424,16 +420,6 @@ class Overlay:
         return result
 
 
-_OVERLAYS = {}
-
-
 def overlay_for(device):
     """The Overlay of a device, made on first use (annotate_frames keeps its buffers here between calls)."""
-    import torch
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    o = _OVERLAYS.get(device)
-    if o is None:
-        o = _OVERLAYS[device] = Overlay(device)
-    return o
+    return _owned.instance(Overlay, device)

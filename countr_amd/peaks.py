@@ -14,7 +14,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _owned
 
 MAX_MAPS, MAX_RADIUS, MAX_CAP = _lib.PEAKS_MAX_MAPS, _lib.PEAKS_MAX_RADIUS, _lib.PEAKS_MAX_POINTS
 REC = 6                     # {y, x, score, cy, cx, mass}
@@ -79,31 +79,18 @@ class PeakFinder:
     monotonically, so a steady stream of calls allocates nothing but its (host) results."""
 
     def __init__(self, device="cuda"):
-        import torch
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.CountrError("PeakFinder needs a GPU device: the HIP path has no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _owned.resolve(device, "PeakFinder")
         self.L = _lib.lib()
         self._descs = (_lib.PeakMap * MAX_MAPS)()
         self._ws = None             # uint8, one chunk's scratch (the chunks of a call follow each other on one stream)
         self._totals = self._recs = self._totals_host = self._recs_host = None
-        self._event = None
-        self._last = None           # the stream of the previous call: another stream waits for its event before it reuses the buffers
+        self._guard = _owned.Guard(self.device)     # a call on another stream than the previous one waits before it reuses the buffers
 
     def _reserve(self, ws_bytes, nmaps, cap):
         import torch
-        if self._ws is None or self._ws.numel() < ws_bytes:
-            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-        if self._totals is None or self._totals.numel() < nmaps:
-            self._totals = torch.empty(nmaps, dtype=torch.int32, device=self.device)
-            self._totals_host = torch.empty(nmaps, dtype=torch.int32).pin_memory()
-        if self._recs is None or self._recs.numel() < nmaps * cap * REC:
-            self._recs = torch.empty(nmaps * cap * REC, dtype=torch.float32, device=self.device)
-            self._recs_host = torch.empty(nmaps * cap * REC, dtype=torch.float32).pin_memory()
-        if self._event is None:
-            self._event = torch.cuda.Event()
+        _owned.grow(self, "_ws", ws_bytes, torch.uint8)
+        _owned.grow(self, "_totals", nmaps, torch.int32, pinned=True)
+        _owned.grow(self, "_recs", nmaps * cap * REC, torch.float32, pinned=True)
 
     def find(self, maps, radius=4, threshold=0.0, rel_threshold=0.1, max_points=4096):
         """maps: fp32 [h, w] device tensors (contiguous; sizes free per map) -> [Peaks(total, yx int32 [P, 2], score [P], centroid
@@ -125,9 +112,7 @@ class PeakFinder:
             ws_bytes = max(ws_bytes, b)
         with torch.cuda.device(self.device):
             self._reserve(ws_bytes, n, cap)
-            cur = torch.cuda.current_stream(self.device)
-            if self._last is not None and self._last != cur:
-                cur.wait_event(self._event)
+            cur = self._guard.enter()
             st = C.c_void_p(cur.cuda_stream)
             for c0 in range(0, n, MAX_MAPS):
                 part = maps[c0:c0 + MAX_MAPS]
@@ -138,24 +123,13 @@ class PeakFinder:
                                                        self._ws.data_ptr(), st), "countr_density_peaks")
             self._totals_host[:n].copy_(self._totals[:n], non_blocking=True)
             self._recs_host[:n * cap * REC].copy_(self._recs[:n * cap * REC], non_blocking=True)
-            self._event.record(cur)
-            self._last = cur
-        self._event.synchronize()                    # the one wait of the call
+            self._guard.leave(cur)
+        self._guard.event.synchronize()                   # the one wait of the call
         totals = self._totals_host[:n].numpy()
         recs = self._recs_host[:n * cap * REC].numpy().reshape(n, cap, REC)
         return [_split(totals[i], recs[i, :min(int(totals[i]), cap)]) for i in range(n)]
 
 
-_FINDERS = {}
-
-
 def peak_finder(device):
     """The PeakFinder of a device, made on first use (locate_frames keeps its buffers here between calls)."""
-    import torch
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    f = _FINDERS.get(device)
-    if f is None:
-        f = _FINDERS[device] = PeakFinder(device)
-    return f
+    return _owned.instance(PeakFinder, device)

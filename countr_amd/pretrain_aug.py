@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _owned
 from .data import fsc147
 from .device_aug import _Stage, _pad16
 
@@ -47,11 +47,7 @@ class PretrainAug:
     shrink.  Only the returned tensor is new in every call: PretrainStep.load() keeps a reference to it until the following step()."""
 
     def __init__(self, device="cuda"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.CountrError("PretrainAug needs a GPU device: the HIP path has no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _owned.resolve(device, "PretrainAug")
         self.L = _lib.lib()
         self._stages = [_Stage(self.device), _Stage(self.device)]
         self._turn = 0
@@ -63,21 +59,14 @@ class PretrainAug:
         ts = [self._tables, self._ws] + [t for s in self._stages for t in (s.host, s.dev)]
         return sum(t.numel() * t.element_size() for t in ts if t is not None)
 
-    def _grow(self, name, n, dtype):
-        t = getattr(self, name)
-        if t is None or t.numel() < n:
-            t = torch.empty(n, dtype=dtype, device=self.device)
-            setattr(self, name, t)
-        return t
-
     def tables(self, table):
         """The table workspace of one group (<= 16 descriptors), filled by countr_pretrain_aug_tables on the current stream ->
         (int32 device tensor, tap stride, [[first int per axis] per sample]).  The tensor is this object's workspace: the next call
         overwrites it."""
         stride, ints, _bytes, offs = layout(table)
-        tabs = self._grow("_tables", ints, torch.int32)
+        tabs = _owned.grow(self, "_tables", ints, torch.int32)
         with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            st = _owned.stream_handle(self.device)
             _lib.check(self.L.countr_pretrain_aug_tables(table, len(table), tabs.data_ptr(), st), "countr_pretrain_aug_tables")
         return tabs, stride, offs
 
@@ -94,8 +83,8 @@ class PretrainAug:
             self.launches = 0
             groups = [descriptors(entries[g0:g0 + GROUP], g0) for g0 in range(0, B, GROUP)]
             sizes = [layout(t) for t in groups]        # (every argument is checked here, before the first launch)
-            tabs = self._grow("_tables", max(s[1] for s in sizes), torch.int32)
-            ws = self._grow("_ws", max(s[2] for s in sizes), torch.uint8)
+            tabs = _owned.grow(self, "_tables", max(s[1] for s in sizes), torch.int32)
+            ws = _owned.grow(self, "_ws", max(s[2] for s in sizes), torch.uint8)
             imgs = torch.empty(B, 3, OUT, OUT, device=dev, dtype=torch.float32)
             for t in groups:
                 _lib.check(self.L.countr_pretrain_aug_tables(t, len(t), tabs.data_ptr(), st), "countr_pretrain_aug_tables")

@@ -16,7 +16,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _owned
 
 MAX_MAPS, MAX_POLYGONS = _lib.EXT_CONSTS["COUNTR_REGIONS_MAX_MAPS"], _lib.EXT_CONSTS["COUNTR_REGIONS_MAX_REGIONS"]
 MAX_VERTICES, MAX_CELLS = _lib.EXT_CONSTS["COUNTR_REGIONS_MAX_VERTICES"], _lib.EXT_CONSTS["COUNTR_REGIONS_MAX_CELLS"]
@@ -181,33 +181,20 @@ class RegionSummer:
     pinned); they grow monotonically, so a steady stream of calls allocates nothing but its (host) results."""
 
     def __init__(self, device="cuda"):
-        import torch
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.CountrError("RegionSummer needs a GPU device: the HIP path has no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _owned.resolve(device, "RegionSummer")
         self.L = _lib.ext_lib()
         self._maps = (_lib.RegionMap * MAX_MAPS)()
         self._regs = (_lib.Region * (MAX_POLYGONS + MAX_GRIDS))()
         self._ws = None             # uint8, one chunk's scratch (the chunks of a call follow each other on one stream)
         self._data = self._data_host = None         # float64: per chunk its maps' placements, then its regions' coordinates
         self._out = self._out_host = None           # int32: mass [slots] (float bits) | area [slots] | total [jobs] (float bits)
-        self._event = None
-        self._last = None           # the stream of the previous call: another stream waits for its event before it reuses the buffers
+        self._guard = _owned.Guard(self.device)     # a call on another stream than the previous one waits before it reuses the buffers
 
     def _reserve(self, ws_bytes, doubles, ints):
         import torch
-        if self._ws is None or self._ws.numel() < ws_bytes:
-            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-        if self._data is None or self._data.numel() < doubles:
-            self._data = torch.empty(doubles, dtype=torch.float64, device=self.device)
-            self._data_host = torch.empty(doubles, dtype=torch.float64).pin_memory()
-        if self._out is None or self._out.numel() < ints:
-            self._out = torch.empty(ints, dtype=torch.int32, device=self.device)
-            self._out_host = torch.empty(ints, dtype=torch.int32).pin_memory()
-        if self._event is None:
-            self._event = torch.cuda.Event()
+        _owned.grow(self, "_ws", ws_bytes, torch.uint8)
+        _owned.grow(self, "_data", doubles, torch.float64, pinned=True)
+        _owned.grow(self, "_out", ints, torch.int32, pinned=True)
 
     def _describe(self, maps, cm, cr, base):
         """The host descriptors of one chunk (indices into data are relative to the chunk's part of the upload)."""
@@ -297,9 +284,7 @@ class RegionSummer:
                     _lib.ext_check(min(b, 0), "countr_regions_workspace")
                     ws_bytes = max(ws_bytes, b)
             self._reserve(ws_bytes, doubles, ints)
-            cur = torch.cuda.current_stream(self.device)
-            if self._last is not None and self._last != cur:
-                cur.wait_event(self._event)
+            cur = self._guard.enter()
             self._data[:doubles].copy_(self._data_host[:doubles], non_blocking=True)      # the one upload
             st = C.c_void_p(cur.cuda_stream)
             out, job0 = self._out.data_ptr(), 0
@@ -316,9 +301,8 @@ class RegionSummer:
                     self._out[2 * nslots + job0:2 * nslots + job0 + len(chunk)].zero_()
                 job0 += len(chunk)
             self._out_host[:ints].copy_(self._out[:ints], non_blocking=True)              # the one download
-            self._event.record(cur)
-            self._last = cur
-        self._event.synchronize()                    # the one wait of the call
+            self._guard.leave(cur)
+        self._guard.event.synchronize()              # the one wait of the call
         got = self._out_host[:ints].numpy()
         res = [[[], [], None] for _ in sets]
         at, job = 0, 0
@@ -332,16 +316,6 @@ class RegionSummer:
         return [(np.concatenate(m), np.concatenate(a), t) for m, a, t in res]
 
 
-_SUMMERS = {}
-
-
 def region_summer(device):
     """The RegionSummer of a device, made on first use (count_regions and the evaluation CLI keep its buffers here between calls)."""
-    import torch
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    f = _SUMMERS.get(device)
-    if f is None:
-        f = _SUMMERS[device] = RegionSummer(device)
-    return f
+    return _owned.instance(RegionSummer, device)

@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, inference
+from . import _lib, _owned, inference
 
 TILE = _lib.TILES_CONSTS["COUNTR_TILES_SIZE"]
 MAX_STARTS, MAX_RECTS = _lib.TILES_CONSTS["COUNTR_TILES_MAX_STARTS"], _lib.TILES_CONSTS["COUNTR_TILES_MAX_RECTS"]
@@ -89,21 +89,16 @@ class TileStitcher:
     begin(ntiles) -> put(first, rows) per forward -> stitch(...), all on the current stream; stitch waits once."""
 
     def __init__(self, device="cuda"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.CountrError("TileStitcher needs a GPU device: the HIP path has no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _owned.resolve(device, "TileStitcher")
         self.L = _lib.tiles_lib()
         self._outs = None           # fp32 [T, 384, 384]: the tile maps of one frame, band-major
         self._ws = None             # uint8: the blend's partials
         self._sums = torch.empty(1 + MAX_RECTS, dtype=torch.float32, device=self.device)
         self._sums_host = torch.empty(1 + MAX_RECTS, dtype=torch.float32).pin_memory()
-        self._event = torch.cuda.Event()
-        self._last = None           # the stream of the previous frame: another stream waits for its event before it reuses the buffers
+        self._guard = _owned.Guard(self.device)     # a frame on another stream than the previous one waits before it reuses the buffers
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _owned.stream_handle(self.device)
 
     def gather(self, image, tiles, dst):
         """tiles [(row, col), ...] of image [1, 3, hk, wk] (or [3, hk, wk]; fp32, contiguous) -> dst[:len(tiles)], dst being a contiguous
@@ -124,9 +119,7 @@ class TileStitcher:
     def begin(self, ntiles):
         """The tile-output buffer of a frame of ntiles tiles, [ntiles, 384, 384]; valid until the next begin."""
         with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream(self.device)
-            if self._last is not None and self._last != cur:
-                cur.wait_event(self._event)
+            self._guard.enter()
             if self._outs is None or self._outs.shape[0] < ntiles:
                 self._outs = torch.empty(ntiles, TILE, TILE, dtype=torch.float32, device=self.device)
         return self._outs[:ntiles]
@@ -147,8 +140,7 @@ class TileStitcher:
         with torch.cuda.device(self.device):
             need = self.L.countr_tiles_workspace(int(hk), int(wk))
             _lib.tiles_check(min(need, 0), "countr_tiles_workspace")
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _owned.grow(self, "_ws", need, torch.uint8)
             dm = torch.empty(int(hk), int(wk), dtype=torch.float32, device=self.device)
             flat = [v for r in rects for v in r]
             _lib.tiles_check(self.L.countr_tile_blend(outs.data_ptr(), len(row_starts), len(col_starts), _ints(row_starts), _ints(col_starts),
@@ -167,24 +159,14 @@ class TileStitcher:
         with torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
             self._sums_host[:n].copy_(sums, non_blocking=True)
-            self._event.record(cur)
-            self._last = cur
-        self._event.synchronize()
+            self._guard.leave(cur)
+        self._guard.event.synchronize()
         return dm, self._sums_host[:n].numpy().copy()
-
-
-_STITCHERS = {}
 
 
 def tile_stitcher(device):
     """The TileStitcher of a device, made on first use (count_frames keeps its buffers here between calls)."""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    s = _STITCHERS.get(device)
-    if s is None:
-        s = _STITCHERS[device] = TileStitcher(device)
-    return s
+    return _owned.instance(TileStitcher, device)
 
 
 def normalised_count(sums, rects, normalization=True):

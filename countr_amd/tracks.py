@@ -20,7 +20,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _owned
 from .match import match_host
 
 _K = {k[len("COUNTR_TRACKS_"):]: v for k, v in _lib.TRACKS_CONSTS.items()}
@@ -210,12 +210,7 @@ class Tracker:
     stream waits for the previous call's event first.  The defaults of max_missed, min_hits and beta are unmeasured."""
 
     def __init__(self, device="cuda", *, streams=1, max_dist, max_missed=2, min_hits=3, beta=0.5, lines=()):
-        import torch
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.CountrError("Tracker needs a GPU device: the HIP path has no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _owned.resolve(device, "Tracker")
         if int(streams) != streams or streams < 1:
             raise ValueError("streams is >= 1")
         self.streams = int(streams)
@@ -225,59 +220,42 @@ class Tracker:
         assert self.L.countr_tracks_state_bytes() == STATE_BYTES
         self._descs = (_lib.TracksStream * MAX_STREAMS)()
         self._ptrs = (C.c_void_p * MAX_STREAMS)()
+        import torch
         with torch.cuda.device(self.device):
             self._states = torch.zeros(self.streams, STATE_BYTES, dtype=torch.uint8, device=self.device)
             self._lines = torch.zeros(MAX_LINES * 4, dtype=torch.float32, device=self.device)
             if self.lines.size:
                 self._lines[:self.lines.size].copy_(torch.from_numpy(self.lines.reshape(-1)))
-            self._event = torch.cuda.Event()
-            self._last = torch.cuda.current_stream(self.device)
-            self._event.record(self._last)
+            self._guard = _owned.Guard(self.device, recorded=True)      # the first call on another stream waits for the fills above
         self._ws = None             # uint8, one call's scratch (the calls follow each other on one stream)
         self._pts = self._pts_host = None           # float32: every step's detections as (x, y) pairs
         self._out = self._out_host = None           # int32: ids [sum N] | events [sum N] | summaries [steps, 40]
 
     def _reserve(self, ws_bytes, floats, ints):
         import torch
-        if self._ws is None or self._ws.numel() < ws_bytes:
-            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-        if self._pts is None or self._pts.numel() < floats:
-            self._pts = torch.empty(floats, dtype=torch.float32, device=self.device)
-            self._pts_host = torch.empty(floats, dtype=torch.float32).pin_memory()
-        if self._out is None or self._out.numel() < ints:
-            self._out = torch.empty(ints, dtype=torch.int32, device=self.device)
-            self._out_host = torch.empty(ints, dtype=torch.int32).pin_memory()
-
-    def _enter(self):
-        import torch
-        cur = torch.cuda.current_stream(self.device)
-        if self._last != cur:
-            cur.wait_event(self._event)
-        return cur
-
-    def _leave(self, cur):
-        self._event.record(cur)
-        self._last = cur
+        _owned.grow(self, "_ws", ws_bytes, torch.uint8)
+        _owned.grow(self, "_pts", floats, torch.float32, pinned=True)
+        _owned.grow(self, "_out", ints, torch.int32, pinned=True)
 
     def reset(self):
         """Every tracker becomes empty at frame 0 again (on the current stream; nothing is waited for)."""
         import torch
         with torch.cuda.device(self.device):
-            cur = self._enter()
+            cur = self._guard.enter()
             for c0 in range(0, self.streams, MAX_STREAMS):
                 n = min(MAX_STREAMS, self.streams - c0)
                 for k in range(n):
                     self._ptrs[k] = self._states[c0 + k].data_ptr()
                 _lib.tracks_check(self.L.countr_tracks_reset(self._ptrs, n, C.c_void_p(cur.cuda_stream)), "countr_tracks_reset")
-            self._leave(cur)
+            self._guard.leave(cur)
 
     def state(self, stream=0):
         """The state of one tracker, downloaded (this synchronises), in the dict form of tracks_host."""
         import torch
         with torch.cuda.device(self.device):
-            cur = self._enter()
+            cur = self._guard.enter()
             raw = self._states[stream].cpu()
-            self._leave(cur)
+            self._guard.leave(cur)
         return state_from_bytes(raw.numpy().tobytes())
 
     def run(self, frames_points):
@@ -299,7 +277,7 @@ class Tracker:
         floats, ints = max(2 * total, 2), 2 * total + SUMMARY_INTS * len(steps)
         with torch.cuda.device(self.device):
             self._reserve(ws_bytes, floats, ints)
-            cur = self._enter()
+            cur = self._guard.enter()
             stage, at, where = self._pts_host.numpy(), 0, {}
             for k, (s, f) in enumerate(steps):
                 D = per[s][f]
@@ -326,8 +304,8 @@ class Tracker:
                         n += 1
                     _lib.tracks_check(self.L.countr_tracks_step(self._descs, n, self._ws.data_ptr(), st), "countr_tracks_step")
             self._out_host[:ints].copy_(self._out[:ints], non_blocking=True)              # the one download
-            self._leave(cur)
-        self._event.synchronize()                    # the one wait of the call
+            self._guard.leave(cur)
+        self._guard.event.synchronize()              # the one wait of the call
         got = self._out_host[:ints].numpy()
         res = [[] for _ in per]
         for s, f in steps:

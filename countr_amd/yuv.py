@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _owned
 
 FORMATS = {"nv12": _lib.YUV_CONSTS["COUNTR_YUV_NV12"], "nv21": _lib.YUV_CONSTS["COUNTR_YUV_NV21"],
            "i420": _lib.YUV_CONSTS["COUNTR_YUV_I420"], "p010": _lib.YUV_CONSTS["COUNTR_YUV_P010"]}
@@ -218,12 +218,7 @@ class YuvConverter:
     the next convert() overwrites them (on the same stream in order; FramePrep's guard covers another stream)."""
 
     def __init__(self, device="cuda"):
-        import torch
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.CountrError("YuvConverter needs a GPU device: the HIP path has no CPU fallback")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _owned.resolve(device, "YuvConverter")
         self.L = _lib.yuv_lib()
         self._staging = {}     # (format, H, W) -> [_Staging, ...]
         self._rgb = {}         # (H, W) -> [uint8 [H, W, 3], ...]
@@ -260,7 +255,7 @@ class YuvConverter:
         out = [None] * len(frames)
         groups, used, taken = {}, {}, {}
         with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            st = _owned.stream_handle(self.device)
             for i, f in enumerate(frames):
                 if not isinstance(f, YuvFrame):
                     raise ValueError("YuvConverter.convert: a YuvFrame is required, got %s" % type(f).__name__)

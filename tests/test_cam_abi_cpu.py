@@ -1,61 +1,31 @@
 """CPU: include/countr_hip_cam.h is the one statement of the camera library's C ABI, as the eight older headers are of theirs.
-countr_amd/_lib.py reads the binding from it and libcountr_hip_cam.so exports exactly it; checked against the library's own dynamic
-symbols and literal pins.  Every refusal runs on the host: a refused call launches nothing.  The library is stated in a second list
-(build.LATER_TAGS, _lib.LATER_LIBRARIES) by the rule of the first, which stays as its tests pin it."""
+countr_amd/_lib.py reads the binding from it and libcountr_hip_cam.so exports exactly it; pinned here by literals (the checks against
+the C compiler and the library's dynamic symbols are in tests/test_libraries_cpu.py, once per tag).  Every refusal runs on the host: a
+refused call launches nothing.  The library is the last entry of the one list of side libraries (build.TAGS)."""
 import ctypes as C
 import glob
 import io
 import os
 import re
-import subprocess
 from contextlib import redirect_stdout
 
 from countr_amd import _lib, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")      # the compiler countr_amd/build.py uses
 NAMES = ("ABI_VERSION", "MAX_FRAMES", "CELL", "MAX_SIDE", "RANGE", "BINS", "RECORD_INTS")
 EXPORTS = ["countr_cam_compensate", "countr_cam_estimate", "countr_cam_last_error", "countr_cam_version", "countr_cam_workspace"]
 OLDER = ["ext", "classes", "tiles", "yuv", "overlay", "tracks", "flow"]
 
 
-def test_header_compiles_as_c(tmp_path):
-    assert list(_lib.CAM_STRUCTS) == []
-    prints = ["COUNTR_CAM_" + n for n in NAMES]
-    src = tmp_path / "use.c"
-    src.write_text('#include <stdio.h>\n#include "countr_hip_cam.h"\nint main(void) {\n  printf("%s\\n", %s);\n  return 0;\n}\n'
-                   % (" ".join(["%d"] * len(prints)), ", ".join(prints)))
-    subprocess.check_call([HIPCC, "-x", "c", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "use")])
-    got = [int(v) for v in subprocess.check_output([str(tmp_path / "use")], text=True).split()]
-    assert got == [_lib.CAM_CONSTS["COUNTR_CAM_" + n] for n in NAMES]
-    assert list(_lib.CAM_CONSTS) == ["COUNTR_CAM_" + n for n in NAMES]
-
-
-def test_library_exports_the_header_and_nothing_else():
-    readelf = subprocess.check_output([HIPCC, "-print-prog-name=llvm-readelf"], text=True).strip()
-    rows = [line.split() for line in subprocess.check_output([readelf, "--dyn-syms", "-W", _lib.CAM_LIB_PATH], text=True).splitlines()]
-    defined = [r[7].split("@")[0] for r in rows if len(r) == 8 and r[0][:-1].isdigit() and r[6] != "UND"]
-    assert sorted(n for n in defined if n.startswith("countr_")) == _lib.cam_exported_symbols() == EXPORTS
-    assert [n for n in defined if not n.startswith(("countr_", "__hip_cuid_"))] == []
-
-
 def test_later_is_stated_once_and_by_the_rule_of_the_first_list():
     paths = glob.glob(os.path.join(ROOT, "countr_amd", "csrc_cam", "*.hip"))
-    src = "".join(open(p).read() for p in paths)
-    for name in _lib.cam_exported_symbols():
-        assert re.search(r'extern "C" [\w ]+\*? ?%s\(' % name, src), name
-    assert re.search(r"countr_cam_version\(void\) \{ return COUNTR_CAM_ABI_VERSION; \}", src)
-    # the library's sources stay outside the globs the other libraries are built from
-    others = [os.path.basename(p) for d in ["csrc"] + ["csrc_" + t for t in OLDER] for p in glob.glob(os.path.join(ROOT, "countr_amd", d, "*.hip"))]
-    assert paths and not set(os.path.basename(p) for p in paths) & set(others)
-    # the first list is whole and as it was; the second holds the camera library alone, in the same three-part form
-    assert list(build.TAGS) == list(build.SINGLE) == list(_lib.LIBRARIES) == OLDER
-    assert list(build.LATER_TAGS) == list(build.LATER) == list(_lib.LATER_LIBRARIES) == ["cam"]
-    assert build.LATER["cam"][1]() == sorted(paths)
-    assert build.LATER["cam"][0] == os.path.join(ROOT, "countr_amd", "libcountr_hip_cam.so") == os.path.normpath(_lib.CAM_LIB_PATH)
-    assert os.path.samefile(build.LATER["cam"][2], _lib.CAM_HEADER)
-    assert isinstance(_lib.LATER_LIBRARIES["cam"], _lib.Library) and _lib.LATER_LIBRARIES["cam"].tag == "cam"
-    assert len(re.findall(r"^LATER_TAGS\s*=", open(os.path.join(ROOT, "countr_amd", "build.py")).read(), re.M)) == 1
+    # one list, whole and in the order the libraries were added; the camera library is its last entry, in the same three-part form
+    assert list(build.TAGS) == list(build.SINGLE) == list(_lib.LIBRARIES) == OLDER + ["cam"]
+    assert paths and build.SINGLE["cam"][1]() == sorted(paths)
+    assert build.SINGLE["cam"][0] == os.path.join(ROOT, "countr_amd", "libcountr_hip_cam.so") == os.path.normpath(_lib.CAM_LIB_PATH)
+    assert os.path.samefile(build.SINGLE["cam"][2], _lib.CAM_HEADER)
+    assert isinstance(_lib.LIBRARIES["cam"], _lib.Library) and _lib.LIBRARIES["cam"].tag == "cam"
+    assert len(re.findall(r"^TAGS\s*=", open(os.path.join(ROOT, "countr_amd", "build.py")).read(), re.M)) == 1
     # the library is a build product: git ignores it like its siblings
     ignored = open(os.path.join(ROOT, ".gitignore")).read().split()
     assert "*.so" in ignored and "*.sha256" in ignored and "build/" in ignored
@@ -65,15 +35,20 @@ def test_build_load_checks_the_later_libraries():
     import __graft_entry__ as entry
     out = io.StringIO()
     with redirect_stdout(out):
-        entry.check_later_libraries()
+        entry.check_side_libraries()
     lines = out.getvalue().splitlines()
-    assert len(lines) == 1 and lines[0].startswith("build ok: ") and "libcountr_hip_cam.so (5 exported symbols)" in lines[0]
+    assert len(lines) == 8 and all(line.startswith("build ok: ") for line in lines)
+    assert "libcountr_hip_cam.so (5 exported symbols)" in lines[-1] and not any("libcountr_hip_cam.so" in line for line in lines[:-1])
     text = open(os.path.join(ROOT, "__graft_entry__.py")).read()
     body = text[text.index("def build():"):text.index("def smoke():")]
-    assert body.index("check_side_libraries()") < body.index("check_later_libraries()")
+    assert body.count("check_side_libraries()") == 1
 
 
 def test_version_limits_binding_and_errors():
+    # the literal pins of the header's names (what holds of every library by rule is in test_libraries_cpu.py)
+    assert list(_lib.CAM_STRUCTS) == []
+    assert list(_lib.CAM_CONSTS) == ["COUNTR_CAM_" + n for n in NAMES]
+    assert _lib.cam_exported_symbols() == EXPORTS
     tags = ["", "EXT_", "CLASSES_", "TILES_", "YUV_", "OVERLAY_", "TRACKS_", "FLOW_"]
     snapshot = lambda: [(dict(getattr(_lib, t + "CONSTS")), dict(getattr(_lib, t + "STRUCTS")), dict(getattr(_lib, t + "PROTOS")),
                          getattr(_lib, (t.lower() if t else "") + "exported_symbols")()) for t in tags]

@@ -1,63 +1,24 @@
 """CPU: include/countr_hip_flow.h is the one statement of the flow library's C ABI, as the seven older headers are of theirs.
-countr_amd/_lib.py reads the binding from it and libcountr_hip_flow.so exports exactly it; checked against the library's own dynamic
-symbols and literal pins.  Every refusal runs on the host: a refused call launches nothing."""
+countr_amd/_lib.py reads the binding from it and libcountr_hip_flow.so exports exactly it; pinned here by literals (the checks against
+the C compiler and the library's dynamic symbols are in tests/test_libraries_cpu.py, once per tag).  Every refusal runs on the host: a
+refused call launches nothing."""
 import ctypes as C
-import glob
-import os
-import re
-import subprocess
 
-from countr_amd import _lib
+from countr_amd import _lib, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")      # the compiler countr_amd/build.py uses
 NAMES = ("ABI_VERSION", "MAX_FRAMES", "MAX_LINES", "MAX_SEARCH", "MAX_INTERVAL", "CELL", "MAX_SIDE", "OUT_FLOATS")
 FIELDS = ("map", "motion", "out", "sx", "tx", "sy", "ty")
 EXPORTS = ["countr_flow_flux", "countr_flow_last_error", "countr_flow_luma", "countr_flow_motion", "countr_flow_version", "countr_flow_workspace"]
 
 
-def test_header_compiles_as_c_and_the_struct_has_the_compiler_s_layout(tmp_path):
-    assert list(_lib.FLOW_STRUCTS) == ["countr_flow_map"]
-    S = _lib.FlowMap
-    assert [f[0] for f in S._fields_] == list(FIELDS)
-    prints = ["COUNTR_FLOW_" + n for n in NAMES] + ["(int)sizeof(countr_flow_map)"] + ["(int)offsetof(countr_flow_map, %s)" % f for f in FIELDS]
-    src = tmp_path / "use.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "countr_hip_flow.h"\nint main(void) {\n  printf("%s\\n", %s);\n  return 0;\n}\n'
-                   % (" ".join(["%d"] * len(prints)), ", ".join(prints)))
-    subprocess.check_call([HIPCC, "-x", "c", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "use")])
-    got = [int(v) for v in subprocess.check_output([str(tmp_path / "use")], text=True).split()]
-    assert got[:len(NAMES)] == [_lib.FLOW_CONSTS["COUNTR_FLOW_" + n] for n in NAMES]
-    assert list(_lib.FLOW_CONSTS) == ["COUNTR_FLOW_" + n for n in NAMES]
-    assert got[len(NAMES)] == C.sizeof(S) == 56 and got[len(NAMES) + 1:] == [getattr(S, f).offset for f in FIELDS]
-
-
-def test_library_exports_the_header_and_nothing_else():
-    readelf = subprocess.check_output([HIPCC, "-print-prog-name=llvm-readelf"], text=True).strip()
-    rows = [line.split() for line in subprocess.check_output([readelf, "--dyn-syms", "-W", _lib.FLOW_LIB_PATH], text=True).splitlines()]
-    defined = [r[7].split("@")[0] for r in rows if len(r) == 8 and r[0][:-1].isdigit() and r[6] != "UND"]
-    assert sorted(n for n in defined if n.startswith("countr_")) == _lib.flow_exported_symbols() == EXPORTS
-    assert [n for n in defined if not n.startswith(("countr_", "__hip_cuid_"))] == []
-
-
-def test_every_prototype_is_defined_extern_c_in_the_sources():
-    paths = glob.glob(os.path.join(ROOT, "countr_amd", "csrc_flow", "*.hip"))
-    src = "".join(open(p).read() for p in paths)
-    for name in _lib.flow_exported_symbols():
-        assert re.search(r'extern "C" [\w ]+\*? ?%s\(' % name, src), name
-    assert re.search(r"countr_flow_version\(void\) \{ return COUNTR_FLOW_ABI_VERSION; \}", src)
-    # the library's sources stay outside the globs the other libraries are built from
-    others = [os.path.basename(p) for d in ("csrc", "csrc_ext", "csrc_classes", "csrc_tiles", "csrc_yuv", "csrc_overlay", "csrc_tracks")
-              for p in glob.glob(os.path.join(ROOT, "countr_amd", d, "*.hip"))]
-    assert paths and not set(os.path.basename(p) for p in paths) & set(others)
-    from countr_amd import build
-    # the one table of the side libraries, whole and in the order they were added
-    assert list(build.SINGLE) == ["ext", "classes", "tiles", "yuv", "overlay", "tracks", "flow"]
-    assert build.SINGLE["flow"][1]() == sorted(paths)
-    assert build.SINGLE["flow"][0] == os.path.join(ROOT, "countr_amd", "libcountr_hip_flow.so")
-    assert os.path.samefile(build.SINGLE["flow"][2], _lib.FLOW_HEADER)
-
-
 def test_version_limits_binding_and_errors():
+    # the literal pins of the header's names (what holds of every library by rule is in test_libraries_cpu.py)
+    assert list(_lib.FLOW_STRUCTS) == ["countr_flow_map"]
+    assert [f[0] for f in _lib.FlowMap._fields_] == list(FIELDS) and C.sizeof(_lib.FlowMap) == 56
+    assert list(_lib.FLOW_CONSTS) == ["COUNTR_FLOW_" + n for n in NAMES]
+    assert _lib.flow_exported_symbols() == EXPORTS
+    # the one table of the side libraries, in the order they were added, up to this one
+    assert list(build.SINGLE)[:7] == ["ext", "classes", "tiles", "yuv", "overlay", "tracks", "flow"]
     snapshot = lambda: (dict(_lib.CONSTS), dict(_lib.STRUCTS), dict(_lib.PROTOS), _lib.exported_symbols(),
                         dict(_lib.EXT_CONSTS), dict(_lib.EXT_STRUCTS), dict(_lib.EXT_PROTOS), _lib.ext_exported_symbols(),
                         dict(_lib.CLASSES_CONSTS), dict(_lib.CLASSES_STRUCTS), dict(_lib.CLASSES_PROTOS), _lib.classes_exported_symbols(),

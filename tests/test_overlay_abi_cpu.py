@@ -1,65 +1,25 @@
 """CPU: include/countr_hip_overlay.h is the one statement of the overlay library's C ABI, as the five older headers are of theirs.
-countr_amd/_lib.py reads the binding from it and libcountr_hip_overlay.so exports exactly it; checked against the library's own dynamic
-symbols and literal pins.  Every refusal runs on the host: a refused call launches nothing."""
+countr_amd/_lib.py reads the binding from it and libcountr_hip_overlay.so exports exactly it; pinned here by literals (the checks
+against the C compiler and the library's dynamic symbols are in tests/test_libraries_cpu.py, once per tag).  Every refusal runs on the
+host: a refused call launches nothing."""
 import ctypes as C
-import glob
-import os
-import re
-import subprocess
 
-from countr_amd import _lib
+from countr_amd import _lib, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")      # the compiler countr_amd/build.py uses
 NAMES = ("ABI_VERSION", "MAX_FRAMES", "MAX_SIDE", "MAX_POINTS", "MAX_POLYGONS", "MAX_VERTICES", "MAX_RADIUS", "PATCH_H", "PATCH_W", "PACK_GAINS",
          "PACK_LUT", "PACK_HEAD", "RGB", "NV12", "NV21", "I420", "BT601", "BT709", "LIMITED", "FULL")
 FIELDS = ("rgb", "map", "out", "yuv", "poly_verts", "gain_max", "n_points", "points_off", "n_polys", "n_edges", "edges_off", "lh", "lw", "lx", "ly",
           "patch_off")
 
 
-def test_header_compiles_as_c_and_the_struct_has_the_compiler_s_layout(tmp_path):
+def test_version_limits_binding_and_errors():
+    # the literal pins of the header's names (what holds of every library by rule is in test_libraries_cpu.py)
     assert list(_lib.OVERLAY_STRUCTS) == ["countr_overlay_frame"]
-    S = _lib.OverlayFrame
-    assert [f[0] for f in S._fields_] == list(FIELDS)
-    prints = ["COUNTR_OVERLAY_" + n for n in NAMES] + ["(int)sizeof(countr_overlay_frame)"] + ["(int)offsetof(countr_overlay_frame, %s)" % f for f in FIELDS]
-    src = tmp_path / "use.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "countr_hip_overlay.h"\nint main(void) {\n  printf("%s\\n", %s);\n  return 0;\n}\n'
-                   % (" ".join(["%d"] * len(prints)), ", ".join(prints)))
-    subprocess.check_call([HIPCC, "-x", "c", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "use")])
-    got = [int(v) for v in subprocess.check_output([str(tmp_path / "use")], text=True).split()]
-    assert got[:len(NAMES)] == [_lib.OVERLAY_CONSTS["COUNTR_OVERLAY_" + n] for n in NAMES]
+    assert [f[0] for f in _lib.OverlayFrame._fields_] == list(FIELDS)
     assert list(_lib.OVERLAY_CONSTS) == ["COUNTR_OVERLAY_" + n for n in NAMES]
-    assert got[len(NAMES)] == C.sizeof(S) and got[len(NAMES) + 1:] == [getattr(S, f).offset for f in FIELDS]
-
-
-def test_library_exports_the_header_and_nothing_else():
-    readelf = subprocess.check_output([HIPCC, "-print-prog-name=llvm-readelf"], text=True).strip()
-    rows = [line.split() for line in subprocess.check_output([readelf, "--dyn-syms", "-W", _lib.OVERLAY_LIB_PATH], text=True).splitlines()]
-    defined = [r[7].split("@")[0] for r in rows if len(r) == 8 and r[0][:-1].isdigit() and r[6] != "UND"]
-    assert sorted(n for n in defined if n.startswith("countr_")) == _lib.overlay_exported_symbols()
     assert _lib.overlay_exported_symbols() == ["countr_overlay_last_error", "countr_overlay_render", "countr_overlay_version"]
-    assert [n for n in defined if not n.startswith(("countr_", "__hip_cuid_"))] == []
-
-
-def test_every_prototype_is_defined_extern_c_in_the_sources():
-    paths = glob.glob(os.path.join(ROOT, "countr_amd", "csrc_overlay", "*.hip"))
-    src = "".join(open(p).read() for p in paths)
-    for name in _lib.overlay_exported_symbols():
-        assert re.search(r'extern "C" [\w ]+\*? ?%s\(' % name, src), name
-    assert re.search(r"countr_overlay_version\(void\) \{ return COUNTR_OVERLAY_ABI_VERSION; \}", src)
-    # the library's sources stay outside the globs the other libraries are built from
-    others = [os.path.basename(p) for d in ("csrc", "csrc_ext", "csrc_classes", "csrc_tiles", "csrc_yuv")
-              for p in glob.glob(os.path.join(ROOT, "countr_amd", d, "*.hip"))]
-    assert paths and not set(os.path.basename(p) for p in paths) & set(others)
-    from countr_amd import build
     # the one table of the side libraries, in the order they were added, up to this one
     assert list(build.SINGLE)[:5] == ["ext", "classes", "tiles", "yuv", "overlay"]
-    assert build.SINGLE["overlay"][1]() == sorted(paths)
-    assert build.SINGLE["overlay"][0] == os.path.join(ROOT, "countr_amd", "libcountr_hip_overlay.so")
-    assert os.path.samefile(build.SINGLE["overlay"][2], _lib.OVERLAY_HEADER)
-
-
-def test_version_limits_binding_and_errors():
     snapshot = lambda: (dict(_lib.CONSTS), dict(_lib.STRUCTS), dict(_lib.PROTOS), _lib.exported_symbols(),
                         dict(_lib.EXT_CONSTS), dict(_lib.EXT_STRUCTS), dict(_lib.EXT_PROTOS), _lib.ext_exported_symbols(),
                         dict(_lib.CLASSES_CONSTS), dict(_lib.CLASSES_STRUCTS), dict(_lib.CLASSES_PROTOS), _lib.classes_exported_symbols(),

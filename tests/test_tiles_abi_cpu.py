@@ -1,54 +1,20 @@
 """CPU: include/countr_hip_tiles.h is the one statement of the tiles library's C ABI, as the three older headers are of theirs.
-countr_amd/_lib.py reads the binding from it and libcountr_hip_tiles.so exports exactly it; checked against the library's own dynamic
-symbols and literal pins.  The size query and every refusal run on the host: a refused call launches nothing."""
+countr_amd/_lib.py reads the binding from it and libcountr_hip_tiles.so exports exactly it; pinned here by literals (the checks against
+the C compiler and the library's dynamic symbols are in tests/test_libraries_cpu.py, once per tag).  The size query and every refusal
+run on the host: a refused call launches nothing."""
 import ctypes as C
-import glob
-import os
-import re
-import subprocess
 
-from countr_amd import _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")      # the compiler countr_amd/build.py uses
-
-
-def test_header_has_no_structs_and_compiles_as_c(tmp_path):
-    assert list(_lib.TILES_STRUCTS) == []          # plain pointers and sizes only: there is no layout to check against the compiler
-    src = tmp_path / "use.c"
-    src.write_text('#include <stdio.h>\n#include "countr_hip_tiles.h"\nint main(void) {\n  printf("%d %d %d %d %d\\n", '
-                   "COUNTR_TILES_ABI_VERSION, COUNTR_TILES_SIZE, COUNTR_TILES_MAX_STARTS, COUNTR_TILES_MAX_RECTS, COUNTR_TILES_MAX_ZOOM);\n"
-                   "  return 0;\n}\n")
-    subprocess.check_call([HIPCC, "-x", "c", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "use")])
-    got = subprocess.check_output([str(tmp_path / "use")], text=True).split()
-    assert [int(v) for v in got] == [_lib.TILES_CONSTS[k] for k in ("COUNTR_TILES_ABI_VERSION", "COUNTR_TILES_SIZE", "COUNTR_TILES_MAX_STARTS",
-                                                                     "COUNTR_TILES_MAX_RECTS", "COUNTR_TILES_MAX_ZOOM")]
-
-
-def test_library_exports_the_header_and_nothing_else():
-    readelf = subprocess.check_output([HIPCC, "-print-prog-name=llvm-readelf"], text=True).strip()
-    rows = [line.split() for line in subprocess.check_output([readelf, "--dyn-syms", "-W", _lib.TILES_LIB_PATH], text=True).splitlines()]
-    defined = [r[7].split("@")[0] for r in rows if len(r) == 8 and r[0][:-1].isdigit() and r[6] != "UND"]
-    assert sorted(n for n in defined if n.startswith("countr_")) == _lib.tiles_exported_symbols()
-    assert _lib.tiles_exported_symbols() == ["countr_tile_blend", "countr_tile_gather", "countr_tiles_last_error", "countr_tiles_version",
-                                             "countr_tiles_workspace"]
-    assert [n for n in defined if not n.startswith(("countr_", "__hip_cuid_"))] == []
-
-
-def test_every_prototype_is_defined_extern_c_in_the_sources():
-    paths = glob.glob(os.path.join(ROOT, "countr_amd", "csrc_tiles", "*.hip"))
-    src = "".join(open(p).read() for p in paths)
-    for name in _lib.tiles_exported_symbols():
-        assert re.search(r'extern "C" [\w ]+\*? ?%s\(' % name, src), name
-    assert re.search(r"countr_tiles_version\(void\) \{ return COUNTR_TILES_ABI_VERSION; \}", src)
-    # the library's sources stay outside the globs the other libraries are built from
-    others = [os.path.basename(p) for d in ("csrc", "csrc_ext", "csrc_classes") for p in glob.glob(os.path.join(ROOT, "countr_amd", d, "*.hip"))]
-    assert paths and not set(os.path.basename(p) for p in paths) & set(others)
-    from countr_amd import build
-    assert list(build.SINGLE)[:3] == ["ext", "classes", "tiles"] and build.SINGLE["tiles"][1]() == sorted(paths)
+from countr_amd import _lib, build
 
 
 def test_version_limits_binding_and_errors():
+    # the literal pins of the header's names (what holds of every library by rule is in test_libraries_cpu.py)
+    assert list(_lib.TILES_STRUCTS) == []          # plain pointers and sizes only
+    assert list(_lib.TILES_CONSTS)[:5] == ["COUNTR_TILES_ABI_VERSION", "COUNTR_TILES_SIZE", "COUNTR_TILES_MAX_STARTS", "COUNTR_TILES_MAX_RECTS",
+                                           "COUNTR_TILES_MAX_ZOOM"]
+    assert _lib.tiles_exported_symbols() == ["countr_tile_blend", "countr_tile_gather", "countr_tiles_last_error", "countr_tiles_version",
+                                             "countr_tiles_workspace"]
+    assert list(build.SINGLE)[:3] == ["ext", "classes", "tiles"]
     snapshot = lambda: (dict(_lib.CONSTS), dict(_lib.STRUCTS), dict(_lib.PROTOS), _lib.exported_symbols(),
                         dict(_lib.EXT_CONSTS), dict(_lib.EXT_STRUCTS), dict(_lib.EXT_PROTOS), _lib.ext_exported_symbols(),
                         dict(_lib.CLASSES_CONSTS), dict(_lib.CLASSES_STRUCTS), dict(_lib.CLASSES_PROTOS), _lib.classes_exported_symbols())

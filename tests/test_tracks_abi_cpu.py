@@ -1,64 +1,25 @@
 """CPU: include/countr_hip_tracks.h is the one statement of the tracks library's C ABI, as the six older headers are of theirs.
-countr_amd/_lib.py reads the binding from it and libcountr_hip_tracks.so exports exactly it; checked against the library's own dynamic
-symbols and literal pins.  Every refusal runs on the host: a refused call launches nothing."""
+countr_amd/_lib.py reads the binding from it and libcountr_hip_tracks.so exports exactly it; pinned here by literals (the checks against
+the C compiler and the library's dynamic symbols are in tests/test_libraries_cpu.py, once per tag).  Every refusal runs on the host: a
+refused call launches nothing."""
 import ctypes as C
-import glob
-import os
-import re
-import subprocess
 
-from countr_amd import _lib
+from countr_amd import _lib, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")      # the compiler countr_amd/build.py uses
 NAMES = ("ABI_VERSION", "MAX_STREAMS", "MAX_TRACKS", "MAX_POINTS", "MAX_LINES", "HEAD_INTS", "FIELDS", "SUMMARY_INTS")
 FIELDS = ("state", "points", "ids", "events", "summary", "lines", "N", "L", "max_dist", "beta", "max_missed", "min_hits")
 EXPORTS = ["countr_tracks_last_error", "countr_tracks_reset", "countr_tracks_state_bytes", "countr_tracks_step", "countr_tracks_version",
            "countr_tracks_workspace"]
 
 
-def test_header_compiles_as_c_and_the_struct_has_the_compiler_s_layout(tmp_path):
+def test_version_limits_binding_and_errors():
+    # the literal pins of the header's names (what holds of every library by rule is in test_libraries_cpu.py)
     assert list(_lib.TRACKS_STRUCTS) == ["countr_tracks_stream"]
-    S = _lib.TracksStream
-    assert [f[0] for f in S._fields_] == list(FIELDS)
-    prints = ["COUNTR_TRACKS_" + n for n in NAMES] + ["(int)sizeof(countr_tracks_stream)"] + ["(int)offsetof(countr_tracks_stream, %s)" % f for f in FIELDS]
-    src = tmp_path / "use.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "countr_hip_tracks.h"\nint main(void) {\n  printf("%s\\n", %s);\n  return 0;\n}\n'
-                   % (" ".join(["%d"] * len(prints)), ", ".join(prints)))
-    subprocess.check_call([HIPCC, "-x", "c", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "use")])
-    got = [int(v) for v in subprocess.check_output([str(tmp_path / "use")], text=True).split()]
-    assert got[:len(NAMES)] == [_lib.TRACKS_CONSTS["COUNTR_TRACKS_" + n] for n in NAMES]
+    assert [f[0] for f in _lib.TracksStream._fields_] == list(FIELDS) and C.sizeof(_lib.TracksStream) == 72
     assert list(_lib.TRACKS_CONSTS) == ["COUNTR_TRACKS_" + n for n in NAMES]
-    assert got[len(NAMES)] == C.sizeof(S) == 72 and got[len(NAMES) + 1:] == [getattr(S, f).offset for f in FIELDS]
-
-
-def test_library_exports_the_header_and_nothing_else():
-    readelf = subprocess.check_output([HIPCC, "-print-prog-name=llvm-readelf"], text=True).strip()
-    rows = [line.split() for line in subprocess.check_output([readelf, "--dyn-syms", "-W", _lib.TRACKS_LIB_PATH], text=True).splitlines()]
-    defined = [r[7].split("@")[0] for r in rows if len(r) == 8 and r[0][:-1].isdigit() and r[6] != "UND"]
-    assert sorted(n for n in defined if n.startswith("countr_")) == _lib.tracks_exported_symbols() == EXPORTS
-    assert [n for n in defined if not n.startswith(("countr_", "__hip_cuid_"))] == []
-
-
-def test_every_prototype_is_defined_extern_c_in_the_sources():
-    paths = glob.glob(os.path.join(ROOT, "countr_amd", "csrc_tracks", "*.hip"))
-    src = "".join(open(p).read() for p in paths)
-    for name in _lib.tracks_exported_symbols():
-        assert re.search(r'extern "C" [\w ]+\*? ?%s\(' % name, src), name
-    assert re.search(r"countr_tracks_version\(void\) \{ return COUNTR_TRACKS_ABI_VERSION; \}", src)
-    # the library's sources stay outside the globs the other libraries are built from
-    others = [os.path.basename(p) for d in ("csrc", "csrc_ext", "csrc_classes", "csrc_tiles", "csrc_yuv", "csrc_overlay")
-              for p in glob.glob(os.path.join(ROOT, "countr_amd", d, "*.hip"))]
-    assert paths and not set(os.path.basename(p) for p in paths) & set(others)
-    from countr_amd import build
+    assert _lib.tracks_exported_symbols() == EXPORTS
     # the one table of the side libraries, in the order they were added, up to this one
     assert list(build.SINGLE)[:6] == ["ext", "classes", "tiles", "yuv", "overlay", "tracks"]
-    assert build.SINGLE["tracks"][1]() == sorted(paths)
-    assert build.SINGLE["tracks"][0] == os.path.join(ROOT, "countr_amd", "libcountr_hip_tracks.so")
-    assert os.path.samefile(build.SINGLE["tracks"][2], _lib.TRACKS_HEADER)
-
-
-def test_version_limits_binding_and_errors():
     snapshot = lambda: (dict(_lib.CONSTS), dict(_lib.STRUCTS), dict(_lib.PROTOS), _lib.exported_symbols(),
                         dict(_lib.EXT_CONSTS), dict(_lib.EXT_STRUCTS), dict(_lib.EXT_PROTOS), _lib.ext_exported_symbols(),
                         dict(_lib.CLASSES_CONSTS), dict(_lib.CLASSES_STRUCTS), dict(_lib.CLASSES_PROTOS), _lib.classes_exported_symbols(),

@@ -1,58 +1,21 @@
 """CPU: include/countr_hip_yuv.h is the one statement of the yuv library's C ABI, as the four older headers are of theirs.
-countr_amd/_lib.py reads the binding from it and libcountr_hip_yuv.so exports exactly it; checked against the library's own dynamic
-symbols and literal pins.  Every refusal runs on the host: a refused call launches nothing."""
+countr_amd/_lib.py reads the binding from it and libcountr_hip_yuv.so exports exactly it; pinned here by literals (the checks against
+the C compiler and the library's dynamic symbols are in tests/test_libraries_cpu.py, once per tag).  Every refusal runs on the host: a
+refused call launches nothing."""
 import ctypes as C
-import glob
-import os
-import re
-import subprocess
 
-from countr_amd import _lib
+from countr_amd import _lib, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")      # the compiler countr_amd/build.py uses
 NAMES = ("ABI_VERSION", "MAX_FRAMES", "MAX_SIDE", "NV12", "NV21", "I420", "P010", "BT601", "BT709", "LIMITED", "FULL", "NEAREST", "LINEAR")
 
 
-def test_header_has_no_structs_and_compiles_as_c(tmp_path):
-    assert list(_lib.YUV_STRUCTS) == []            # plain pointers and sizes only: there is no layout to check against the compiler
-    src = tmp_path / "use.c"
-    src.write_text('#include <stdio.h>\n#include "countr_hip_yuv.h"\nint main(void) {\n  printf("%s\\n", %s);\n  return 0;\n}\n'
-                   % (" ".join(["%d"] * len(NAMES)), ", ".join("COUNTR_YUV_" + n for n in NAMES)))
-    subprocess.check_call([HIPCC, "-x", "c", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "use")])
-    got = subprocess.check_output([str(tmp_path / "use")], text=True).split()
-    assert [int(v) for v in got] == [_lib.YUV_CONSTS["COUNTR_YUV_" + n] for n in NAMES]
+def test_version_limits_binding_and_errors():
+    # the literal pins of the header's names (what holds of every library by rule is in test_libraries_cpu.py)
+    assert list(_lib.YUV_STRUCTS) == []            # plain pointers and sizes only
     assert list(_lib.YUV_CONSTS) == ["COUNTR_YUV_" + n for n in NAMES]
-
-
-def test_library_exports_the_header_and_nothing_else():
-    readelf = subprocess.check_output([HIPCC, "-print-prog-name=llvm-readelf"], text=True).strip()
-    rows = [line.split() for line in subprocess.check_output([readelf, "--dyn-syms", "-W", _lib.YUV_LIB_PATH], text=True).splitlines()]
-    defined = [r[7].split("@")[0] for r in rows if len(r) == 8 and r[0][:-1].isdigit() and r[6] != "UND"]
-    assert sorted(n for n in defined if n.startswith("countr_")) == _lib.yuv_exported_symbols()
     assert _lib.yuv_exported_symbols() == ["countr_yuv_last_error", "countr_yuv_to_rgb", "countr_yuv_version"]
-    assert [n for n in defined if not n.startswith(("countr_", "__hip_cuid_"))] == []
-
-
-def test_every_prototype_is_defined_extern_c_in_the_sources():
-    paths = glob.glob(os.path.join(ROOT, "countr_amd", "csrc_yuv", "*.hip"))
-    src = "".join(open(p).read() for p in paths)
-    for name in _lib.yuv_exported_symbols():
-        assert re.search(r'extern "C" [\w ]+\*? ?%s\(' % name, src), name
-    assert re.search(r"countr_yuv_version\(void\) \{ return COUNTR_YUV_ABI_VERSION; \}", src)
-    # the library's sources stay outside the globs the other libraries are built from
-    others = [os.path.basename(p) for d in ("csrc", "csrc_ext", "csrc_classes", "csrc_tiles")
-              for p in glob.glob(os.path.join(ROOT, "countr_amd", d, "*.hip"))]
-    assert paths and not set(os.path.basename(p) for p in paths) & set(others)
-    from countr_amd import build
     # the one table of the side libraries, in the order they were added, up to this one
     assert list(build.SINGLE)[:4] == ["ext", "classes", "tiles", "yuv"]
-    assert build.SINGLE["yuv"][1]() == sorted(paths)
-    assert build.SINGLE["yuv"][0] == os.path.join(ROOT, "countr_amd", "libcountr_hip_yuv.so")
-    assert os.path.samefile(build.SINGLE["yuv"][2], _lib.YUV_HEADER)
-
-
-def test_version_limits_binding_and_errors():
     snapshot = lambda: (dict(_lib.CONSTS), dict(_lib.STRUCTS), dict(_lib.PROTOS), _lib.exported_symbols(),
                         dict(_lib.EXT_CONSTS), dict(_lib.EXT_STRUCTS), dict(_lib.EXT_PROTOS), _lib.ext_exported_symbols(),
                         dict(_lib.CLASSES_CONSTS), dict(_lib.CLASSES_STRUCTS), dict(_lib.CLASSES_PROTOS), _lib.classes_exported_symbols(),
