@@ -159,6 +159,40 @@ template <int NW> __device__ __forceinline__ float block_sum(float v, float* sm)
   return r;
 }
 
+// The integer forms, for the counting kernels off the hot path (plain shuffles): sums and prefixes of integers do not depend on an order.
+__device__ __forceinline__ int wave_sum_i(int v) {      // (all 64 lanes active)
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_scan_incl_i(int v) {      // inclusive prefix over the 64 lanes (all active)
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int u = __shfl_up(v, d, 64);
+    if (lane >= d) v += u;
+  }
+  return v;
+}
+// exclusive prefix of v over the threads of a block of NW waves in thread order, and the block's total; `sm` holds NW ints.  Every thread
+// calls it.
+template <int NW> __device__ __forceinline__ int block_scan_i(int v, int* sm, int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int inc = wave_scan_incl_i(v);
+  __syncthreads();                               // (sm may still be read from the scan before)
+  if (lane == 63) sm[wave] = inc;
+  __syncthreads();
+  int pre = 0;
+  total = 0;
+#pragma unroll
+  for (int k = 0; k < NW; ++k) {
+    const int c = sm[k];
+    if (k < wave) pre += c;
+    total += c;
+  }
+  return pre + inc - v;
+}
+
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_erf_grad(float x) {
   const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752f));
@@ -244,6 +278,7 @@ static inline int countr_blocks_for(int64_t threads, int cap) {
   return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 __device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
+__device__ __forceinline__ uint32_t clamp255(int v) { return (uint32_t)min(max(v, 0), 255); }
 
 // K order of the 3x3 convolutions' implicit GEMMs in linear.hip / gemm256.hip (K = 9 taps x Cin, k-tile = 64 channels of one tap):
 // channel-chunk-major -- k-tile t is tap t % 9 of chunk t / 9, so nine consecutive k-tiles read the SAME 128-byte pieces of the

@@ -107,25 +107,9 @@ __global__ __launch_bounds__(256) void peaks_detect_kernel(const PeakArgs a, con
   }
 }
 
-// exclusive scan of one int per thread over the block's 256 threads; *total = the sum.  Every thread calls it.
-__device__ __forceinline__ int block_scan(int v, int* sm, int* total) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  sm[t] = v;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const int add = t >= d ? sm[t - d] : 0;
-    __syncthreads();
-    sm[t] += add;
-    __syncthreads();
-  }
-  *total = sm[255];
-  return sm[t] - v;
-}
-
 __global__ __launch_bounds__(256) void peaks_write_kernel(const PeakArgs a, const unsigned long long* __restrict__ masks, int* __restrict__ totals,
                                                           float* __restrict__ raw, int r, int cap) {
-  __shared__ int sm[256];
+  __shared__ int sm[4];                                  // the scans' wave totals
   __shared__ int list[LIST];
   const int i = blockIdx.y, b = blockIdx.x;
   const int h = a.h[i], w = a.w[i];
@@ -139,12 +123,12 @@ __global__ __launch_bounds__(256) void peaks_write_kernel(const PeakArgs a, cons
   int before = 0;
   for (int s = threadIdx.x; s < s0; s += 256) before += __popcll(mk[s]);
   int base;
-  block_scan(before, sm, &base);                         // peaks in front of this block's rows
+  block_scan_i<4>(before, sm, base);                     // peaks in front of this block's rows
   for (int c0 = s0; c0 < s1; c0 += 256) {
     const int s = c0 + threadIdx.x;
     const unsigned long long mask = s < s1 ? mk[s] : 0ull;
     int chunk;
-    const int first = block_scan(__popcll(mask), sm, &chunk);
+    const int first = block_scan_i<4>(__popcll(mask), sm, chunk);
     const int sy = s / tiles_x, sx = (s - sy * tiles_x) * TILE_W;
     for (int p0 = 0; p0 < chunk && base + p0 < cap; p0 += LIST) {
       unsigned long long bits = mask;

@@ -93,15 +93,6 @@ __global__ __launch_bounds__(THREADS) void cam_texture_kernel(const EstimateArgs
   }
 }
 
-__device__ __forceinline__ int wave_scan_int(int v, int lane) {      // inclusive, over the 64 lanes
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int u = __shfl_up(v, d);
-    if (lane >= d) v += u;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(THREADS) void cam_record_kernel(const EstimateArgs a, const unsigned char* __restrict__ flags,
                                                              const int* __restrict__ hist, int* __restrict__ records, int cells, int tol,
                                                              int min_voters) {
@@ -119,7 +110,7 @@ __global__ __launch_bounds__(THREADS) void cam_record_kernel(const EstimateArgs 
       c[q] = b < BINS ? H[axis * BINS + b] : 0;
       mine += c[q];
     }
-    int inc = wave_scan_int(mine, lane);
+    int inc = wave_scan_incl_i(mine);
     if (lane == 63) s_wave[wave] = inc;
     __syncthreads();
     int total = 0;
@@ -148,8 +139,7 @@ __global__ __launch_bounds__(THREADS) void cam_record_kernel(const EstimateArgs 
     const int ox = lo16(v), oy = hi16(v);
     if (fl[k] && in_range(ox, oy) && absdiff(ox, gx) <= tol && absdiff(oy, gy) <= tol) ++in;
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) in += __shfl_xor(in, d);
+  in = wave_sum_i(in);
   if (lane == 0) s_in[wave] = in;
   __syncthreads();
   if (tid == 0) {

@@ -37,12 +37,6 @@ struct Sums {
   int area[NC];
 };
 
-__device__ __forceinline__ int wave_sum_i(int v) {      // (all 64 lanes active)
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 // the header's rule for one pixel, one operation per statement and no contraction: the product is rounded to fp32 before it is
 // compared or added.  Every index below is a constant after unrolling: the arrays live in registers.
 #pragma clang fp contract(off)

@@ -39,12 +39,6 @@ struct RegionArgs {
   int nv[MAX_REG], gy[MAX_REG], gx[MAX_REG], data[MAX_REG], slot[MAX_REG];
 };
 
-__device__ __forceinline__ int wave_sum_i(int v) {      // (all 64 lanes active)
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 // the header's two rules, fp64, one operation per statement and no contraction
 #pragma clang fp contract(off)
 __device__ __forceinline__ double place(double a, double c, double b) {

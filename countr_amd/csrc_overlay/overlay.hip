@@ -267,8 +267,6 @@ __global__ __launch_bounds__(64) void point_kernel(const OvArgs a) {
   }
 }
 
-__device__ __forceinline__ uint32_t clamp255(int v) { return (uint32_t)min(max(v, 0), 255); }
-
 template <int FMT>
 __global__ __launch_bounds__(BX * BY) void yuv_kernel(const OvArgs a) {
   const int x0 = (blockIdx.x * BX + threadIdx.x) * PX;

@@ -9,9 +9,9 @@
 //                           wave also writes its prediction p = (fl(x + vx), fl(y + vy)) to the workspace; a detection's wave forms the
 //                           predictions it scans from the state (the same two additions, so the same bits).
 //   2 tracks_step_kernel    a block of 1024 threads per tracker.
-//       the rounds          csrc/match.hip's exact rounds of locally dominant pairs with pred = the detections and gt = the predictions:
-//                           bests and the two "still free" masks in LDS; the loop ends with the first round that matches nothing, so no
-//                           round count is assumed.  The matching stays in LDS (det -> track, track -> det).
+//       the rounds          the rounds of csrc/greedy_match.hpp -- the code csrc/match.hip runs -- with side a = the detections and side b =
+//                           the predictions: bests and the two "still free" masks in LDS; the loop ends with the first round that matches
+//                           nothing, so no round count is assumed.  The matching stays in LDS (det -> track, track -> det).
 //       the update          a thread holds four consecutive tracks in registers (16-byte loads): a matched track runs the crossing test
 //                           in fp64 (__dsub_rn / __dmul_rn), writes ids[i] / events[i] of its detection and takes the detection; an
 //                           unmatched one coasts.  After a barrier -- every old value is in a register -- an integer scan of the
@@ -25,14 +25,15 @@
 #include <stdio.h>
 #include <string.h>
 #include "../csrc/common.hpp"
+#include "../csrc/greedy_match.hpp"
 #include "../csrc/host_api.hpp"
 #include "../../include/countr_hip_tracks.h"
 
 namespace {
 
+using namespace countr_greedy;
 constexpr int MAXS = COUNTR_TRACKS_MAX_STREAMS, MAXT = COUNTR_TRACKS_MAX_TRACKS, MAXP = COUNTR_TRACKS_MAX_POINTS;
 constexpr int MAXL = COUNTR_TRACKS_MAX_LINES, HEAD = COUNTR_TRACKS_HEAD_INTS, SUMMARY = COUNTR_TRACKS_SUMMARY_INTS;
-constexpr int NONE = 0xFFFF;                     // "no eligible free partner" (an index is < 4096)
 constexpr int INIT_BLOCKS = 256;                 // blocks per tracker of the first launch (4 waves each): one tracker alone fills every CU
 constexpr int STEP_THREADS = 1024, STEP_WAVES = STEP_THREADS / 64;
 constexpr int PER = 4;                           // tracks / detections of a thread in the update: 4 * 1024 = 4096
@@ -67,50 +68,10 @@ struct State {
 
 __device__ __forceinline__ int live_of(const int* head) { const int T = head[0]; return T < 0 ? 0 : (T > MAXT ? MAXT : T); }
 
-// d2 of detection d and prediction p: always d - p, so both sides' scans compute the same bits for a pair
-__device__ __forceinline__ float pair_d2(const float2 d, const float2 p) {
-  const float dx = __fsub_rn(d.x, p.x), dy = __fsub_rn(d.y, p.y);
-  return __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
-}
-
-__device__ __forceinline__ unsigned mask_word(const unsigned* m, int w) {      // (other threads may clear bits of the word meanwhile)
-  return __hip_atomic_load(m + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ bool mask_bit(const unsigned* m, int k) { return (mask_word(m, k >> 5) >> (k & 31)) & 1u; }
-__device__ __forceinline__ void mask_clear(unsigned* m, int k) { atomicAnd(m + (k >> 5), ~(1u << (k & 31))); }
-
-struct FromArray {                               // candidates read from an array of points
-  const float2* p;
-  __device__ __forceinline__ float2 at(int k) const { return p[k]; }
-};
 struct FromState {                               // candidates are the tracks' predictions, formed from the state
   const State* s;
   __device__ __forceinline__ float2 at(int k) const { return s->predict(k); }
 };
-
-// The index of q's smallest key (d2, index) among the eligible (and, MASKED, still free) candidates, or NONE.  Q_IS_DET: q is a
-// detection and the candidates are predictions; otherwise the reverse.  The whole wave calls it with the same arguments; every lane gets
-// the result.  A lane walks its candidates in ascending index order and replaces its best only by a strictly smaller d2, so it holds the
-// smallest index of its smallest d2; two butterflies then take the smallest d2 of the wave and the smallest index that has it (an index
-// is exact as a float).  A NaN d2 fails `<= md2`: such a pair is never eligible.
-template <bool MASKED, bool Q_IS_DET, class Src>
-__device__ __forceinline__ int wave_best(const float2 q, const Src src, int n, const unsigned* free, float md2, int lane) {
-  float best = 0.f;
-  int at = NONE;
-  for (int k0 = 0; k0 < n; k0 += 64) {
-    if (MASKED && (mask_word(free, k0 >> 5) | mask_word(free, (k0 >> 5) + 1)) == 0u) continue;      // (wave-uniform: k0 is)
-    const int k = k0 + lane;
-    if (k < n && (!MASKED || mask_bit(free, k))) {
-      const float2 c = src.at(k);
-      const float d = Q_IS_DET ? pair_d2(q, c) : pair_d2(c, q);
-      if (d <= md2 && (at == NONE || d < best)) { best = d; at = k; }
-    }
-  }
-  const float ninf = -__builtin_inff();
-  const float low = -wave_max(at != NONE ? -best : ninf);
-  const float idx = wave_max((at != NONE && best == low) ? -(float)at : ninf);
-  return idx == ninf ? NONE : (int)(-idx);
-}
 
 __global__ __launch_bounds__(256) void tracks_init_kernel(const TrArgs a, unsigned char* __restrict__ ws) {
   const int s = blockIdx.y;
@@ -124,37 +85,14 @@ __global__ __launch_bounds__(256) void tracks_init_kernel(const TrArgs a, unsign
   unsigned short* best_d = reinterpret_cast<unsigned short*>(w + WS_BEST_D);
   for (int q = blockIdx.x * 4 + (threadIdx.x >> 6); q < N + T; q += INIT_BLOCKS * 4) {      // (wave-uniform)
     if (q < N) {
-      const int j = wave_best<false, true>(det[q], FromState{&st}, T, nullptr, a.md2[s], lane);
+      const int j = wave_best<false>(det[q], FromState{&st}, T, nullptr, a.md2[s], lane);
       if (lane == 0) best_d[q] = (unsigned short)j;
     } else {
       const float2 p = st.predict(q - N);
-      const int i = wave_best<false, false>(p, FromArray{det}, N, nullptr, a.md2[s], lane);
+      const int i = wave_best<false>(p, FromArray{det}, N, nullptr, a.md2[s], lane);
       if (lane == 0) { best_t[q - N] = (unsigned short)i; pred[q - N] = p; }
     }
   }
-}
-
-// exclusive prefix of v over the block's threads in thread order, and the block's total; `sm` holds STEP_WAVES ints
-__device__ __forceinline__ int block_scan(int v, int* sm, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int n = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += n;
-  }
-  __syncthreads();                               // (sm may still be read from the scan before)
-  if (lane == 63) sm[wave] = inc;
-  __syncthreads();
-  int pre = 0;
-  total = 0;
-#pragma unroll
-  for (int k = 0; k < STEP_WAVES; ++k) {
-    const int c = sm[k];
-    if (k < wave) pre += c;
-    total += c;
-  }
-  return pre + inc - v;
 }
 
 // side(a, b, p) of the header: fp64 from the fp32 values, in the written order, no fma
@@ -171,7 +109,6 @@ __global__ __launch_bounds__(STEP_THREADS) void tracks_step_kernel(const TrArgs 
   __shared__ float4 s_lines[MAXL];
   __shared__ int s_counts[2 * MAXL], s_scan[STEP_WAVES], s_conf, s_matched;
   const int s = blockIdx.x, t = threadIdx.x;
-  const int lane = t & 63, wave = t >> 6;
   const State st(a.state[s]);
   const int N = a.N[s], L = a.L[s], T = live_of(st.head);
   const int started = st.head[1];
@@ -191,56 +128,11 @@ __global__ __launch_bounds__(STEP_THREADS) void tracks_step_kernel(const TrArgs 
   if (t < 2 * MAXL) s_counts[t] = 0;
   if (t == 0) { s_conf = 0; s_matched = 0; }
   __syncthreads();
-  // free = has an eligible partner at all: a point without one never gets one, and nobody's best points at it
-  for (int k = t; k < MAXP / 32 + 2; k += STEP_THREADS) {
-    unsigned md = 0u, mt = 0u;
-    for (int b = 0; b < 32; ++b) {
-      const int q = k * 32 + b;
-      if (q < N && best_d[q] != NONE) md |= 1u << b;
-      if (q < T && best_t[q] != NONE) mt |= 1u << b;
-    }
-    free_d[k] = md; free_t[k] = mt;
-  }
-  __syncthreads();
-  int mine = 0;
-  for (;;) {
-    // (A) mutual bests.  Only the thread of detection i clears bit i and reads it; best_d / best_t do not change in this phase.
-    int hit = 0;
-    for (int i = t; i < N; i += STEP_THREADS) {
-      if (!mask_bit(free_d, i)) continue;
-      const int j = best_d[i];
-      if (j == NONE || best_t[j] != i) continue;
-      m_d[i] = (unsigned short)j;
-      m_t[j] = (unsigned short)i;
-      mask_clear(free_d, i);
-      mask_clear(free_t, j);
-      hit = 1; ++mine;
-    }
-    if (!__syncthreads_or(hit)) break;             // every round that goes on has cleared a bit of free_d: at most N + 1 rounds
-    // (B) a free point whose best was taken scans the free points of the other side again; one that finds none leaves for good.  A
-    // point that leaves during this phase is eligible for no free point, so whether a concurrent scan still sees its bit changes nothing.
-    for (int base = wave * 64; base < N; base += STEP_WAVES * 64) {
-      const int i = base + lane;
-      bool stale = false;
-      if (i < N && mask_bit(free_d, i)) { const int j = best_d[i]; stale = j != NONE && !mask_bit(free_t, j); }
-      for (unsigned long long m = __ballot(stale); m; m &= m - 1) {
-        const int q = base + __ffsll((long long)m) - 1;
-        const int j = wave_best<true, true>(det[q], FromArray{pred}, T, free_t, md2, lane);
-        if (lane == 0) { best_d[q] = (unsigned short)j; if (j == NONE) mask_clear(free_d, q); }
-      }
-    }
-    for (int base = wave * 64; base < T; base += STEP_WAVES * 64) {
-      const int j = base + lane;
-      bool stale = false;
-      if (j < T && mask_bit(free_t, j)) { const int i = best_t[j]; stale = i != NONE && !mask_bit(free_d, i); }
-      for (unsigned long long m = __ballot(stale); m; m &= m - 1) {
-        const int q = base + __ffsll((long long)m) - 1;
-        const int i = wave_best<true, false>(pred[q], FromArray{det}, N, free_d, md2, lane);
-        if (lane == 0) { best_t[q] = (unsigned short)i; if (i == NONE) mask_clear(free_t, q); }
-      }
-    }
-    __syncthreads();
-  }
+  greedy_free_masks<STEP_THREADS>(best_d, N, best_t, T, free_d, free_t, MAXP / 32 + 2);
+  const int mine = greedy_rounds<STEP_THREADS>(FromArray{det}, N, FromArray{pred}, T, best_d, best_t, free_d, free_t, md2, [&](int i, int j) {
+    m_d[i] = (unsigned short)j;
+    m_t[j] = (unsigned short)i;
+  });
   if (mine) atomicAdd(&s_matched, mine);
 
   // ---- the update: tracks PER * t .. PER * t + PER - 1 of this thread, in registers
@@ -301,7 +193,7 @@ __global__ __launch_bounds__(STEP_THREADS) void tracks_step_kernel(const TrArgs 
     nkeep += keep[k];
   }
   int S;                                           // the survivors
-  int pos = block_scan(nkeep, s_scan, S);          // (its first barrier: every old value of the state is in a register from here on)
+  int pos = block_scan_i<STEP_WAVES>(nkeep, s_scan, S);      // (its first barrier: every old value of the state is in a register from here on)
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     if (!keep[k]) continue;
@@ -324,7 +216,7 @@ __global__ __launch_bounds__(STEP_THREADS) void tracks_step_kernel(const TrArgs 
     ncand += cand[k];
   }
   int U;                                           // the unmatched finite detections
-  int r = block_scan(ncand, s_scan, U);
+  int r = block_scan_i<STEP_WAVES>(ncand, s_scan, U);
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     if (!cand[k]) continue;

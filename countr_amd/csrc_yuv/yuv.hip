@@ -111,8 +111,6 @@ __device__ __forceinline__ void load_c(const uint8_t* __restrict__ r0, const uin
   if (ninth) sample_c<FMT>(r0, r1, min(i0 + NC, Wc - 1), U[NC], V[NC]);
 }
 
-__device__ __forceinline__ uint32_t clamp255(int v) { return (uint32_t)min(max(v, 0), 255); }
-
 // one luma row of the thread: its 16 pixels from Y and the row's chroma (U, V: samples under NEAREST, the sums s[] of the rule under
 // LINEAR), packed as 48 bytes and stored
 template <int FMT, bool LINEAR>

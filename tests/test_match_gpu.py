@@ -55,6 +55,13 @@ def case(name):
     elif name == "nan_and_far":
         pred, gt, md = f(40, 30, 30), f(50, 30, 30), 3.0
         pred[3, 0], pred[11, 1], gt[7, 1], gt[20, 0] = np.nan, np.inf, np.nan, 1e30
+    elif name.startswith("edge_"):
+        # integer lattice, sizes that straddle the 64-candidate chunk and the 32-bit mask word on both sides: thousands of tied
+        # distances, so the masked rescan and the (d2, i, j) tie-break run at every boundary (4 to 9 rounds in match_rounds_host)
+        P, G = map(int, name.split("_")[1:])
+        edge = np.random.RandomState(1000 * P + G)
+        pred = edge.randint(0, 12, (P, 2)).astype(np.float32)
+        gt, md = edge.randint(0, 12, (G, 2)).astype(np.float32), 4.0
     elif name.startswith("mixed_"):
         k = int(name.split("_")[1])
         P, G = [(0, 0), (1, 0), (0, 3), (70, 65), (129, 200), (33, 31), (5, 500), (260, 9)][k % 8]
@@ -115,7 +122,7 @@ def compare(names, match, d2, counts, offsets):
 
 
 SHAPES = ["one", "no_pred", "no_gt", "counter_example", "uniform_17_33", "lattice_64_64", "field_300_257", "all_pairs_1024_1000",
-          "ladder", "nan_and_far"]
+          "ladder", "nan_and_far", "edge_63_65", "edge_64_64", "edge_65_63", "edge_127_129", "edge_128_128", "edge_129_127"]
 
 
 @pytest.mark.parametrize("name", SHAPES)
