@@ -182,8 +182,8 @@ def localize_group(args, dists, grp, res):
     -> per image (P, G, rows of localization_metrics, labels)."""
     from countr_amd import frames, match
     # sizes = the evaluated image's own: frame_points is then the identity, and points and dots share one coordinate system
-    pts = frames.locate_maps([(r[0], r[1]) for r in res], [(int(r[1].shape[1]), frames.NEW_H) for r in res], [r[2] for r in res],
-                             radius=args.points_radius, rel_threshold=args.points_rel_threshold, keep=args.points_keep)
+    pts = frames.locate_maps(res, [(int(r[1].shape[1]), frames.NEW_H) for r in res], radius=args.points_radius,
+                             rel_threshold=args.points_rel_threshold, keep=args.points_keep)
     use, sets = [], []
     for (_name, _img, _boxes, pos, _gt, _map, dots), (xy, _score, _total) in zip(grp, pts):
         box = box_distance(pos, args.localize_box_scale)

@@ -249,49 +249,56 @@ def frame_prep(device):
     return _owned.instance(FramePrep, device)
 
 
+def _sizes(frames):
+    """(W, H) of every frame."""
+    return [(int(f.shape[1]), int(f.shape[0])) for f in frames]
+
+
+def _frame_exemplars(im, frame, boxes, i, new_h=NEW_H):
+    """Frame i's boxes (boxes: None or one list per frame) cut from its prepared image im -> exemplars()' (crops, rects), or (an empty
+    [1, 0] tensor, None) for a frame without boxes.  frame: the original frame, for its size."""
+    if boxes is None or boxes[i] is None or len(boxes[i]) == 0:
+        return torch.zeros(1, 0, device=im.device), None
+    return exemplars(im, boxes[i], int(frame.shape[1]), int(frame.shape[0]), new_h)
+
+
 def prepare_items(device, frames, boxes=None, prep=None, new_h=NEW_H):
     """Raw frames (+ per-frame lists of (x1, y1, x2, y2) boxes in original pixels, or None) -> the items inference.count_images takes:
     [(image [1, 3, new_h, new_W], exemplars [1, S, 3, 64, 64] or an empty [1, 0] tensor, rects or None), ...], all made on the device."""
     prep = prep or frame_prep(device)
     images = prep.prepare(frames, new_h)
-    items = []
-    for i, im in enumerate(images):
-        bx = boxes[i] if boxes is not None else None
-        if bx is not None and len(bx) > 0:
-            H, W = int(frames[i].shape[0]), int(frames[i].shape[1])
-            ex, rects = exemplars(im, bx, W, H, new_h)
-            items.append((im, ex, rects))
-        else:
-            items.append((im, torch.zeros(1, 0, device=im.device), None))
-    return items
+    return [(im,) + _frame_exemplars(im, frames[i], boxes, i, new_h) for i, im in enumerate(images)]
 
 
 @torch.no_grad()
-def count_items(model, items, normalization=True, max_s_cnt=1, max_batch=32):
-    """inference.count_images over device-prepared items, with the 3 x 3 split of frames with tiny exemplars (demo.py:79-99) cut and
-    upscaled by countr_crop_resize_f32.  The reference's quirks stay: the count of a split frame is the sum over its nine maps and its
-    normalisation reads the LAST crop's map."""
+def count_items_crops(model, items, normalization=True, max_s_cnt=1, max_batch=32):
+    """count_items, which also hands back the nine maps of a frame that took the 3 x 3 path: [(count, density map, crops or None), ...]."""
     res = [None] * len(items)
     rest = []
     for idx, (im, ex, rects) in enumerate(items):
         if rects is not None and inference._small_exemplars(rects) >= max_s_cnt:
             dms = inference.density_maps(model, split_crops(im), [ex] * 9, ex.shape[1], max_batch)
-            pred = sum((d.sum() / 60).item() for d in dms)
-            res[idx] = (inference._normalise(pred, dms[-1], rects, normalization), dms[-1])
+            res[idx] = inference.split_count(dms, rects, normalization) + (dms,)
         else:
             rest.append(idx)
     if rest:
-        for idx, r in zip(rest, inference.count_images(model, [items[i] for i in rest], normalization, max_s_cnt, max_batch)):
+        for idx, r in zip(rest, inference.count_images(model, [items[i] for i in rest], normalization, max_s_cnt, max_batch, return_crops=True)):
             res[idx] = r
     return res
+
+
+def count_items(model, items, normalization=True, max_s_cnt=1, max_batch=32):
+    """inference.count_images over device-prepared items, with the 3 x 3 split of frames with tiny exemplars (demo.py:79-99) cut and
+    upscaled by countr_crop_resize_f32.  The reference's quirks stay: the count of a split frame is the sum over its nine maps and its
+    normalisation reads the LAST crop's map."""
+    return [r[:2] for r in count_items_crops(model, items, normalization, max_s_cnt, max_batch)]
 
 
 def frame_zooms(frames, boxes, zoom, zoom_max=3, max_s_cnt=1):
     """The zoom of every frame: `zoom` itself, or under zoom="auto" tiles.auto_zoom of the frame's boxes."""
     if zoom != "auto":
         return [int(zoom)] * len(frames)
-    return [tiles_.auto_zoom(boxes[i] if boxes is not None else None, int(f.shape[1]), int(f.shape[0]), max_s_cnt, zoom_max)
-            for i, f in enumerate(frames)]
+    return [tiles_.auto_zoom(boxes[i] if boxes is not None else None, W, H, max_s_cnt, zoom_max) for i, (W, H) in enumerate(_sizes(frames))]
 
 
 @torch.no_grad()
@@ -305,19 +312,25 @@ def count_frames_zoomed(model, frames, boxes, ks, normalization=True, max_s_cnt=
     ones = [i for i, k in enumerate(ks) if k == 1]
     if ones:
         items = prepare_items(device, [frames[i] for i in ones], [boxes[i] for i in ones] if boxes is not None else None)
-        got = (count_items_crops if crops else count_items)(model, items, normalization, max_s_cnt, max_batch)
-        for i, r in zip(ones, got):
+        for i, r in zip(ones, count_items_crops(model, items, normalization, max_s_cnt, max_batch)):
             res[i] = r
     for k in sorted(set(ks) - {1}):
         sel = [i for i, kk in enumerate(ks) if kk == k]
         items = prepare_items(device, [frames[i] for i in sel], [boxes[i] for i in sel] if boxes is not None else None, new_h=NEW_H * k)
         for i, (im, ex, rects) in zip(sel, items):
-            r = tiles_.count_zoomed(model, im, ex, rects, normalization, max_batch, band_stride)
-            res[i] = r + (None,) if crops else r
-    return res
+            res[i] = tiles_.count_zoomed(model, im, ex, rects, normalization, max_batch, band_stride) + (None,)
+    return res if crops else [r[:2] for r in res]
 
 
-@torch.no_grad()
+def _count_at_zoom(model, frames, boxes, zoom, zoom_max, band_stride, normalization, max_s_cnt, max_batch):
+    """The counting of count_frames, locate_frames and annotate_frames behind their check_zoom: ([(count, density map, crops or None),
+    ...], the height every frame was resized to).  zoom=1 is count_frames_zoomed with every k = 1: one count_items_crops call over all
+    the frames."""
+    ks = frame_zooms(frames, boxes, zoom, zoom_max, max_s_cnt)
+    res = count_frames_zoomed(model, frames, boxes, ks, normalization, max_s_cnt, max_batch, band_stride, crops=True)
+    return res, [NEW_H * k for k in ks]
+
+
 def count_frames(model, frames, boxes=None, normalization=True, max_s_cnt=1, max_batch=32, *, zoom=1, zoom_max=3, band_stride=128):
     """Raw frames in, [(count, density map [384, new_W]), ...] out.  frames: uint8 [H, W, 3] each, on the host or on the model's device;
     boxes: None (zero-shot) or one list of (x1, y1, x2, y2) exemplar boxes per frame, in pixels of the original frame (an empty list =
@@ -330,11 +343,7 @@ def count_frames(model, frames, boxes=None, normalization=True, max_s_cnt=1, max
     frame the smallest k in 1..zoom_max at which fewer than max_s_cnt of its exemplars are under 10 px (zoom_max if none, 1 without
     boxes); its frames at 1 are counted as count_frames counts just them.  zoom=1 is the path above, untouched."""
     tiles_.check_zoom(zoom, zoom_max, band_stride)
-    if zoom != 1:
-        ks = frame_zooms(frames, boxes, zoom, zoom_max, max_s_cnt)
-        return count_frames_zoomed(model, frames, boxes, ks, normalization, max_s_cnt, max_batch, band_stride)
-    device = next(model.parameters()).device
-    return count_items(model, prepare_items(device, frames, boxes), normalization, max_s_cnt, max_batch)
+    return [r[:2] for r in _count_at_zoom(model, frames, boxes, zoom, zoom_max, band_stride, normalization, max_s_cnt, max_batch)[0]]
 
 
 ClassCounts = collections.namedtuple("ClassCounts", "names counts maps labels won total area")
@@ -367,14 +376,9 @@ def count_classes(model, frames, classes, *, normalization=True, max_s_cnt=1, ma
     widths = [int(im.shape[-1]) for im in images]
     ex, rects, split, groups = [], [], [], collections.OrderedDict()
     for c, name in enumerate(names):
-        boxes = classes[name]
         ex.append([]); rects.append([]); split.append([])
         for f, im in enumerate(images):
-            bx = boxes[f] if boxes is not None else None
-            if bx is not None and len(bx) > 0:
-                e, r = exemplars(im, bx, int(frames[f].shape[1]), int(frames[f].shape[0]))
-            else:
-                e, r = torch.zeros(1, 0, device=im.device), None
+            e, r = _frame_exemplars(im, frames[f], classes[name], f)
             ex[c].append(e); rects[c].append(r)
             split[c].append(r is not None and inference._small_exemplars(r) >= max_s_cnt)
         shots = [int(e.shape[1]) if e.nelement() > 0 else 0 for e in ex[c]]
@@ -396,14 +400,11 @@ def count_classes(model, frames, classes, *, normalization=True, max_s_cnt=1, ma
     for f in range(F_):
         for c in range(len(names)):
             if split[c][f]:
-                nine = [dm[(c, (f, k))] for k in range(9)]
-                pred, m = sum((d.sum() / 60).item() for d in nine), nine[-1]      # (the reference normalises with the LAST crop's map)
+                counts[f][c], maps[f][c] = inference.split_count([dm[(c, (f, k))] for k in range(9)], rects[c][f], normalization)
             else:
-                m = dm[(c, (f, -1))]
+                maps[f][c] = m = dm[(c, (f, -1))]
                 sums[(f, c)] = tot = m.sum()
-                pred = (tot / 60).item()
-            counts[f][c] = inference._normalise(pred, m, rects[c][f], normalization)
-            maps[f][c] = m
+                counts[f][c] = inference._normalise((tot / 60).item(), m, rects[c][f], normalization)
     folded = {}
     if fold and names:
         plain = [f for f in range(F_) if not any(split[c][f] for c in range(len(names)))]
@@ -441,25 +442,36 @@ def _keep_count(P, count, keep):
     return min(P, max(0, int(np.floor(count + 0.5))))
 
 
+def _crops_of(results, crops):
+    """The crops per frame that locate_maps and region_maps read: the explicit list, or without one every (count, map, crops) entry's own
+    third field and None for a (count, map) entry."""
+    return crops or [r[2] if len(r) == 3 else None for r in results]
+
+
+def _fp32_maps(maps):
+    """The maps as the side libraries take them: fp32 and contiguous (a map that is both is used where it lies)."""
+    return [m if (m.dtype == torch.float32 and m.is_contiguous()) else m.float().contiguous() for m in maps]
+
+
 def locate_maps(results, sizes, crops=None, *, radius=4, threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all", new_h=NEW_H):
     """The points of counted frames: results [(count, density map [384, new_W] on the device), ...], sizes [(W, H), ...] of the original
     frames, crops per frame None or the nine maps of the 3 x 3 path -> [(points float32 [P, 2] as (x, y), score [P], total), ...].
     Every map of the call (the nine crop maps of a split frame included) goes through ONE PeakFinder.find.  new_h: the height the
-    frames were resized to, one number or one per frame (384 k for a frame counted at zoom k)."""
-    crops = crops or [None] * len(results)
+    frames were resized to, one number or one per frame (384 k for a frame counted at zoom k).  A results entry may also be (count,
+    density map, crops) as count_items_crops returns it: without crops= its third field is the frame's crops."""
+    crops = _crops_of(results, crops)
     heights = [int(new_h)] * len(results) if np.ndim(new_h) == 0 else [int(v) for v in new_h]
     if len(heights) != len(results):
         raise ValueError("locate_maps: new_h is one height, or one per frame")
     maps, first = [], []
-    for (_c, dm), cr in zip(results, crops):
+    for r, cr in zip(results, crops):
         first.append(len(maps))
-        maps.extend(cr if cr is not None else [dm])
+        maps.extend(cr if cr is not None else [r[1]])
     if not maps:
         return []
-    maps = [m if (m.dtype == torch.float32 and m.is_contiguous()) else m.float().contiguous() for m in maps]
-    found = peaks.peak_finder(maps[0].device).find(maps, radius, threshold, rel_threshold, max_points)
+    found = peaks.peak_finder(maps[0].device).find(_fp32_maps(maps), radius, threshold, rel_threshold, max_points)
     out = []
-    for (count, dm), (W, H), cr, f0, nh in zip(results, sizes, crops, first, heights):
+    for (count, dm, *_cr), (W, H), cr, f0, nh in zip(results, sizes, crops, first, heights):
         h, w = dm.shape
         if cr is None:
             pk = found[f0]
@@ -481,31 +493,12 @@ def locate_maps(results, sizes, crops=None, *, radius=4, threshold=0.0, rel_thre
 
 
 @torch.no_grad()
-def count_items_crops(model, items, normalization=True, max_s_cnt=1, max_batch=32):
-    """count_items, which also hands back the nine maps of a frame that took the 3 x 3 path: [(count, density map, crops or None), ...]."""
-    res = [None] * len(items)
-    rest = []
-    for idx, (im, ex, rects) in enumerate(items):
-        if rects is not None and inference._small_exemplars(rects) >= max_s_cnt:
-            dms = inference.density_maps(model, split_crops(im), [ex] * 9, ex.shape[1], max_batch)
-            pred = sum((d.sum() / 60).item() for d in dms)
-            res[idx] = (inference._normalise(pred, dms[-1], rects, normalization), dms[-1], dms)
-        else:
-            rest.append(idx)
-    if rest:
-        for idx, (c, dm) in zip(rest, inference.count_images(model, [items[i] for i in rest], normalization, max_s_cnt, max_batch)):
-            res[idx] = (c, dm, None)
-    return res
-
-
-@torch.no_grad()
 def locate_items(model, items, sizes, *, radius=4, threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all", normalization=True,
                  max_s_cnt=1, max_batch=32, crops=False):
     """count_items + locate_maps over device-prepared items: [(count, density map, points, score, total peaks), ...]; with crops=True
     each tuple ends with the nine maps of the 3 x 3 path, or None."""
     res = count_items_crops(model, items, normalization, max_s_cnt, max_batch)
-    pts = locate_maps([(c, dm) for c, dm, _cr in res], sizes, [cr for _c, _dm, cr in res], radius=radius, threshold=threshold,
-                      rel_threshold=rel_threshold, max_points=max_points, keep=keep)
+    pts = locate_maps(res, sizes, radius=radius, threshold=threshold, rel_threshold=rel_threshold, max_points=max_points, keep=keep)
     return [(c, dm, p, s, t) + ((cr,) if crops else ()) for (c, dm, cr), (p, s, t) in zip(res, pts)]
 
 
@@ -525,24 +518,18 @@ def locate_frames(model, frames, boxes=None, *, radius=4, threshold=0.0, rel_thr
     object is k times larger there, so a radius chosen at zoom 1 is k times tighter at zoom k.  regions together with a zoom other than
     1 raises ValueError."""
     tiles_.check_zoom(zoom, zoom_max, band_stride)
-    sizes = [(int(f.shape[1]), int(f.shape[0])) for f in frames]
-    if zoom != 1:
-        if regions is not None:
-            raise ValueError("locate_frames: regions are counted at zoom=1 only")
-        ks = frame_zooms(frames, boxes, zoom, zoom_max, max_s_cnt)
-        res = count_frames_zoomed(model, frames, boxes, ks, normalization, max_s_cnt, max_batch, band_stride, crops=True)
-        pts = locate_maps([(c, dm) for c, dm, _cr in res], sizes, [cr for _c, _dm, cr in res], radius=radius, threshold=threshold,
-                          rel_threshold=rel_threshold, max_points=max_points, keep=keep, new_h=[NEW_H * k for k in ks])
-        return [(c, dm, p, s) for (c, dm, _cr), (p, s, _t) in zip(res, pts)]
-    device = next(model.parameters()).device
-    items = prepare_items(device, frames, boxes)
-    res = locate_items(model, items, sizes, radius=radius, threshold=threshold, rel_threshold=rel_threshold, max_points=max_points, keep=keep,
-                       normalization=normalization, max_s_cnt=max_s_cnt, max_batch=max_batch, crops=regions is not None)
+    sizes = _sizes(frames)
+    if zoom != 1 and regions is not None:
+        raise ValueError("locate_frames: regions are counted at zoom=1 only")
+    res, heights = _count_at_zoom(model, frames, boxes, zoom, zoom_max, band_stride, normalization, max_s_cnt, max_batch)
+    pts = locate_maps(res, sizes, radius=radius, threshold=threshold, rel_threshold=rel_threshold, max_points=max_points, keep=keep,
+                      new_h=heights)
+    out = [(c, dm, p, s) for (c, dm, _cr), (p, s, _t) in zip(res, pts)]
     if regions is None:
-        return [r[:4] for r in res]
+        return out
     per = frame_regions(regions, sizes)
-    sums = region_maps([(r[0], r[1]) for r in res], sizes, [r[5] for r in res], per)
-    return [r[:4] + (counts, regions_.point_regions(r[2], rs)) for r, rs, (counts, _area) in zip(res, per, sums)]
+    sums = _region_sums(res, sizes, None, per)
+    return [r + (counts, regions_.point_regions(r[2], rs)) for r, rs, (counts, _area) in zip(out, per, sums)]
 
 
 def cut_exemplars(device, frame, boxes, prep=None):
@@ -561,6 +548,28 @@ def shared_exemplar_items(device, frames, crops, prep=None):
 
 def _is_shared(boxes):
     return isinstance(boxes, tuple) and len(boxes) == 2 and isinstance(boxes[0], (int, np.integer))
+
+
+def _clip_groups(who, device, frames, boxes, group):
+    """count_clip's and count_flow's walk over a clip: (items, sizes) of every consecutive group of `group` frames.  boxes: None, one
+    list per frame, or (k, boxes): the exemplar crops are then cut once, from frame k of the call, before the first group.  who: the
+    calling function's name, for the error texts."""
+    if int(group) != group or group < 1:
+        raise ValueError("%s: group is >= 1" % who)
+    frames = list(frames)
+    cut = None
+    if _is_shared(boxes):
+        k, bx = boxes
+        if not 0 <= int(k) < len(frames):
+            raise ValueError("%s: (k, boxes) names a frame of the call" % who)
+        cut = cut_exemplars(device, frames[int(k)], bx)
+    for g0 in range(0, len(frames), int(group)):
+        part = frames[g0:g0 + int(group)]
+        if cut is not None:
+            items = shared_exemplar_items(device, part, cut)
+        else:
+            items = prepare_items(device, part, boxes[g0:g0 + int(group)] if boxes is not None else None)
+        yield items, _sizes(part)
 
 
 @torch.no_grad()
@@ -589,8 +598,6 @@ def count_clip(model, frames, boxes=None, *, max_dist, lines=None, group=8, max_
     tracker=; camera and its settings are then the counter's own."""
     from . import flow as flow_, tracks as tracks_
     device = next(model.parameters()).device
-    if int(group) != group or group < 1:
-        raise ValueError("count_clip: group is >= 1")
     if tracker is None:
         tracker = tracks_.Tracker(device, max_dist=max_dist, max_missed=max_missed, min_hits=min_hits, beta=beta, lines=lines if lines is not None else ())
     elif tracker.streams != 1 or lines is not None:
@@ -600,21 +607,8 @@ def count_clip(model, frames, boxes=None, *, max_dist, lines=None, group=8, max_
     if counter is None and camera is not None:
         counter = flow_.FlowCounter(device, lines=(), search=search, interval=interval, min_gain=min_gain, camera=camera,
                                     min_texture=min_texture, cam_tol=cam_tol, min_voters=min_voters)
-    frames = list(frames)
-    cut = None
-    if _is_shared(boxes):
-        k, bx = boxes
-        if not 0 <= int(k) < len(frames):
-            raise ValueError("count_clip: (k, boxes) names a frame of the call")
-        cut = cut_exemplars(device, frames[int(k)], bx)
     out, last = [], None
-    for g0 in range(0, len(frames), int(group)):
-        part = frames[g0:g0 + int(group)]
-        sizes = [(int(f.shape[1]), int(f.shape[0])) for f in part]
-        if cut is not None:
-            items = shared_exemplar_items(device, part, cut)
-        else:
-            items = prepare_items(device, part, boxes[g0:g0 + int(group)] if boxes is not None else None)
+    for items, sizes in _clip_groups("count_clip", device, frames, boxes, group):
         res = locate_items(model, items, sizes, radius=radius, threshold=threshold, rel_threshold=rel_threshold, max_points=max_points,
                            keep=keep, normalization=normalization, max_s_cnt=max_s_cnt, max_batch=max_batch)
         points, where = [r[2] for r in res], [()] * len(res)
@@ -660,28 +654,13 @@ def count_flow(model, frames, boxes=None, *, lines, search=4, interval=1, min_ga
     raw field."""
     from . import flow as flow_
     device = next(model.parameters()).device
-    if int(group) != group or group < 1:
-        raise ValueError("count_flow: group is >= 1")
     if counter is None:
         counter = flow_.FlowCounter(device, lines=lines if lines is not None else (), search=search, interval=interval, min_gain=min_gain, band=band,
                                     camera=camera, min_texture=min_texture, cam_tol=cam_tol, min_voters=min_voters)
     elif lines is not None or camera is not None:
         raise ValueError("count_flow: counter= is a FlowCounter, and the lines are its own" + (", and so is the camera" if lines is None else ""))
-    frames = list(frames)
-    cut = None
-    if _is_shared(boxes):
-        k, bx = boxes
-        if not 0 <= int(k) < len(frames):
-            raise ValueError("count_flow: (k, boxes) names a frame of the call")
-        cut = cut_exemplars(device, frames[int(k)], bx)
     out = []
-    for g0 in range(0, len(frames), int(group)):
-        part = frames[g0:g0 + int(group)]
-        sizes = [(int(f.shape[1]), int(f.shape[0])) for f in part]
-        if cut is not None:
-            items = shared_exemplar_items(device, part, cut)
-        else:
-            items = prepare_items(device, part, boxes[g0:g0 + int(group)] if boxes is not None else None)
+    for items, sizes in _clip_groups("count_flow", device, frames, boxes, group):
         res = count_items_crops(model, items, normalization, max_s_cnt, max_batch)
         t0 = counter.frames
         got = counter.run([it[0] for it in items], [None if cr is not None else dm for _c, dm, cr in res], sizes,
@@ -700,10 +679,7 @@ def _frame_polygons(regions, n):
     """annotate_frames' `regions` -> one list of polygons per frame (one list for every frame, or one list per frame)."""
     if regions is None:
         return [None] * n
-    regions = list(regions)
-    per = [regions] * n if all(_is_region(r) for r in regions) else regions
-    if len(per) != n:
-        raise ValueError("regions: one list for every frame, or one list per frame")
+    per = _per_frame(regions, n)
     if any(_is_grid(r) for rs in per for r in rs):
         raise ValueError("annotate_frames draws polygons: a grid has no outline")
     return per
@@ -726,22 +702,16 @@ def annotate_frames(model, frames, boxes=None, *, out="rgb", gain=127.5, colorma
     tiles_.check_zoom(zoom, zoom_max, band_stride)
     device = next(model.parameters()).device
     n = len(frames)
-    sizes = [(int(f.shape[1]), int(f.shape[0])) for f in frames]
+    sizes = _sizes(frames)
     spaces = [(matrix or (f.matrix if isinstance(f, yuv_.YuvFrame) else "bt709"), range or (f.range if isinstance(f, yuv_.YuvFrame) else "limited"))
               for f in frames]
     polygons = _frame_polygons(regions, n)
     dev = frame_prep(device).device_frames(frames)
-    if zoom != 1:
-        ks = frame_zooms(dev, boxes, zoom, zoom_max, max_s_cnt)
-        res = count_frames_zoomed(model, dev, boxes, ks, normalization, max_s_cnt, max_batch, band_stride, crops=True)
-        heights = [NEW_H * k for k in ks]
-    else:
-        res = count_items_crops(model, prepare_items(device, dev, boxes), normalization, max_s_cnt, max_batch)
-        heights = NEW_H
+    res, heights = _count_at_zoom(model, dev, boxes, zoom, zoom_max, band_stride, normalization, max_s_cnt, max_batch)
     located = [(None, None, None)] * n
     if points:
-        located = locate_maps([(c, dm) for c, dm, _cr in res], sizes, [cr for _c, _dm, cr in res], radius=radius, threshold=threshold,
-                              rel_threshold=rel_threshold, max_points=max_points, keep=keep, new_h=heights)
+        located = locate_maps(res, sizes, radius=radius, threshold=threshold, rel_threshold=rel_threshold, max_points=max_points, keep=keep,
+                              new_h=heights)
     pictures = overlay_.overlay_for(device).render(
         dev, [None if cr is not None else dm for _c, dm, cr in res], gain=gain, colormap=colormap, points=[p for p, _s, _t in located],
         point_radius=point_radius, regions=polygons, labels=[overlay_.count_label(r[0], *wh) if label else None for r, wh in zip(res, sizes)],
@@ -778,18 +748,21 @@ def _is_region(r):
     return v.ndim == 2 and v.shape[1] == 2
 
 
+def _per_frame(regions, n):
+    """`regions` -- one list of regions for every frame, or one list per frame -- as one list per frame of n frames."""
+    regions = list(regions)
+    per = [regions] * n if all(_is_region(r) for r in regions) else regions
+    if len(per) != n:
+        raise ValueError("regions: one list for every frame, or one list per frame")
+    return per
+
+
 def frame_regions(regions, sizes):
     """count_regions' `regions` -> one list of regions.region() per frame.  regions: one list for every frame, or one list per frame; a
     region is a polygon [(x, y), ...] in pixels of the original frame, or ("grid", gy, gx) = the uniform grid over the frame (explicit
     boundaries ("grid", ys, xs) pass through)."""
-    regions = list(regions)
-    per = [regions] * len(sizes) if all(_is_region(r) for r in regions) else regions
-    if len(per) != len(sizes):
-        raise ValueError("regions: one list for every frame, or one list per frame")
-    out = []
-    for rs, (W, H) in zip(per, sizes):
-        out.append([regions_.frame_grid(W, H, int(r[1]), int(r[2])) if _is_grid(r) and np.ndim(r[1]) == 0 else regions_.region(r) for r in rs])
-    return out
+    return [[regions_.frame_grid(W, H, int(r[1]), int(r[2])) if _is_grid(r) and np.ndim(r[1]) == 0 else regions_.region(r) for r in rs]
+            for rs, (W, H) in zip(_per_frame(regions, len(sizes)), sizes)]
 
 
 def region_maps(results, sizes, crops, regions):
@@ -798,11 +771,16 @@ def region_maps(results, sizes, crops, regions):
     [(region_counts float32 [R], region_area int32 [R]), ...].  Every map of the call goes through ONE RegionSummer.sum; a split
     frame's nine crop maps add into the frame's regions.  region_counts[r] = scale * mass[r] / 60 with scale = count / (total / 60)
     when total > 0, else 1: the scale carries the test-time normalisation and nothing else, so regions that partition the frame sum
-    to count up to the reduction's rounding."""
-    crops = crops or [None] * len(results)
-    regions = frame_regions(regions, sizes)
+    to count up to the reduction's rounding.  A results entry may also be (count, density map, crops) as count_items_crops returns it:
+    with crops None its third field is the frame's crops."""
+    return _region_sums(results, sizes, crops, frame_regions(regions, sizes))
+
+
+def _region_sums(results, sizes, crops, regions):
+    """region_maps behind its frame_regions: regions is that function's result, which count_regions and locate_frames already hold."""
+    crops = _crops_of(results, crops)
     maps, places, set_of_map = [], [], []
-    for f, ((_c, dm), (W, H), cr) in enumerate(zip(results, sizes, crops)):
+    for f, ((_c, dm, *_cr), (W, H), cr) in enumerate(zip(results, sizes, crops)):
         h, w = dm.shape
         pl = map_placement(W, H, w)
         for k, m in enumerate(cr if cr is not None else [dm]):
@@ -811,12 +789,11 @@ def region_maps(results, sizes, crops, regions):
             set_of_map.append(f)
     if not maps:
         return []
-    maps = [m if (m.dtype == torch.float32 and m.is_contiguous()) else m.float().contiguous() for m in maps]
-    sums = regions_.region_summer(maps[0].device).sum(maps, places, set_of_map, regions)
+    sums = regions_.region_summer(maps[0].device).sum(_fp32_maps(maps), places, set_of_map, regions)
     out = []
-    for (count, _dm), (mass, area, total) in zip(results, sums):
+    for r, (mass, area, total) in zip(results, sums):
         pred = np.float64(total) / 60
-        scale = np.float64(count) / pred if total > 0 else np.float64(1.0)
+        scale = np.float64(r[0]) / pred if total > 0 else np.float64(1.0)
         out.append(((scale * mass.astype(np.float64) / 60).astype(np.float32), area))
     return out
 
@@ -831,8 +808,8 @@ def count_regions(model, frames, regions, boxes=None, *, normalization=True, max
     map pixels whose centre lies in the region.  A frame that takes the 3 x 3 split is summed over its nine crop maps."""
     device = next(model.parameters()).device
     items = prepare_items(device, frames, boxes)
-    sizes = [(int(f.shape[1]), int(f.shape[0])) for f in frames]
+    sizes = _sizes(frames)
     per = frame_regions(regions, sizes)
     res = count_items_crops(model, items, normalization, max_s_cnt, max_batch)
-    sums = region_maps([(c, dm) for c, dm, _cr in res], sizes, [cr for _c, _dm, cr in res], per)
+    sums = _region_sums(res, sizes, None, per)
     return [(c, dm, counts, area) for (c, dm, _cr), (counts, area) in zip(res, sums)]

@@ -95,6 +95,18 @@ def _gather_windows(L, images, plan, h, dst, nb, st):
         dst[nw:].zero_()                       # padding rows only need defined values
 
 
+def _width_runs(images):
+    """Runs of consecutive images of one width: [(first image, count, width), ...]."""
+    runs, i = [], 0
+    while i < len(images):
+        j = i
+        while j + 1 < len(images) and images[j + 1].shape[-1] == images[i].shape[-1]:
+            j += 1
+        runs.append((i, j - i + 1, images[i].shape[-1]))
+        i = j + 1
+    return runs
+
+
 def _blend_outputs(L, out, images, want_sums, st):
     """The forward's per-window densities out [>= windows, h, 384], in the order of _native_plan(images), stitched per image
     (countr_window_blend: one launch per run of consecutive images of one width) -> maps, or (maps, sums)."""
@@ -103,16 +115,10 @@ def _blend_outputs(L, out, images, want_sums, st):
     dev = images[0].device
     res, sums = [None] * len(images), [None] * len(images)
     row = 0
-    i = 0
-    while i < len(images):                      # runs of consecutive images of one width: one blend launch each
-        w = images[i].shape[-1]
-        j = i
-        while j + 1 < len(images) and images[j + 1].shape[-1] == w:
-            j += 1
-        n = j - i + 1
+    for i, n, w in _width_runs(images):         # one blend launch each
         stw = window_starts(w)
         if not stw:
-            for k in range(i, j + 1):
+            for k in range(i, i + n):
                 res[k] = torch.zeros(h, w, device=dev)          # narrower than a window: the reference's loop never runs
                 sums[k] = torch.zeros((), device=dev)
         else:
@@ -127,8 +133,41 @@ def _blend_outputs(L, out, images, want_sums, st):
                 if want_sums:
                     sums[i + k] = sm[k]
             row += n * len(stw)
-        i = j + 1
     return (res, sums) if want_sums else res
+
+
+def _native_front(model, images, max_batch):
+    """What every native one-forward call starts with: (window list, engine, forward batch size, stream pointer) after check_ln_fold on
+    the first window, or None where _native_plan refuses the images."""
+    import ctypes as C
+    plan = _native_plan(model, images, max_batch)
+    if plan is None:
+        return None
+    eng = model._engine()
+    eng.check_ln_fold(images[plan[0][0]][:, :, :, plan[0][1]:plan[0][1] + 384])     # (first use of a weight set only: may rebuild the plans)
+    return plan, eng, _bucket(len(plan), max_batch), C.c_void_p(torch.cuda.current_stream(images[0].device).cuda_stream)
+
+
+def forward_ahead(eng, p, nb, S, fill, fill_next=None, load_boxes=None, have=None):
+    """One forward batch of plan p = eng.plan(nb, S, False) with the optional encoder look-ahead -> (out [nb, h, 384], valid until the next
+    forward of this plan, token).  fill(dst) writes this batch's images into dst [nb, 3, h, 384], padding rows included; it is skipped
+    when `have` is the engine's token for this batch's latent (an earlier call ran its encoder ahead).  fill_next(dst), given where the
+    caller found that the NEXT batch qualifies, does the same for that batch: its encoder forward then runs beside this batch's decoder /
+    density head, and token (engine.pipe_claim) is the next call's `have`; None otherwise.  load_boxes(view [nb, S, 3, 64, 64]) writes the
+    exemplars, padding rows included, when S > 0."""
+    img = p.buf["img"]
+    mine = p.enc_pipe is not None and eng.pipe_owner(have)
+    if not mine:
+        fill(img)
+    ahead = p.enc_pipe is not None and fill_next is not None
+    if ahead:
+        fill_next(p.pipe_img[:img.numel()].view(img.shape))
+    token = eng.pipe_claim() if ahead else None
+    if S > 0:
+        load_boxes(p.buf["boxes"].view(nb, S, 3, 64, 64))
+    if mine or ahead:
+        return eng.forward_loaded_pipelined(nb, S, mine, ahead), token
+    return eng.forward_loaded(nb, S), token
 
 
 @torch.no_grad()
@@ -139,41 +178,28 @@ def _native_maps(model, images, boxes, shot_num, max_batch, want_sums, have=None
     Pipelined encoder (density_maps_stream): `ahead` = the images of the NEXT call -- if that call takes this path with the same forward
     batch size, their windows are gathered now and their frozen-encoder forward runs beside this call's decoder / density head
     (flags["ahead"] = the engine's ownership token if it did); `have` = the token of the call that ran THIS call's encoder forward."""
-    import ctypes as C
-    plan = _native_plan(model, images, max_batch)
-    if plan is None:
+    front = _native_front(model, images, max_batch)
+    if front is None:
         return None
+    plan, eng, nb, st = front
     h = images[0].shape[-2]
-    dev = images[0].device
-    eng = model._engine()
-    L = eng.L
-    eng.check_ln_fold(images[plan[0][0]][:, :, :, plan[0][1]:plan[0][1] + 384])     # (first use of a weight set only: may rebuild the plans)
-    nb = _bucket(len(plan), max_batch)
     p = eng.plan(nb, shot_num, False)
-    img = p.buf["img"]
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    nw = len(plan)
-    have = p.enc_pipe is not None and eng.pipe_owner(have)      # (`have`: the token of the call that ran our encoder)
-    if not have:
-        _gather_windows(L, images, plan, h, img, nb, st)
     plan_next = _native_plan(model, ahead, max_batch) if (ahead is not None and p.enc_pipe is not None) else None
-    if plan_next is not None and (_bucket(len(plan_next), max_batch) != nb or ahead[0].shape[-2] != h or ahead[0].device != dev):
+    if plan_next is not None and (_bucket(len(plan_next), max_batch) != nb or ahead[0].shape[-2] != h or ahead[0].device != images[0].device):
         plan_next = None
-    if plan_next is not None:
-        _gather_windows(L, ahead, plan_next, h, p.pipe_img[:img.numel()].view(img.shape), nb, st)
-    if flags is not None:
-        flags["ahead"] = eng.pipe_claim() if plan_next is not None else None
-    if shot_num > 0:
-        bx = p.buf["boxes"].view(nb, shot_num, 3, 64, 64)
+
+    def load_boxes(bx):
         for j, (i, _s) in enumerate(plan):
             bx[j].copy_(boxes[i][0, :shot_num])
-        if nb > nw:
-            bx[nw:].zero_()
-    if have or plan_next is not None:
-        out = eng.forward_loaded_pipelined(nb, shot_num, have, plan_next is not None)
-    else:
-        out = eng.forward_loaded(nb, shot_num)      # [nb, h, 384], valid until the next forward of this plan
-    return _blend_outputs(L, out, images, want_sums, st)
+        if nb > len(plan):
+            bx[len(plan):].zero_()
+
+    out, token = forward_ahead(eng, p, nb, shot_num, lambda dst: _gather_windows(eng.L, images, plan, h, dst, nb, st),
+                               (lambda dst: _gather_windows(eng.L, ahead, plan_next, h, dst, nb, st)) if plan_next is not None else None,
+                               load_boxes, have)
+    if flags is not None:
+        flags["ahead"] = token
+    return _blend_outputs(eng.L, out, images, want_sums, st)
 
 
 @torch.no_grad()
@@ -193,13 +219,7 @@ def density_maps(model, images, boxes, shot_num, max_batch=32, return_sums=False
     plan = [(i, s) for i, im in enumerate(images) for s in window_starts(im.shape[-1])]
     # runs of consecutive images with one width: (first image, count, width).  Their windows are consecutive rows of the plan
     # (image-major), so window position k of the whole run is the strided slice rows[k::nwin] -- no index tensors, no host sync
-    runs, i = [], 0
-    while i < len(images):
-        j = i
-        while j + 1 < len(images) and images[j + 1].shape[-1] == images[i].shape[-1]:
-            j += 1
-        runs.append((i, j - i + 1, images[i].shape[-1]))
-        i = j + 1
+    runs = _width_runs(images)
     first_row, r = {}, 0
     for i, im in enumerate(images):
         first_row[i] = r
@@ -297,6 +317,15 @@ def _normalise(pred, dm, pos, normalization):
     return pred
 
 
+def split_count(dms, pos, normalization):
+    """The count rule of the 3 x 3 split (FSC_test_cross(few-shot).py:273-320, 353-359): dms = the nine crops' maps in the reference's
+    list order -> (pred_cnt, density_map).  The count is the sum of the nine maps' counts, added in list order (the order decides the
+    last bits); the map, which the normalisation reads, is the LAST crop's (the reference reuses its variable)."""
+    pred = sum((d.sum() / 60).item() for d in dms)
+    dm = dms[-1]
+    return _normalise(pred, dm, pos, normalization), dm
+
+
 @torch.no_grad()
 def count_image(model, samples, boxes, shot_num, pos=None, normalization=True, max_s_cnt=1, max_batch=32, return_crops=False):
     """Full per-image test path: returns (pred_cnt, density_map).  pos: exemplar rectangles [(y1, x1, y2, x2), ...].
@@ -313,12 +342,10 @@ def count_image(model, samples, boxes, shot_num, pos=None, normalization=True, m
             crop = samples[:, :, top:top + h // 3, left:left + w // 3]
             crops.append(F.interpolate(crop, size=(h, w), mode="bilinear", align_corners=False))
         dms = density_maps(model, crops, [boxes] * 9, shot_num, max_batch)
-        pred = sum((d.sum() / 60).item() for d in dms)
-        dm = dms[-1]                                   # the reference normalises with the LAST crop's map (its variable is reused)
+        pred, dm = split_count(dms, pos, normalization)
     else:
         dm = density_map(model, samples, boxes, shot_num, max_batch)
-        pred = (dm.sum() / 60).item()
-    pred = _normalise(pred, dm, pos, normalization)
+        pred = _normalise((dm.sum() / 60).item(), dm, pos, normalization)
     return (pred, dm, dms) if return_crops else (pred, dm)
 
 
@@ -372,25 +399,19 @@ def density_maps_shared(model, images, jobs, max_batch=32):
     of its shot count only the class-dependent tail (engine.forward_loaded_tail), and the first job of another shot count the decoder
     side on a copy of the latent (engine.forward_loaded_from).  A job's exemplars enter its plan by one indexed copy.  Images that do
     not fit run through density_maps job by job."""
-    import ctypes as C
-    plan = _native_plan(model, images, max_batch)
-    if plan is None:
+    front = _native_front(model, images, max_batch)
+    if front is None:
         return [density_maps(model, images, bx, int(S), max_batch) for bx, S in jobs]
-    h = images[0].shape[-2]
+    plan, eng, nb, st = front
     dev = images[0].device
-    eng = model._engine()
-    L = eng.L
-    eng.check_ln_fold(images[plan[0][0]][:, :, :, plan[0][1]:plan[0][1] + 384])     # (first use of a weight set only: may rebuild the plans)
     nw = len(plan)
-    nb = _bucket(nw, max_batch)
     shots = list(dict.fromkeys(int(S) for _bx, S in jobs))
     for _ in range(2):          # every plan exists before the first forward: building one may grow the shared scratch and drop the others
         for S in shots:
             eng.plan(nb, S, False)
     if any((nb, S, False) not in eng.plans for S in shots):
         raise _lib.CountrError("density_maps_shared: the engine could not hold the plans of %d shot counts at once" % len(shots))
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _gather_windows(L, images, plan, h, eng.plan(nb, shots[0], False).buf["img"], nb, st)
+    _gather_windows(eng.L, images, plan, images[0].shape[-2], eng.plan(nb, shots[0], False).buf["img"], nb, st)
     rows = torch.tensor([i for i, _s in plan], device=dev) if any(shots) else None          # window -> its image
     res = [None] * len(jobs)
     for S in shots:
@@ -411,7 +432,7 @@ def density_maps_shared(model, images, jobs, max_batch=32):
             else:
                 out = eng.forward_loaded_from(nb, S, shots[0])
             first = False
-            res[j] = _blend_outputs(L, out, images, False, st)
+            res[j] = _blend_outputs(eng.L, out, images, False, st)
     return res
 
 

@@ -210,32 +210,25 @@ def zoomed_map(model, image, ex, rects=None, max_batch=32, band_stride=128, stit
     eng.check_ln_fold(image[:, :, :TILE, :TILE])     # (first use of a weight set only: may rebuild the plans)
     with torch.cuda.device(dev):
         st.begin(len(tiles))
+        def fill(chunk):
+            def into(dst):
+                st.gather(image, chunk, dst)
+                if dst.shape[0] > len(chunk):
+                    dst[len(chunk):].zero_()           # padding rows only need defined values
+            return into
+
         have, first = None, 0
         for i, (chunk, nb) in enumerate(zip(chunks, buckets)):
-            p = eng.plan(nb, S, False)
-            img = p.buf["img"]
             n = len(chunk)
-            mine = p.enc_pipe is not None and eng.pipe_owner(have)       # this chunk's encoder ran beside the previous chunk's decoder
-            if not mine:
-                st.gather(image, chunk, img)
-                if nb > n:
-                    img[n:].zero_()                # padding rows only need defined values
-            ahead = i + 1 < len(chunks) and buckets[i + 1] == nb and p.enc_pipe is not None
-            if ahead:
-                nxt = p.pipe_img[:img.numel()].view(img.shape)
-                st.gather(image, chunks[i + 1], nxt)
-                if nb > len(chunks[i + 1]):
-                    nxt[len(chunks[i + 1]):].zero_()
-            have = eng.pipe_claim() if ahead else None
-            if S > 0:
-                bx = p.buf["boxes"].view(nb, S, 3, 64, 64)
+
+            def load_boxes(bx):
                 bx[:n].copy_(ex[:, :S].expand(n, S, 3, 64, 64))
                 if nb > n:
                     bx[n:].zero_()
-            if mine or ahead:
-                out = eng.forward_loaded_pipelined(nb, S, mine, ahead)
-            else:
-                out = eng.forward_loaded(nb, S)     # [nb, 384, 384], valid until the next forward of this plan
+
+            ahead = i + 1 < len(chunks) and buckets[i + 1] == nb     # the next chunk's encoder runs beside this chunk's decoder
+            out, have = inference.forward_ahead(eng, eng.plan(nb, S, False), nb, S, fill(chunk), fill(chunks[i + 1]) if ahead else None,
+                                                load_boxes, have)
             st.put(first, out[:n])
             first += n
         return st.stitch(rows, cols, hk, wk, rects)

@@ -193,7 +193,7 @@ def main():
         else:
             results = [r + (None, None, None, None) for r in frames.count_items(model, items)]
         if polygons is not None:      # the nine crop maps of a frame that took the 3 x 3 path add into the frame's regions
-            summed = frames.region_maps([r[:2] for r in results], sizes, [r[5] for r in results], frames.frame_regions(polygons, sizes))
+            summed = frames.region_maps([r[:2] for r in results], sizes, [r[5] for r in results], polygons)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / len(paths)
         for pth, (sample, _ex, rects), (pred_cnt, dm, pts, score, total, _crops), size, reg in zip(paths, items, results, sizes, summed):

@@ -118,9 +118,8 @@ def count_zoomed(model, raw, boxes, zoom, args, normalization):
     res = frames.count_frames_zoomed(model, raw, boxes, ks, normalization, 1, 32, args.band_stride, crops=True)
     located = [(None, None, None)] * len(raw)
     if args.points:
-        located = frames.locate_maps([(c, dm) for c, dm, _cr in res], [(r.shape[1], r.shape[0]) for r in raw], [cr for _c, _dm, cr in res],
-                                     radius=args.points_radius, rel_threshold=args.points_rel_threshold, keep=args.points_keep,
-                                     new_h=[frames.NEW_H * k for k in ks])
+        located = frames.locate_maps(res, [(r.shape[1], r.shape[0]) for r in raw], radius=args.points_radius,
+                                     rel_threshold=args.points_rel_threshold, keep=args.points_keep, new_h=[frames.NEW_H * k for k in ks])
     torch.cuda.synchronize()
     prep = frames.frame_prep(next(model.parameters()).device)
     samples = [None if args.no_viz else prep.prepare([r], frames.NEW_H * k)[0][0] for r, k in zip(raw, ks)]
@@ -209,7 +208,7 @@ def annotate_group(model, raw, args, zoom, polygons, out, **space):
                                                         keep=args.points_keep, new_h=[frames.NEW_H * k for k in ks])]
     summed = [None] * len(raw)
     if polygons is not None:
-        summed = frames.region_maps(results, sizes, None, frames.frame_regions(polygons, sizes))
+        summed = frames.region_maps(results, sizes, None, polygons)
     torch.cuda.synchronize()
     return [(c, dm, pic, pts, score, total, reg) for (c, dm, pic, pts, score), total, reg in zip(res, totals, summed)]
 
@@ -287,7 +286,7 @@ def run_yuv(args, model, device, zoom, region_names, polygons, clip):
                                              keep=args.points_keep)
             summed = [None] * len(raw)
             if polygons is not None:
-                summed = frames.region_maps(results, [(w, h)] * len(raw), None, frames.frame_regions(polygons, [(w, h)] * len(raw)))
+                summed = frames.region_maps(results, [(w, h)] * len(raw), None, polygons)
             torch.cuda.synchronize()
             got = [(c, dm, pts, score, total, None, 1) for (c, dm), (pts, score, total) in zip(results, located)]
         dt = (time.perf_counter() - t0) / len(raw)
@@ -537,7 +536,7 @@ def main():
         summed = [None] * len(paths)
         if polygons is not None:
             sizes = [(w, h) for _s, _b, w, h in loaded]
-            summed = frames.region_maps(results, sizes, None, frames.frame_regions(polygons, sizes))
+            summed = frames.region_maps(results, sizes, None, polygons)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / len(paths)
         for pth, (sample, _b, old_w, old_h), (pred_cnt, dm), loc, reg in zip(paths, loaded, results, located, summed):

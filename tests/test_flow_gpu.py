@@ -356,6 +356,22 @@ def test_count_flow_on_yuv_frames(model):
     assert any(x[3].any() for x in a)
 
 
+def test_count_flow_with_shared_exemplars_equals_count_items_on_the_shared_crop_items(model):
+    """count_flow's (k, boxes): count_clip's form of it (tests/test_tracks_gpu.py), which runs the same walk over the clip."""
+    from countr_amd import count_flow, frames as FR
+    clip = nv12_clip(3, seed=9)
+    bx = [(10, 10, 11, 11), (40, 20, 41, 21), (70, 40, 71, 41)]            # under 10 px: with rectangles these would take the 3 x 3 split
+    got, _c = count_flow(model, clip, (1, bx), lines=FLOW_LINES, group=2, **FLOW)
+    crops = FR.cut_exemplars("cuda", clip[1], bx)
+    items = FR.shared_exemplar_items("cuda", clip, crops)
+    ref = FR.count_items(model, items[:2]) + FR.count_items(model, items[2:])
+    assert len(got) == 3
+    for a, (c, dm) in zip(got, ref):
+        assert a[0] == c and torch.equal(a[1], dm)
+    with pytest.raises(ValueError, match=r"count_flow: \(k, boxes\) names a frame of the call"):
+        count_flow(model, clip, (3, bx), lines=FLOW_LINES, **FLOW)
+
+
 # ---- the demo in a fresh child process
 def test_demo_zero_flow_on_a_raw_clip(tmp_path):
     Wd, H = 80, 96

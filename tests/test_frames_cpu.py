@@ -129,3 +129,47 @@ def test_package_exports():
     import countr_amd
     from countr_amd import frames
     assert countr_amd.count_frames is frames.count_frames and countr_amd.FramePrep is frames.FramePrep
+
+
+@pytest.mark.parametrize("scale, rects, normalization", [(1.0, None, True), (1.0, [[0, 0, 3, 3], [2, 2, 5, 7], [1, 0, 1, 9]], True),
+                                                         (40.0, [[0, 0, 3, 3], [2, 2, 5, 7], [1, 0, 1, 9]], True),
+                                                         (40.0, [[0, 0, 3, 3], [2, 2, 5, 7], [1, 0, 1, 9]], False)])
+def test_split_count_is_the_references_expression(scale, rects, normalization):
+    """inference.split_count on nine small maps against FSC_test_cross(few-shot).py:273-320 + 353-359 written out: the nine counts
+    added in list order, the LAST map returned and read by the normalisation.  scale = 40 puts the rectangles' mean over 1.8."""
+    import torch
+    from countr_amd import inference
+    g = torch.Generator().manual_seed(11)
+    dms = [torch.rand(6, 10, generator=g) * scale * (k + 1) for k in range(9)]
+    pred = 0
+    for d in dms:
+        pred += (d.sum() / 60).item()
+    want, divided = pred, False
+    if normalization and rects:
+        e_cnt = 0
+        for r in rects:
+            e_cnt += (dms[-1][r[0]:r[2] + 1, r[1]:r[3] + 1].sum() / 60).item()
+        e_cnt = e_cnt / 3
+        if e_cnt > 1.8:
+            want, divided = pred / e_cnt, True
+    assert divided == (scale == 40.0 and normalization)
+    got, dm = inference.split_count(dms, rects, normalization)
+    assert got == want and dm is dms[-1]
+
+
+def test_regions_one_list_for_every_frame_or_one_per_frame():
+    from countr_amd import frames
+    tri, quad, grid = [(0, 0), (4, 0), (0, 4)], [(1, 1), (5, 1), (5, 5), (1, 5)], ("grid", 2, 3)
+    per = frames._per_frame([tri, grid], 3)
+    assert len(per) == 3 and all(p == [tri, grid] for p in per)
+    assert frames._per_frame([[tri], [quad, grid], []], 3) == [[tri], [quad, grid], []]
+    assert frames._per_frame(iter([tri]), 2) == [[tri], [tri]]
+    for bad, n in (([[tri], [quad]], 3), ([[tri], [quad], [tri]], 2)):
+        with pytest.raises(ValueError, match="regions: one list for every frame, or one list per frame"):
+            frames._per_frame(bad, n)
+    # both users raise it: the polygons of annotate_frames and the regions of count_regions
+    with pytest.raises(ValueError, match="regions: one list for every frame, or one list per frame"):
+        frames._frame_polygons([[tri], [quad]], 3)
+    with pytest.raises(ValueError, match="regions: one list for every frame, or one list per frame"):
+        frames.frame_regions([[tri], [quad]], [(8, 8)] * 3)
+    assert [len(rs) for rs in frames.frame_regions([tri, grid], [(8, 8), (6, 4)])] == [2, 2]

@@ -251,3 +251,34 @@ def test_demo_cli_counts_and_writes_the_visualisation(tmp_path):
     m = models_mae_cross.mae_vit_base_patch16(norm_pix_loss="store_true", precision="bf16").to("cuda").eval()
     (cnt, _dm), = count_frames(m, [frame], [[(136, 98, 173, 127), (209, 125, 242, 150), (212, 168, 258, 200)]])
     assert float(line.split()[1]) == cnt
+
+
+def test_count_items_is_the_front_of_count_items_crops():
+    """count_items returns the first two fields of count_items_crops (one implementation): a frame on the 3 x 3 split beside a frame on
+    the plain path, on the tiny configuration in fp32."""
+    from functools import partial
+    import torch.nn as nn
+    from countr_amd import frames as FR
+    from countr_amd.models_mae_cross import SupervisedMAE
+    p, D, depth, H, Dd, ddepth, Hd = W.CONFIGS["tiny_test"]
+    m = SupervisedMAE(patch_size=p, embed_dim=D, depth=depth, num_heads=H, decoder_embed_dim=Dd, decoder_depth=ddepth, decoder_num_heads=Hd,
+                      mlp_ratio=4, norm_layer=partial(nn.LayerNorm, eps=1e-6), precision="fp32")
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in W.make_state_dict("tiny_test", seed=3).items()}, strict=True)
+    m = m.to("cuda").eval()
+    fs = [np.random.RandomState(11).randint(0, 256, (60, 90, 3)).astype(np.uint8), np.random.RandomState(12).randint(0, 256, (48, 120, 3)).astype(np.uint8)]
+    # frame 0: three exemplars under 10 px in the resized image -> the 3 x 3 split; frame 1: large exemplars -> the plain path
+    boxes = [[(10, 10, 11, 11), (40, 20, 41, 21), (70, 40, 71, 41)], [(5, 5, 30, 30), (50, 10, 80, 40), (90, 8, 115, 36)]]
+    items = FR.prepare_items("cuda", fs, boxes)
+    assert [inference_small(it[2]) for it in items] == [3, 0]
+    full = FR.count_items_crops(m, items)
+    short = FR.count_items(m, items)
+    assert len(short) == len(full) == 2 and all(len(s) == 2 and len(f) == 3 for s, f in zip(short, full))
+    for (c, dm), (fc, fdm, _cr) in zip(short, full):
+        assert c == fc and torch.equal(dm, fdm)
+    assert len(full[0][2]) == 9 and full[0][1] is full[0][2][-1]
+    assert full[1][2] is None
+
+
+def inference_small(rects):
+    from countr_amd import inference
+    return inference._small_exemplars(rects)

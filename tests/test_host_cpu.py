@@ -249,3 +249,71 @@ def test_density_maps_stream_looks_one_group_ahead(monkeypatch):
     assert [r for r, _p in out] == ["res:a", "res:b", "torch:torchpath", "res:c", "res:d"]
     assert out[0][1] == ["a", "b"] and out[1][1] == ["a", "b", "torchpath"]          # one group of look-ahead, no more
     assert seen == [("a", None, "b"), ("b", ("tok", "a"), "torchpath"), ("torchpath", None, "c"), ("c", None, "d"), ("d", ("tok", "c"), None)]
+
+
+class _FakePlan:
+    def __init__(self, nb, S, pipe):
+        self.buf = {"img": torch.zeros(nb, 3, 4, 4), "boxes": torch.zeros(nb * max(S, 1) * 3 * 64 * 64)}
+        self.enc_pipe = object() if pipe else None
+        self.pipe_img = torch.zeros(2 * nb * 3 * 4 * 4)         # longer than one batch: the step takes its front
+
+
+class _FakeEngine:
+    def __init__(self):
+        self.calls, self.token = [], None
+
+    def pipe_owner(self, token):
+        self.calls.append(("owner", token))
+        return token is not None and token is self.token
+
+    def pipe_claim(self):
+        self.token = object()
+        self.calls.append(("claim",))
+        return self.token
+
+    def forward_loaded(self, nb, S):
+        self.calls.append(("plain", nb, S))
+        return "out"
+
+    def forward_loaded_pipelined(self, nb, S, have, ahead):
+        self.calls.append(("pipelined", nb, S, have, ahead))
+        return "out"
+
+
+@pytest.mark.parametrize("pipe, have, nxt", [(False, "own", True), (True, None, False), (True, None, True), (True, "own", False),
+                                             (True, "own", True), (True, "stale", True), (True, "stale", False)])
+@pytest.mark.parametrize("S", [0, 2])
+def test_forward_ahead_fills_claims_and_chooses_the_forward(pipe, have, nxt, S):
+    """Host logic of inference.forward_ahead (no GPU) against a fake engine and plan: the current fill gets the plan's image buffer and
+    is skipped exactly when the engine owns `have`; the next fill gets the front of pipe_img in the image buffer's shape, and only on a
+    plan with an encoder lane; the token is pipe_claim()'s exactly when a next fill ran; the exemplars go into the [nb, S, 3, 64, 64]
+    view of the boxes buffer when S > 0; the pipelined forward runs with (mine, ahead) when either holds, the plain one otherwise."""
+    from countr_amd import inference
+    nb = 4
+    eng, p = _FakeEngine(), _FakePlan(nb, S, pipe)
+    owned = eng.pipe_claim() if have == "own" else None
+    token_in = owned if have == "own" else (object() if have == "stale" else None)
+    eng.calls.clear()
+    got = []
+    fill = lambda dst: got.append(("fill", dst))
+    fill_next = (lambda dst: got.append(("next", dst))) if nxt else None
+    out, token = inference.forward_ahead(eng, p, nb, S, fill, fill_next, lambda bx: got.append(("boxes", bx)), token_in)
+    mine, ahead = pipe and have == "own", pipe and nxt
+    assert out == "out"
+    assert [k for k, _d in got] == ["fill"] * (not mine) + ["next"] * ahead + ["boxes"] * (S > 0)
+    for kind, dst in got:
+        if kind == "fill":
+            assert dst is p.buf["img"]
+        elif kind == "next":
+            assert dst.shape == p.buf["img"].shape and dst.data_ptr() == p.pipe_img.data_ptr()
+        else:
+            assert dst.shape == (nb, S, 3, 64, 64) and dst.data_ptr() == p.buf["boxes"].data_ptr()
+    if ahead:
+        assert token is eng.token and token is not owned and ("claim",) in eng.calls
+    else:
+        assert token is None and ("claim",) not in eng.calls
+    assert eng.calls[-1] == (("pipelined", nb, S, mine, ahead) if (mine or ahead) else ("plain", nb, S))
+    assert sum(c[0] in ("plain", "pipelined") for c in eng.calls) == 1
+    # the latent is looked up before the next claim replaces the token
+    if pipe and ahead:
+        assert eng.calls.index(("owner", token_in)) < eng.calls.index(("claim",))

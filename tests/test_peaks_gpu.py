@@ -272,6 +272,13 @@ def test_locate_frames_few_shot_takes_the_three_by_three_path(model):
     assert np.array_equal(score, np.array([-t[0] for t in rows], np.float32))
     assert np.abs(pts - np.array([[t[3], t[4]] for t in rows])).max() <= 1e-3
     assert (pts[:, 0] > -0.5).all() and (pts[:, 0] < 199.5).all() and (pts[:, 1] > -0.5).all() and (pts[:, 1] < 119.5).all()
+    # locate_maps: (count, map, crops) entries without crops= give what (count, map) entries with an explicit crops list give
+    (p1, s1, t1), = FR.locate_maps([(cnt, dm)], [(200, 120)], [dms])
+    (p2, s2, t2), = FR.locate_maps([(cnt, dm, dms)], [(200, 120)])
+    (p3, _s3, t3), = FR.locate_maps([(cnt, dm, dms)], [(200, 120)], [None])          # an explicit crops= wins: the last crop's map alone
+    assert np.array_equal(p1, pts) and np.array_equal(p2, p1) and np.array_equal(s2, s1) and t2 == t1 and np.array_equal(s1, score)
+    (p4, _s4, t4), = FR.locate_maps([(cnt, dm)], [(200, 120)])
+    assert np.array_equal(p3, p4) and t3 == t4 and t4 <= t1
 
 
 # ---- the CLIs

@@ -234,6 +234,14 @@ def test_count_regions_end_to_end(model, shots):
         # sum, so two differences of two of them are within 4 n 2^-24 sum|v|; plus the rounding of the sixteen float32 results and of count
         part = float(rc[3:].astype(np.float64).sum())
         assert abs(part - cnt) <= abs(scale) / 60 * 4 * npix * u * tabs + float(np.spacing(np.abs(rc[3:])).sum()) + np.spacing(np.float32(abs(cnt))), (part, cnt)
+    # region_maps: (count, map, crops) entries with crops None give what (count, map) entries with an explicit crops list give, from raw
+    # regions or from frame_regions' result
+    triples = FR.count_items_crops(model, items)
+    sizes = [(f.shape[1], f.shape[0]) for f in FRAMES]
+    explicit = FR.region_maps([t[:2] for t in triples], sizes, crops, regs)
+    for other in (FR.region_maps(triples, sizes, None, regs), FR.region_maps(triples, sizes, None, FR.frame_regions(regs, sizes))):
+        for (rc, ra), (rc2, ra2), (_c, _d, rc0, ra0) in zip(explicit, other, res):
+            assert np.array_equal(rc, rc2) and np.array_equal(ra, ra2) and np.array_equal(rc, rc0) and np.array_equal(ra, ra0)
     loc = locate_frames(model, FRAMES, boxes)
     both = locate_frames(model, FRAMES, boxes, regions=regs)
     for (cnt, dm, pts, score), got, (_c, _d, rc, _ra), frame in zip(loc, both, res, FRAMES):
