@@ -2,8 +2,8 @@
 //   softmax rows fwd/bwd  : the unfused self-attention path (scores via countr_gemm), fp32 statistics
 //   cross attention       : q [B*N, D] against S exemplar tokens (<= 8: keys in registers; more: online softmax); one wave per query row
 //   (the fused flash-style self-attention forward lives in flash_attn.hip)
-#include "common.hpp"
-#include "../../include/countr_hip.h"
+#include "launch.hpp"
+#include <type_traits>
 
 namespace {
 
@@ -371,10 +371,11 @@ __global__ void xattn_bwd_finish_kernel(const float* __restrict__ partial, float
 
 extern "C" int countr_softmax_fwd_ld(const float* s, void* p, int64_t rows, int n, int ld, int out_bf16, void* stream) {
   if (!s || !p || n <= 0 || ld < n || ld > 64 * SMAX_PER_LANE) { countr_set_error("countr_softmax_fwd: need 0 < n <= ld <= 1024"); return -1; }
-  dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  if (out_bf16) hipLaunchKernelGGL(softmax_fwd_kernel<bf16_t>, grid, block, 0, STREAM(stream), s, (bf16_t*)p, rows, n, ld);
-  else hipLaunchKernelGGL(softmax_fwd_kernel<float>, grid, block, 0, STREAM(stream), s, (float*)p, rows, n, ld);
-  COUNTR_LAUNCH_CHECK("countr_softmax_fwd");
+  by_dtype(out_bf16 ? COUNTR_BF16 : COUNTR_F32, [&](auto t) {
+    using T = decltype(t);
+    launch(softmax_fwd_kernel<T>, (unsigned)((rows + 3) / 4), 256, stream, s, ptr<T>(p), rows, n, ld);
+  });
+  return countr_check_launch("countr_softmax_fwd");
 }
 extern "C" int countr_softmax_fwd(const float* s, void* p, int64_t rows, int n, int out_bf16, void* stream) {
   return countr_softmax_fwd_ld(s, p, rows, n, n, out_bf16, stream);
@@ -383,24 +384,27 @@ extern "C" int countr_softmax_fwd(const float* s, void* p, int64_t rows, int n, 
 extern "C" int countr_softmax_bwd(const void* p, const float* dp, void* ds, int64_t rows, int n, float scale, int dtype,
                                   void* stream) {
   if (!p || !dp || !ds || n > 64 * SMAX_PER_LANE) { countr_set_error("countr_softmax_bwd: bad args"); return -1; }
-  dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  if (dtype == COUNTR_BF16) hipLaunchKernelGGL(softmax_bwd_kernel<bf16_t>, grid, block, 0, STREAM(stream), (const bf16_t*)p, dp, (bf16_t*)ds, rows, n, scale);
-  else hipLaunchKernelGGL(softmax_bwd_kernel<float>, grid, block, 0, STREAM(stream), (const float*)p, dp, (float*)ds, rows, n, scale);
-  COUNTR_LAUNCH_CHECK("countr_softmax_bwd");
+  const dim3 grid((unsigned)((rows + 3) / 4));
+  by_dtype(dtype, [&](auto t) { using T = decltype(t); launch(softmax_bwd_kernel<T>, grid, 256, stream, ptr<T>(p), dp, ptr<T>(ds), rows, n, scale); });
+  return countr_check_launch("countr_softmax_bwd");
 }
 
 extern "C" int countr_xattn_fwd(const void* q, const void* k, const void* v, void* out, int B, int N, int S, int D, int heads,
                                 int ldkv, float scale, int dtype, void* stream) {
   if (!q || !k || !v || !out || S < 1 || D != 512 || heads * 32 != D) { countr_set_error("countr_xattn_fwd: need S >= 1, D == 512, head_dim == 32"); return -1; }
-  dim3 grid((unsigned)(((int64_t)B * N + 3) / 4)), block(256);
+  const dim3 grid((unsigned)(((int64_t)B * N + 3) / 4));
   if (S > XS) {      // more keys than the register form holds: online softmax over the key rows
-    if (dtype == COUNTR_BF16) hipLaunchKernelGGL(xattn_fwd_any_kernel<bf16_t>, grid, block, 0, STREAM(stream), (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, B, N, S, D, ldkv, scale);
-    else hipLaunchKernelGGL(xattn_fwd_any_kernel<float>, grid, block, 0, STREAM(stream), (const float*)q, (const float*)k, (const float*)v, (float*)out, B, N, S, D, ldkv, scale);
-    COUNTR_LAUNCH_CHECK("countr_xattn_fwd");
+    by_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      launch(xattn_fwd_any_kernel<T>, grid, 256, stream, ptr<T>(q), ptr<T>(k), ptr<T>(v), ptr<T>(out), B, N, S, D, ldkv, scale);
+    });
+    return countr_check_launch("countr_xattn_fwd");
   }
-  if (dtype == COUNTR_BF16) hipLaunchKernelGGL(xattn_fwd_kernel<bf16_t>, grid, block, 0, STREAM(stream), (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, B, N, S, D, ldkv, scale);
-  else hipLaunchKernelGGL(xattn_fwd_kernel<float>, grid, block, 0, STREAM(stream), (const float*)q, (const float*)k, (const float*)v, (float*)out, B, N, S, D, ldkv, scale);
-  COUNTR_LAUNCH_CHECK("countr_xattn_fwd");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(xattn_fwd_kernel<T>, grid, 256, stream, ptr<T>(q), ptr<T>(k), ptr<T>(v), ptr<T>(out), B, N, S, D, ldkv, scale);
+  });
+  return countr_check_launch("countr_xattn_fwd");
 }
 
 static constexpr int XATTN_ROWS_PER_BLOCK = 16;   // 8 x 36 = 288 blocks at B = 8: backward 11.8 us (32 rows per block: 14.8 us)
@@ -417,29 +421,28 @@ extern "C" int countr_xattn_bwd(const void* q, const void* k, const void* v, con
   const int bpb = (N + XATTN_ROWS_PER_BLOCK - 1) / XATTN_ROWS_PER_BLOCK;
   if (S > XS) {
     static_assert(XATTN_ROWS_PER_BLOCK == 4 * XROWS, "xattn_bwd_any_kernel holds XROWS rows per wave");
-    if (dtype == COUNTR_BF16) hipLaunchKernelGGL(xattn_bwd_any_kernel<bf16_t>, dim3(B * bpb), dim3(256), 0, STREAM(stream), (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, (bf16_t*)dq, workspace, N, S, D, ldkv, scale, XATTN_ROWS_PER_BLOCK);
-    else hipLaunchKernelGGL(xattn_bwd_any_kernel<float>, dim3(B * bpb), dim3(256), 0, STREAM(stream), (const float*)q, (const float*)k, (const float*)v, (const float*)dout, (float*)dq, workspace, N, S, D, ldkv, scale, XATTN_ROWS_PER_BLOCK);
-    hipLaunchKernelGGL(xattn_bwd_finish_kernel, dim3((2 * S * D + 255) / 256, B), dim3(256), 0, STREAM(stream), workspace, dk, dv,
-                       (bf16_t*)dk_bf16, (bf16_t*)dv_bf16, bpb, S, D);
-    COUNTR_LAUNCH_CHECK("countr_xattn_bwd");
+    by_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      launch(xattn_bwd_any_kernel<T>, B * bpb, 256, stream, ptr<T>(q), ptr<T>(k), ptr<T>(v), ptr<T>(dout), ptr<T>(dq), workspace, N, S, D, ldkv, scale,
+             XATTN_ROWS_PER_BLOCK);
+    });
+    launch(xattn_bwd_finish_kernel, dim3((2 * S * D + 255) / 256, B), 256, stream, workspace, dk, dv, ptr<bf16_t>(dk_bf16), ptr<bf16_t>(dv_bf16), bpb, S, D);
+    return countr_check_launch("countr_xattn_bwd");
   }
   const size_t lds = (size_t)4 * 2 * S * D * sizeof(float);
-#define COUNTR_XB_LAUNCH(TT, KSV)                                                                                             \
-  do {                                                                                                                         \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_bwd_kernel<TT, KSV>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              4 * 2 * XS * 512 * 4);                                                                           \
-    hipLaunchKernelGGL((xattn_bwd_kernel<TT, KSV>), dim3(B * bpb), dim3(256), lds, STREAM(stream), (const TT*)q, (const TT*)k,   \
-                       (const TT*)v, (const TT*)dout, (TT*)dq, workspace, N, S, D, ldkv, scale, XATTN_ROWS_PER_BLOCK);         \
-  } while (0)
-#define COUNTR_XB_DISPATCH(TT)                                                                                                 \
-  do {                                                                                                                         \
-    if (S == 1) COUNTR_XB_LAUNCH(TT, 1); else if (S == 2) COUNTR_XB_LAUNCH(TT, 2); else if (S == 3) COUNTR_XB_LAUNCH(TT, 3);  \
-    else COUNTR_XB_LAUNCH(TT, XS);                                                                                             \
-  } while (0)
-  if (dtype == COUNTR_BF16) COUNTR_XB_DISPATCH(bf16_t); else COUNTR_XB_DISPATCH(float);
-#undef COUNTR_XB_DISPATCH
-#undef COUNTR_XB_LAUNCH
-  hipLaunchKernelGGL(xattn_bwd_finish_kernel, dim3((2 * S * D + 255) / 256, B), dim3(256), 0, STREAM(stream), workspace, dk, dv,
-                     (bf16_t*)dk_bf16, (bf16_t*)dv_bf16, bpb, S, D);
-  COUNTR_LAUNCH_CHECK("countr_xattn_bwd");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    auto run = [&](auto ks) {      // KS: the kernel's compile-time bound on the number of keys
+      constexpr int KS = decltype(ks)::value;
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_bwd_kernel<T, KS>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * XS * 512 * 4);
+      launch_lds(xattn_bwd_kernel<T, KS>, B * bpb, 256, lds, stream, ptr<T>(q), ptr<T>(k), ptr<T>(v), ptr<T>(dout), ptr<T>(dq), workspace, N, S, D, ldkv,
+                 scale, XATTN_ROWS_PER_BLOCK);
+    };
+    if (S == 1) run(std::integral_constant<int, 1>{});
+    else if (S == 2) run(std::integral_constant<int, 2>{});
+    else if (S == 3) run(std::integral_constant<int, 3>{});
+    else run(std::integral_constant<int, XS>{});
+  });
+  launch(xattn_bwd_finish_kernel, dim3((2 * S * D + 255) / 256, B), 256, stream, workspace, dk, dv, ptr<bf16_t>(dk_bf16), ptr<bf16_t>(dv_bf16), bpb, S, D);
+  return countr_check_launch("countr_xattn_bwd");
 }

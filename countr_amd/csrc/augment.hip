@@ -464,7 +464,7 @@ extern "C" int countr_aug_normal(float* out, int64_t n, float scale, uint64_t se
   if (!out || n < 1 || n > ((int64_t)1 << 33)) { countr_set_error("countr_aug_normal: bad args (1 <= n <= 2^33)"); return -1; }
   hipLaunchKernelGGL(normal_kernel, dim3(countr_blocks_for((n + 3) / 4, 2048)), dim3(256), 0, STREAM(stream), out, (long long)n, scale,
                      (unsigned int)seed, (unsigned int)(seed >> 32), (unsigned int)counter, (unsigned int)(counter >> 32));
-  COUNTR_LAUNCH_CHECK("countr_aug_normal");
+  return countr_check_launch("countr_aug_normal");
 }
 
 extern "C" int countr_aug_jitter(const countr_aug_image* imgs, int n, uint64_t seed, float* partials, void* stream) {
@@ -498,7 +498,7 @@ extern "C" int countr_aug_jitter(const countr_aug_image* imgs, int n, uint64_t s
   }
   hipLaunchKernelGGL(jitter_a_kernel, dim3(n * PARTS), dim3(256), 0, STREAM(stream), a, (unsigned int)seed, (unsigned int)(seed >> 32), partials);
   if (any_cut) hipLaunchKernelGGL(jitter_b_kernel, dim3(n * PARTS), dim3(256), 0, STREAM(stream), a, partials);
-  COUNTR_LAUNCH_CHECK("countr_aug_jitter");
+  return countr_check_launch("countr_aug_jitter");
 }
 
 extern "C" int countr_aug_blur(const countr_aug_image* imgs, int n, void* stream) {
@@ -518,7 +518,7 @@ extern "C" int countr_aug_blur(const countr_aug_image* imgs, int n, void* stream
     d.vec = (s.w & 3) == 0 && ((((uintptr_t)s.jit) | ((uintptr_t)s.blr)) & 15) == 0;
   }
   hipLaunchKernelGGL(blur_kernel, dim3(items), dim3(256), 0, STREAM(stream), a, n);
-  COUNTR_LAUNCH_CHECK("countr_aug_blur");
+  return countr_check_launch("countr_aug_blur");
 }
 
 extern "C" int countr_aug_window(const countr_aug_image* imgs, int n, float* out, void* stream) {
@@ -537,7 +537,7 @@ extern "C" int countr_aug_window(const countr_aug_image* imgs, int n, float* out
     for (int k = 0; k < 6; ++k) d.m[k] = s.affine[k];
   }
   hipLaunchKernelGGL(window_kernel, dim3(countr_blocks_for((int64_t)n * OUT * (OUT / 4), 2048)), dim3(256), 0, STREAM(stream), a, out, n);
-  COUNTR_LAUNCH_CHECK("countr_aug_window");
+  return countr_check_launch("countr_aug_window");
 }
 
 extern "C" int countr_aug_density(const countr_aug_image* imgs, int n, const int* cells, int ncells, float* out, void* stream) {
@@ -553,7 +553,7 @@ extern "C" int countr_aug_density(const countr_aug_image* imgs, int n, const int
   for (int k = 0; k < 9; ++k) { a.w[k] = exp(-0.5 * (double)((k - 4) * (k - 4))); sum += a.w[k]; }
   for (int k = 0; k < 9; ++k) a.w[k] /= sum;
   hipLaunchKernelGGL(density_kernel, dim3(n * (OUT / DT) * (OUT / DT)), dim3(256), 0, STREAM(stream), a, cells, out);
-  COUNTR_LAUNCH_CHECK("countr_aug_density");
+  return countr_check_launch("countr_aug_density");
 }
 
 extern "C" int countr_aug_exemplars(const countr_aug_image* imgs, int n, float* out, void* stream) {
@@ -575,5 +575,5 @@ extern "C" int countr_aug_exemplars(const countr_aug_image* imgs, int n, float* 
     }
   }
   hipLaunchKernelGGL(exemplar_kernel, dim3(countr_blocks_for((int64_t)n * NBOX * 3 * BOX * (BOX / 4), 2048)), dim3(256), 0, STREAM(stream), a, out, n);
-  COUNTR_LAUNCH_CHECK("countr_aug_exemplars");
+  return countr_check_launch("countr_aug_exemplars");
 }

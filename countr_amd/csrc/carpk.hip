@@ -185,7 +185,7 @@ extern "C" int countr_carpk_prep_u8(const void* const* frames, const int* shapes
   const int blocks = countr_blocks_for(threads, MAX_BLOCKS);
   if (vec) hipLaunchKernelGGL(carpk_prep_kernel<true>, dim3(blocks), dim3(256), 0, STREAM(stream), a, img, ex, n, nrects, out_h, out_w, out_cols);
   else hipLaunchKernelGGL(carpk_prep_kernel<false>, dim3(blocks), dim3(256), 0, STREAM(stream), a, img, ex, n, nrects, out_h, out_w, out_cols);
-  COUNTR_LAUNCH_CHECK("countr_carpk_prep_u8");
+  return countr_check_launch("countr_carpk_prep_u8");
 }
 
 extern "C" int countr_carpk_count_blocks(int H, int W) {
@@ -209,5 +209,5 @@ extern "C" int countr_carpk_count(const float* maps, int n, int H, int W, const 
   const int blocks = countr_carpk_count_blocks(H, W);
   hipLaunchKernelGGL(carpk_count_kernel, dim3(blocks, n), dim3(256), 0, STREAM(stream), maps, a, H, W, workspace, blocks);
   hipLaunchKernelGGL(carpk_fold_kernel, dim3(n), dim3(64), 0, STREAM(stream), workspace, out, blocks);
-  COUNTR_LAUNCH_CHECK("countr_carpk_count");
+  return countr_check_launch("countr_carpk_count");
 }

@@ -270,11 +270,13 @@ int countr_check_launch(const char* what);
 // text) when countr_init was not called for this device.  The launch paths never allocate.
 #define COUNTR_ZERO_VEC_FLOATS 8192
 const float* countr_zero_vec(int n);
-#define COUNTR_LAUNCH_CHECK(what) return countr_check_launch(what)
 #define STREAM(s) reinterpret_cast<hipStream_t>(s)      // the exports take the stream as void*
-// workgroups of 256 threads for a grid-stride loop over `threads` items: at least one, at most `cap`
-static inline int countr_blocks_for(int64_t threads, int cap) {
-  const int64_t b = (threads + 255) / 256;
+// workgroups for a grid-stride loop over `work` items, `per_block` of them per workgroup and trip: at least one, at most `cap`.  THE
+// block count of the host code (the rest of the core library's export layer is in launch.hpp; this one the side libraries share).
+// Argument order: (work, cap, per_block) -- the cap comes BEFORE the items per block, e.g. countr_blocks_for(n16, 2048, 1024) is at most
+// 2048 blocks of 1024 items each
+static inline int countr_blocks_for(int64_t work, int cap, int per_block = 256) {
+  const int64_t b = (work + per_block - 1) / per_block;
   return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 __device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }

@@ -22,9 +22,7 @@
 // Round 5, the big maps (cwg3_body below): where the rows of the map are whole k-tiles (W % 64 == 0, or W % 96 == 0 with 96-pixel k-tiles)
 // a workgroup computes the THREE taps of one kernel row from ONE staged row segment of the input map -- a third fewer staged bytes and
 // a sixth fewer fragment reads per MFMA; the 192 x 192 and 96 x 96 layers of the density head.
-#include "common.hpp"
-#include "../../include/countr_hip.h"
-#include <stdlib.h>
+#include "launch.hpp"
 #include <type_traits>
 #include <utility>
 
@@ -430,7 +428,7 @@ int launch_cwg3(const CwgArgs& a, hipStream_t s) {
     attr_set = true;
   }
   hipLaunchKernelGGL((cwg3_kernel<KS>), dim3(a.tiles * a.Z), dim3(768), lds, s, a);
-  COUNTR_LAUNCH_CHECK("countr_gemm(conv wgrad, three taps per workgroup)");
+  return countr_check_launch("countr_gemm(conv wgrad, three taps per workgroup)");
 }
 
 template <int WNB, bool LIN>
@@ -465,7 +463,7 @@ int launch_cwg_group(const CwgGroup& g, hipStream_t s) {
     attr_set = true;
   }
   hipLaunchKernelGGL((cwg_group_kernel<WNB>), dim3(g.start[CWG_GROUP_MAX]), dim3(256 * WNB + 256), lds, s, g);
-  COUNTR_LAUNCH_CHECK("countr_gemm_group(lean linear wgrad)");
+  return countr_check_launch("countr_gemm_group(lean linear wgrad)");
 }
 
 template <int WNB, bool LIN>
@@ -477,7 +475,7 @@ int launch_cwg(const CwgArgs& a, hipStream_t s) {
     attr_set = true;
   }
   hipLaunchKernelGGL((cwg_kernel<WNB, LIN>), dim3(a.tiles * a.Z), dim3(256 * WNB + 256), lds, s, a);
-  COUNTR_LAUNCH_CHECK("countr_gemm(lean conv wgrad)");
+  return countr_check_launch("countr_gemm(lean conv wgrad)");
 }
 
 // k-tile of form 3 in pixels: a divisor of the map's width (64 where it divides, else 96)
@@ -489,8 +487,7 @@ static int cwg_contributors(const countr_gemm_args* a, int form) { return form =
 // form: 0 = does not qualify, 1 = 128x128 tiles, 2 = 128x256 tiles, 3 = 128 x 128 x the three taps of a kernel row (conv only).
 // lin: the (COL, COL) launch of an nn.Linear weight gradient
 int cwg_form(const countr_gemm_args* a, bool lin) {
-  { const char* e = getenv("COUNTR_LEAN"); if (e && atoi(e) == 0) return 0; }
-  { const char* e = getenv(lin ? "COUNTR_LEAN_LWGRAD" : "COUNTR_LEAN_WGRAD"); if (e && atoi(e) == 0) return 0; }
+  if (!env_int("COUNTR_LEAN", 1) || !env_int(lin ? "COUNTR_LEAN_LWGRAD" : "COUNTR_LEAN_WGRAD", 1)) return 0;      // (unset means on)
   if (!a->partial || a->nbatch > 1 || a->alpha != 1.0f || a->bias || a->resid || a->C2 || a->act != COUNTR_ACT_NONE) return 0;
   if (a->ln_xcopy || a->ln_stats_out || a->ln_stats || a->ln_colsum) return 0;
   if ((a->M % 128) || (a->N % 128) || (a->K % 64) || a->K < 64 || a->ldc != a->N) return 0;
@@ -513,7 +510,7 @@ int cwg_form(const countr_gemm_args* a, bool lin) {
   // 12 Cout Cin / 128^2 tiles x a chip-filling split leave >= 16 k-tiles each: the 192 x 192 layer
   const bool can3 = !lin && ((a->W % 64) == 0 || (a->W % 96) == 0);
   if (can3 && (long)(a->K / 64) * (a->M / 128) * 3 * (a->Cin / 128) >= 16 * 256) form = 3;
-  { const char* e = getenv("COUNTR_LEAN_WGRAD_FORM"); if (e) form = atoi(e); }
+  form = env_int("COUNTR_LEAN_WGRAD_FORM", form);      // (unset keeps the chosen form)
   if (form == 3 && !can3) form = 2;
   if (form == 2 && (wide % 256)) form = 1;
   if (form < 1 || form > 3) form = 1;
@@ -567,7 +564,7 @@ int countr_lean_wgrad_group_form(const countr_gemm_args* items, int n) {
     if (!cwg_form(&b, true)) return 0;
     if (b.N % 256) form = 1;
   }
-  { const char* e = getenv("COUNTR_LEAN_WGRAD_FORM"); if (e && atoi(e) == 1) form = 1; }
+  if (env_int("COUNTR_LEAN_WGRAD_FORM", form) == 1) form = 1;
   return form;
 }
 

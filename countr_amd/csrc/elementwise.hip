@@ -6,11 +6,7 @@
 //   cast / permute  : weight shadows (OIHW -> OHWI, dgrad form)
 //   masked mse loss : FSC_finetune_cross.py:290-303
 //   adamw           : torch.optim.AdamW(betas=(0.9,0.95))           (FSC_finetune_cross.py:235)
-#include "common.hpp"
-#include <stdlib.h>
-#include "../../include/countr_hip.h"
-
-extern "C" int countr_colsum_partials(const float* partial, float* out, int nparts, int C, int accumulate, void* stream);
+#include "launch.hpp"
 
 namespace {
 
@@ -712,44 +708,39 @@ __global__ __launch_bounds__(256) void amp_check_kernel(const float* __restrict_
 
 }  // namespace
 
-static inline int nblocks(int64_t work, int per_block = 256, int cap = 4096) {
-  int64_t b = (work + per_block - 1) / per_block;
-  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 extern "C" int countr_im2patch(const float* img, void* out, int B, int H, int W, int patch, int dtype, void* stream) {
   if (!img || !out || patch <= 0) { countr_set_error("countr_im2patch: bad args"); return -1; }
   const int gh = H / patch, gw = W / patch;
   const int64_t total = (int64_t)B * gh * gw * 3 * patch * patch;
   if ((patch & 7) == 0 && (W & 3) == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)out & 31) == 0 && total / 8 < (int64_t)0x7fffffff) {
-    const int nb = nblocks(total / 8);
-    if (dtype == COUNTR_BF16) hipLaunchKernelGGL(im2patch_vec8_kernel<bf16_t>, dim3(nb), dim3(256), 0, STREAM(stream), img, (bf16_t*)out, B, H, W, patch, gh, gw);
-    else hipLaunchKernelGGL(im2patch_vec8_kernel<float>, dim3(nb), dim3(256), 0, STREAM(stream), img, (float*)out, B, H, W, patch, gh, gw);
-    COUNTR_LAUNCH_CHECK("countr_im2patch");
+    by_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      launch(im2patch_vec8_kernel<T>, countr_blocks_for(total / 8, 4096), 256, stream, img, ptr<T>(out), B, H, W, patch, gh, gw);
+    });
+    return countr_check_launch("countr_im2patch");
   }
-  if (dtype == COUNTR_BF16) hipLaunchKernelGGL(im2patch_kernel<bf16_t>, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), img, (bf16_t*)out, B, H, W, patch, gh, gw);
-  else hipLaunchKernelGGL(im2patch_kernel<float>, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), img, (float*)out, B, H, W, patch, gh, gw);
-  COUNTR_LAUNCH_CHECK("countr_im2patch");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(im2patch_kernel<T>, countr_blocks_for(total, 4096), 256, stream, img, ptr<T>(out), B, H, W, patch, gh, gw);
+  });
+  return countr_check_launch("countr_im2patch");
 }
 
 extern "C" int countr_conv3x3_c3_fwd(const float* in, const float* w, const float* bias, void* out, int S, int H, int W,
                                      int dtype, void* stream) {
   if (!in || !w || !bias || !out) { countr_set_error("countr_conv3x3_c3_fwd: null"); return -1; }
-  // every block first stages the 64x27 weights into LDS: few, long-lived blocks (COUNTR_C3_BLOCKS overrides the cap for tuning)
+  // every block first stages the 64x27 weights into LDS: few, long-lived blocks
   constexpr int cap = 256;   // measured at 24 boxes: 2048 blocks 31.2 us, 512 23.6, 256 22.2, 128 38.2
-  const int nb = nblocks((int64_t)S * H * W, 32, cap);
   // four pixels per thread where rows are whole quads and 16-byte aligned (the 64 x 64 exemplar crops): COUNTR_C3_QUAD=0 keeps the per-pixel kernel
-  const char* eq = getenv("COUNTR_C3_QUAD");      // (read per call: tests compare the two kernels inside one process)
-  const int quad = eq ? atoi(eq) : 1;
-  if (quad && (W % 4) == 0 && ((uintptr_t)in & 15) == 0 && (int64_t)S * H * W < ((int64_t)1 << 30)) {
-    const int nbq = nblocks((int64_t)S * H * (W / 4), 32, cap);
-    if (dtype == COUNTR_BF16) hipLaunchKernelGGL(conv3x3_c3_fwd4_kernel<bf16_t>, dim3(nbq), dim3(256), 0, STREAM(stream), in, w, bias, (bf16_t*)out, S, H, W);
-    else hipLaunchKernelGGL(conv3x3_c3_fwd4_kernel<float>, dim3(nbq), dim3(256), 0, STREAM(stream), in, w, bias, (float*)out, S, H, W);
-    COUNTR_LAUNCH_CHECK("countr_conv3x3_c3_fwd");
+  // (the switch is read on every call: tests compare the two kernels inside one process)
+  if (env_int("COUNTR_C3_QUAD", 1) && (W % 4) == 0 && ((uintptr_t)in & 15) == 0 && (int64_t)S * H * W < ((int64_t)1 << 30)) {
+    const int nbq = countr_blocks_for((int64_t)S * H * (W / 4), cap, 32);
+    by_dtype(dtype, [&](auto t) { using T = decltype(t); launch(conv3x3_c3_fwd4_kernel<T>, nbq, 256, stream, in, w, bias, ptr<T>(out), S, H, W); });
+    return countr_check_launch("countr_conv3x3_c3_fwd");
   }
-  if (dtype == COUNTR_BF16) hipLaunchKernelGGL(conv3x3_c3_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, STREAM(stream), in, w, bias, (bf16_t*)out, S, H, W);
-  else hipLaunchKernelGGL(conv3x3_c3_fwd_kernel<float>, dim3(nb), dim3(256), 0, STREAM(stream), in, w, bias, (float*)out, S, H, W);
-  COUNTR_LAUNCH_CHECK("countr_conv3x3_c3_fwd");
+  const int nb = countr_blocks_for((int64_t)S * H * W, cap, 32);
+  by_dtype(dtype, [&](auto t) { using T = decltype(t); launch(conv3x3_c3_fwd_kernel<T>, nb, 256, stream, in, w, bias, ptr<T>(out), S, H, W); });
+  return countr_check_launch("countr_conv3x3_c3_fwd");
 }
 
 extern "C" int countr_conv3x3_c3_wgrad_nblocks(void) {
@@ -762,18 +753,15 @@ extern "C" int countr_conv3x3_c3_wgrad(const float* in, const void* dy, float* d
   if (!in || !dy || !dw || !db || !workspace) { countr_set_error("countr_conv3x3_c3_wgrad: null"); return -1; }
   if ((int64_t)S * H * W >= (int64_t)1 << 31) { countr_set_error("countr_conv3x3_c3_wgrad: more than 2^31 pixels"); return -1; }
   const int nb = countr_conv3x3_c3_wgrad_nblocks();
-  if (dtype == COUNTR_BF16) hipLaunchKernelGGL(conv3x3_c3_wgrad_kernel<bf16_t>, dim3(nb), dim3(256), 0, STREAM(stream), in, (const bf16_t*)dy, workspace, S, H, W);
-  else hipLaunchKernelGGL(conv3x3_c3_wgrad_kernel<float>, dim3(nb), dim3(256), 0, STREAM(stream), in, (const float*)dy, workspace, S, H, W);
-  hipLaunchKernelGGL(conv3x3_c3_wgrad_finish_kernel, dim3((64 * 28 + 15) / 16), dim3(16 * C3F_GROUPS), 0, STREAM(stream), workspace, dw, db, nb, accumulate);
-  COUNTR_LAUNCH_CHECK("countr_conv3x3_c3_wgrad");
+  by_dtype(dtype, [&](auto t) { using T = decltype(t); launch(conv3x3_c3_wgrad_kernel<T>, nb, 256, stream, in, ptr<T>(dy), workspace, S, H, W); });
+  launch(conv3x3_c3_wgrad_finish_kernel, (64 * 28 + 15) / 16, 16 * C3F_GROUPS, stream, workspace, dw, db, nb, accumulate);
+  return countr_check_launch("countr_conv3x3_c3_wgrad");
 }
 
 // Grid of the XCD-aware form (up2_block): one pass over the map, a multiple of 8 blocks, uncapped; COUNTR_UP2_XCD=0 keeps launch order.
 static int up2_xcd_grid(int64_t work, int& nb) {
-  const char* e = getenv("COUNTR_UP2_XCD");
-  const int on = e ? atoi(e) : 1;
   const int64_t b = (work + 255) / 256;
-  if (!on || b < 64 || b > (1 << 22)) return 0;
+  if (!env_int("COUNTR_UP2_XCD", 1) || b < 64 || b > (1 << 22)) return 0;
   nb = (int)((b + 7) / 8 * 8);
   return 1;
 }
@@ -781,47 +769,41 @@ static int up2_xcd_grid(int64_t work, int& nb) {
 // the adjoint's chunk form (upsample2x_bwd_chunk_kernel): 256 channels, rows of whole 8-pixel chunks, 32-bit element offsets inside
 // one image's fine map; COUNTR_UP2_ROWS=0 keeps the per-pixel kernel
 static bool up2_rows_form(int B, int H, int W, int C) {
-  const char* e = getenv("COUNTR_UP2_ROWS");      // (read per call: A/B and tests inside one process; not on a replay path)
-  const int on = e ? atoi(e) : 1;
-  return on && C == 256 && (W % 8) == 0 && W >= 8 && (long long)4 * H * W * C < (1ll << 30) && (long long)B * H * (W / 8) < (1ll << 30);
+  return env_int("COUNTR_UP2_ROWS", 1) && C == 256 && (W % 8) == 0 && W >= 8 && (long long)4 * H * W * C < (1ll << 30) &&
+         (long long)B * H * (W / 8) < (1ll << 30);
 }
 
 extern "C" int countr_upsample2x_fwd(const void* in, void* out, int B, int H, int W, int C, int dtype, void* stream) {
   if (!in || !out || (C != 1 && C % 8)) { countr_set_error("countr_upsample2x_fwd: C must be 1 or a multiple of 8"); return -1; }
   const int64_t total = (int64_t)B * 4 * H * W * (C == 1 ? 1 : C / 8);
-  const int nb = nblocks(total, 256, 8192);
-  int nbq = nblocks(total / 4, 256, 8192);     // multi-channel maps: one thread per 2x2 block of fine pixels (quad kernel)
+  const int nb = countr_blocks_for(total, 8192);
+  int nbq = countr_blocks_for(total / 4, 8192);     // multi-channel maps: one thread per 2x2 block of fine pixels (quad kernel)
   const int xcd = up2_xcd_grid(total / 4, nbq);
-  if (dtype == COUNTR_BF16) {
-    if (C == 1) hipLaunchKernelGGL((upsample2x_fwd_kernel<bf16_t, 1>), dim3(nb), dim3(256), 0, STREAM(stream), (const bf16_t*)in, (bf16_t*)out, B, H, W, C);
-    else hipLaunchKernelGGL((upsample2x_fwd_quad_kernel<bf16_t>), dim3(nbq), dim3(256), 0, STREAM(stream), (const bf16_t*)in, (bf16_t*)out, B, H, W, C, xcd);
-  } else {
-    if (C == 1) hipLaunchKernelGGL((upsample2x_fwd_kernel<float, 1>), dim3(nb), dim3(256), 0, STREAM(stream), (const float*)in, (float*)out, B, H, W, C);
-    else hipLaunchKernelGGL((upsample2x_fwd_quad_kernel<float>), dim3(nbq), dim3(256), 0, STREAM(stream), (const float*)in, (float*)out, B, H, W, C, xcd);
-  }
-  COUNTR_LAUNCH_CHECK("countr_upsample2x_fwd");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (C == 1) launch(upsample2x_fwd_kernel<T, 1>, nb, 256, stream, ptr<T>(in), ptr<T>(out), B, H, W, C);
+    else launch(upsample2x_fwd_quad_kernel<T>, nbq, 256, stream, ptr<T>(in), ptr<T>(out), B, H, W, C, xcd);
+  });
+  return countr_check_launch("countr_upsample2x_fwd");
 }
 
 extern "C" int countr_upsample2x_bwd(const void* dout, void* din, int B, int H, int W, int C, int dtype, void* stream) {
   if (!dout || !din || (C != 1 && C % 8)) { countr_set_error("countr_upsample2x_bwd: C must be 1 or a multiple of 8"); return -1; }
   const int64_t total = (int64_t)B * H * W * (C == 1 ? 1 : C / 8);
-  int nb = nblocks(total, 256, 8192);
+  int nb = countr_blocks_for(total, 8192);
   // (a 2x2-coarse-block variant like the forward's was measured: 50.7 vs 50.2 us at 96 -> 192 and slower on the small maps)
   const int xcd = C == 1 ? 0 : up2_xcd_grid(total, nb);
   if (up2_rows_form(B, H, W, C)) {     // the density head's maps: one workgroup per 8-pixel chunk of a coarse row
     const int nbr = (B * H * (W / 8) + 7) / 8 * 8;
-    if (dtype == COUNTR_BF16) hipLaunchKernelGGL((upsample2x_bwd_chunk_kernel<bf16_t>), dim3(nbr), dim3(256), 0, STREAM(stream), (const bf16_t*)dout, (bf16_t*)din, B, H, W, 1);
-    else hipLaunchKernelGGL((upsample2x_bwd_chunk_kernel<float>), dim3(nbr), dim3(256), 0, STREAM(stream), (const float*)dout, (float*)din, B, H, W, 1);
-    COUNTR_LAUNCH_CHECK("countr_upsample2x_bwd");
+    by_dtype(dtype, [&](auto t) { using T = decltype(t); launch(upsample2x_bwd_chunk_kernel<T>, nbr, 256, stream, ptr<T>(dout), ptr<T>(din), B, H, W, 1); });
+    return countr_check_launch("countr_upsample2x_bwd");
   }
-  if (dtype == COUNTR_BF16) {
-    if (C == 1) hipLaunchKernelGGL((upsample2x_bwd_kernel<bf16_t, 1>), dim3(nb), dim3(256), 0, STREAM(stream), (const bf16_t*)dout, (bf16_t*)din, B, H, W, C, 0);
-    else hipLaunchKernelGGL((upsample2x_bwd_kernel<bf16_t, 8>), dim3(nb), dim3(256), 0, STREAM(stream), (const bf16_t*)dout, (bf16_t*)din, B, H, W, C, xcd);
-  } else {
-    if (C == 1) hipLaunchKernelGGL((upsample2x_bwd_kernel<float, 1>), dim3(nb), dim3(256), 0, STREAM(stream), (const float*)dout, (float*)din, B, H, W, C, 0);
-    else hipLaunchKernelGGL((upsample2x_bwd_kernel<float, 8>), dim3(nb), dim3(256), 0, STREAM(stream), (const float*)dout, (float*)din, B, H, W, C, xcd);
-  }
-  COUNTR_LAUNCH_CHECK("countr_upsample2x_bwd");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (C == 1) launch(upsample2x_bwd_kernel<T, 1>, nb, 256, stream, ptr<T>(dout), ptr<T>(din), B, H, W, C, 0);
+    else launch(upsample2x_bwd_kernel<T, 8>, nb, 256, stream, ptr<T>(dout), ptr<T>(din), B, H, W, C, xcd);
+  });
+  return countr_check_launch("countr_upsample2x_bwd");
 }
 
 // Several device-to-device copies in ONE launch (the per-step staging of a batch: images, exemplar crops, ground-truth map, loss mask --
@@ -859,11 +841,11 @@ extern "C" int countr_copy_multi(int n, const void* const* src, void* const* dst
     }
     t.src[i] = reinterpret_cast<const uint4*>(src[i]); t.dst[i] = reinterpret_cast<uint4*>(dst[i]); t.n16[i] = bytes[i] / 16;
     t.first[i] = blocks;
-    blocks += nblocks(t.n16[i], 1024, 2048);     // 4 x 16 bytes per thread and trip
+    blocks += countr_blocks_for(t.n16[i], 2048, 1024);     // 4 x 16 bytes per thread and trip
   }
   for (int i = n; i < 8; ++i) { t.src[i] = nullptr; t.dst[i] = nullptr; t.n16[i] = 0; t.first[i] = blocks; }
-  hipLaunchKernelGGL(copy_multi_kernel, dim3(blocks), dim3(256), 0, STREAM(stream), t);
-  COUNTR_LAUNCH_CHECK("countr_copy_multi");
+  launch(copy_multi_kernel, blocks, 256, stream, t);
+  return countr_check_launch("countr_copy_multi");
 }
 
 // ---- step prologue: everything an optimisation step needs from the host, as ONE kernel node at the head of the step's hipGraph ----
@@ -956,32 +938,27 @@ extern "C" int countr_step_prologue(const void* ring, int slots, int64_t* counte
     countr_set_error("countr_step_prologue: null / unaligned argument (16-byte pointers, mask_n % 4 == 0)"); return -1;
   }
   PrologueRec* rec_dev = reinterpret_cast<PrologueRec*>(counter + 2);       // counter: int64[2 + 32]: {executions, reserved, record copy}
-  hipLaunchKernelGGL(step_prologue_fetch_kernel, dim3(1), dim3(64), 0, STREAM(stream), reinterpret_cast<const PrologueRec*>(ring), slots,
-                     reinterpret_cast<long long*>(counter), rec_dev, hyper_dev);
-  hipLaunchKernelGGL(step_prologue_kernel, dim3(PRO_COPY_BLOCKS + (mask ? PRO_MASK_BLOCKS : 0)), dim3(256), 0, STREAM(stream),
-                     rec_dev, mask, mask ? mask_n / 4 : 0);
-  COUNTR_LAUNCH_CHECK("countr_step_prologue");
+  launch(step_prologue_fetch_kernel, 1, 64, stream, reinterpret_cast<const PrologueRec*>(ring), slots, reinterpret_cast<long long*>(counter),
+         rec_dev, hyper_dev);
+  launch(step_prologue_kernel, PRO_COPY_BLOCKS + (mask ? PRO_MASK_BLOCKS : 0), 256, stream, rec_dev, mask, mask ? mask_n / 4 : 0);
+  return countr_check_launch("countr_step_prologue");
 }
 
 extern "C" int countr_gelu_bwd(const void* dh, const void* pre, void* dpre, int64_t n, int dtype, void* stream) {
   if (!dh || !pre || !dpre || (n & 7)) { countr_set_error("countr_gelu_bwd: n must be a multiple of 8"); return -1; }
-  const int nb = nblocks(n / 8, 256, 8192);
-  if (dtype == COUNTR_BF16) hipLaunchKernelGGL(gelu_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, STREAM(stream), (const bf16_t*)dh, (const bf16_t*)pre, (bf16_t*)dpre, n / 8);
-  else hipLaunchKernelGGL(gelu_bwd_kernel<float>, dim3(nb), dim3(256), 0, STREAM(stream), (const float*)dh, (const float*)pre, (float*)dpre, n / 8);
-  COUNTR_LAUNCH_CHECK("countr_gelu_bwd");
+  const int nb = countr_blocks_for(n / 8, 8192);
+  by_dtype(dtype, [&](auto t) { using T = decltype(t); launch(gelu_bwd_kernel<T>, nb, 256, stream, ptr<T>(dh), ptr<T>(pre), ptr<T>(dpre), n / 8); });
+  return countr_check_launch("countr_gelu_bwd");
 }
 
-extern "C" int countr_colsum_nparts(void) { return 256; }
-// workspace: fp32 [256][N]
-extern "C" int countr_colsum(const void* x, float* out, float* workspace, int M, int N, int dtype, int accumulate, void* stream);
+extern "C" int countr_colsum_nparts(void) { return 256; }      // countr_colsum's workspace: fp32 [256][N]
 
 extern "C" int countr_cast_permute(const float* src, void* dst, int64_t n, int mode, int Co, int Ci, int taps, int dtype,
                                    void* stream) {
   if (!src || !dst) { countr_set_error("countr_cast_permute: null"); return -1; }
-  const int nb = nblocks(n, 256, 4096);
-  if (dtype == COUNTR_BF16) hipLaunchKernelGGL(cast_permute_kernel<bf16_t>, dim3(nb), dim3(256), 0, STREAM(stream), src, (bf16_t*)dst, n, mode, Co, Ci, taps);
-  else hipLaunchKernelGGL(cast_permute_kernel<float>, dim3(nb), dim3(256), 0, STREAM(stream), src, (float*)dst, n, mode, Co, Ci, taps);
-  COUNTR_LAUNCH_CHECK("countr_cast_permute");
+  const int nb = countr_blocks_for(n, 4096);
+  by_dtype(dtype, [&](auto t) { using T = decltype(t); launch(cast_permute_kernel<T>, nb, 256, stream, src, ptr<T>(dst), n, mode, Co, Ci, taps); });
+  return countr_check_launch("countr_cast_permute");
 }
 
 extern "C" int countr_conv_shadows(int n, const float* const* src, void* const* wf, void* const* wd, const int* co, const int* ci,
@@ -998,10 +975,9 @@ extern "C" int countr_conv_shadows(int n, const float* const* src, void* const* 
   }
   for (int i = 0; i < n; ++i)
     if (taps[i] > 9) { countr_set_error("countr_conv_shadows: at most 9 taps"); return -1; }
-  dim3 grid(nblocks(big, 32 * CS_CI * 9, 1024), n);   // one block per 32 x 8 x taps tile of the largest convolution
-  if (dtype == COUNTR_BF16) hipLaunchKernelGGL(conv_shadows_kernel<bf16_t>, grid, dim3(256), 0, STREAM(stream), t);
-  else hipLaunchKernelGGL(conv_shadows_kernel<float>, grid, dim3(256), 0, STREAM(stream), t);
-  COUNTR_LAUNCH_CHECK("countr_conv_shadows");
+  const dim3 grid(countr_blocks_for(big, 1024, 32 * CS_CI * 9), n);   // one block per 32 x 8 x taps tile of the largest convolution
+  by_dtype(dtype, [&](auto tag) { launch(conv_shadows_kernel<decltype(tag)>, grid, 256, stream, t); });
+  return countr_check_launch("countr_conv_shadows");
 }
 
 // Transposes of up to 96 16-bit matrices in ONE launch (blockIdx.y = matrix): dst[c][r] = src[r][c].  The refresh of the W^T shadows
@@ -1063,13 +1039,11 @@ extern "C" int countr_transpose16(int n, const void* const* src, void* const* ds
     if (m > big) big = m;
   }
   const int gx = (int)((big / 4096 + 3) / 4);       // up to four tiles of the largest matrix per block
-  hipLaunchKernelGGL(transpose16_kernel, dim3(gx < 1 ? 1 : gx, n), dim3(256), 0, STREAM(stream), t);
-  COUNTR_LAUNCH_CHECK("countr_transpose16");
+  launch(transpose16_kernel, dim3(gx < 1 ? 1 : gx, n), 256, stream, t);
+  return countr_check_launch("countr_transpose16");
 }
 
 extern "C" int countr_masked_mse_workspace_floats(int B) { return B * MSE_BLOCKS * 3; }
-extern "C" int countr_masked_mse_amp(const float* pred, const float* gt, const float* mask, float* dpred, float* sums,
-                                     float* workspace, int B, int HW, float grad_scale, const float* amp, void* stream);
 extern "C" int countr_masked_mse(const float* pred, const float* gt, const float* mask, float* dpred, float* sums,
                                  float* workspace, int B, int HW, float grad_scale, void* stream) {
   return countr_masked_mse_amp(pred, gt, mask, dpred, sums, workspace, B, HW, grad_scale, nullptr, stream);
@@ -1077,16 +1051,12 @@ extern "C" int countr_masked_mse(const float* pred, const float* gt, const float
 extern "C" int countr_masked_mse_amp(const float* pred, const float* gt, const float* mask, float* dpred, float* sums,
                                      float* workspace, int B, int HW, float grad_scale, const float* amp, void* stream) {
   if (!pred || !gt || !mask || !sums || !workspace) { countr_set_error("countr_masked_mse: null"); return -1; }
-  hipLaunchKernelGGL(masked_mse_kernel, dim3(MSE_BLOCKS, B), dim3(256), 0, STREAM(stream), pred, gt, mask, dpred, workspace, B, HW, grad_scale, amp);
-  hipLaunchKernelGGL(masked_mse_finish_kernel, dim3(1), dim3(64), 0, STREAM(stream), workspace, sums, B, MSE_BLOCKS);
-  COUNTR_LAUNCH_CHECK("countr_masked_mse");
+  launch(masked_mse_kernel, dim3(MSE_BLOCKS, B), 256, stream, pred, gt, mask, dpred, workspace, B, HW, grad_scale, amp);
+  launch(masked_mse_finish_kernel, 1, 64, stream, workspace, sums, B, MSE_BLOCKS);
+  return countr_check_launch("countr_masked_mse");
 }
 
 extern "C" int countr_adamw_gnorm_floats(void) { return 1 + 2048; }
-extern "C" int countr_adamw_step_amp(float* p, const float* g, float* m, float* v, void* shadow_bf16, int nranges,
-                                     const int64_t* starts, const int64_t* ends, const float* wds, const int* groups,
-                                     const int* zero_grad, float lr, float beta1, float beta2, float eps, int step, float grad_scale,
-                                     const float* hyper_dev, float* gnorm_ws, float* amp, void* stream);
 extern "C" int countr_adamw_step(float* p, const float* g, float* m, float* v, void* shadow_bf16, int nranges,
                                  const int64_t* starts, const int64_t* ends, const float* wds, const int* groups,
                                  const int* zero_grad, float lr, float beta1, float beta2, float eps, int step, float grad_scale,
@@ -1109,12 +1079,12 @@ extern "C" int countr_adamw_step_amp(float* p, const float* g, float* m, float* 
     if (R.grp[i] < 0 || R.grp[i] > 2) { countr_set_error("countr_adamw_step: counter group must be 0, 1 or 2"); return -1; }
   }
   const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-  const int nb = nblocks(total, 256, 2048);
-  if (amp) hipLaunchKernelGGL(amp_check_kernel, dim3(nblocks(total, 1024, 2048)), dim3(256), 0, STREAM(stream), g, R, amp);
-  hipLaunchKernelGGL(adamw_kernel, dim3(nb), dim3(256), 0, STREAM(stream), p, g, m, v, (bf16_t*)shadow_bf16, R, lr, beta1, beta2, eps, bc1, bc2, grad_scale, hyper_dev, gnorm_ws, amp);
-  if (gnorm_ws) hipLaunchKernelGGL(gnorm_finish_kernel, dim3(1), dim3(1024), 0, STREAM(stream), gnorm_ws, nb, amp);
-  else if (amp) hipLaunchKernelGGL(amp_update_kernel, dim3(1), dim3(64), 0, STREAM(stream), amp);
-  COUNTR_LAUNCH_CHECK("countr_adamw_step");
+  const int nb = countr_blocks_for(total, 2048);
+  if (amp) launch(amp_check_kernel, countr_blocks_for(total, 2048, 1024), 256, stream, g, R, amp);
+  launch(adamw_kernel, nb, 256, stream, p, g, m, v, ptr<bf16_t>(shadow_bf16), R, lr, beta1, beta2, eps, bc1, bc2, grad_scale, hyper_dev, gnorm_ws, amp);
+  if (gnorm_ws) launch(gnorm_finish_kernel, 1, 1024, stream, gnorm_ws, nb, amp);
+  else if (amp) launch(amp_update_kernel, 1, 64, stream, amp);
+  return countr_check_launch("countr_adamw_step");
 }
 
 extern "C" int countr_colsum(const void* x, float* out, float* workspace, int M, int N, int dtype, int accumulate, void* stream) {
@@ -1125,8 +1095,6 @@ extern "C" int countr_colsum(const void* x, float* out, float* workspace, int M,
   int parts = 2048 / ctiles; if (parts > 256) parts = 256; if (parts < 1) parts = 1;   // >= ~2k workgroups on 256 CUs
   const int rl = 256 / CV;
   if (parts > (M + rl - 1) / rl) parts = (M + rl - 1) / rl;
-  dim3 grid(ctiles, parts);
-  if (dtype == COUNTR_BF16) hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, STREAM(stream), (const bf16_t*)x, workspace, M, N, CV);
-  else hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, STREAM(stream), (const float*)x, workspace, M, N, CV);
+  by_dtype(dtype, [&](auto t) { using T = decltype(t); launch(colsum_kernel<T>, dim3(ctiles, parts), 256, stream, ptr<T>(x), workspace, M, N, CV); });
   return countr_colsum_partials(workspace, out, parts, N, accumulate, stream);
 }

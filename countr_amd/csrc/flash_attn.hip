@@ -332,7 +332,7 @@ int launch_attn_bwd(const void* qkv, const void* out, const void* dout, const fl
     hipLaunchKernelGGL((flash_attn_bwd_kernel<DH, true>), grid, block, lds, s, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv, N, H, scale);
   else
     hipLaunchKernelGGL((flash_attn_bwd_kernel<DH, false>), grid, block, lds, s, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv, N, H, scale);
-  COUNTR_LAUNCH_CHECK("countr_attn_bwd");
+  return countr_check_launch("countr_attn_bwd");
 }
 
 }  // namespace

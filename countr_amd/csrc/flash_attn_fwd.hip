@@ -582,7 +582,7 @@ int launch_fa_fwd_pipe(const void* qkv, void* out, float* lse, int B, int N, int
     if (DH != 64 || N % 64) { countr_set_error("countr_attn_fwd: scale <= 0 (pre-scaled q) needs head_dim 64 and N % 64 == 0"); return -1; }
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fa_fwd_pipe_kernel<64, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_ALL);
     hipLaunchKernelGGL((fa_fwd_pipe_kernel<64, false, true>), grid, block, C::LDS_ALL, s, (const bf16_t*)qkv, (bf16_t*)out, lse, N, H, 1.f);
-    COUNTR_LAUNCH_CHECK("countr_attn_fwd");
+    return countr_check_launch("countr_attn_fwd");
   }
   if (N % 64) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fa_fwd_pipe_kernel<DH, true>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_ALL);
@@ -591,7 +591,7 @@ int launch_fa_fwd_pipe(const void* qkv, void* out, float* lse, int B, int N, int
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fa_fwd_pipe_kernel<DH, false>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_ALL);
     hipLaunchKernelGGL((fa_fwd_pipe_kernel<DH, false>), grid, block, C::LDS_ALL, s, (const bf16_t*)qkv, (bf16_t*)out, lse, N, H, c);
   }
-  COUNTR_LAUNCH_CHECK("countr_attn_fwd");
+  return countr_check_launch("countr_attn_fwd");
 }
 
 }  // namespace

@@ -129,7 +129,7 @@ extern "C" int countr_frame_resize_u8(const void* const* frames, void* const* ou
   const int64_t vthreads = (int64_t)n * out_h * (vec_out ? out_w / 4 : out_w);
   if (vec_out) hipLaunchKernelGGL(resize_v_kernel<true>, dim3(countr_blocks_for(vthreads, MAX_BLOCKS)), dim3(256), 0, STREAM(stream), a, t8, vbounds, vweights, av.ksize, n, H, out_h, out_w);
   else hipLaunchKernelGGL(resize_v_kernel<false>, dim3(countr_blocks_for(vthreads, MAX_BLOCKS)), dim3(256), 0, STREAM(stream), a, t8, vbounds, vweights, av.ksize, n, H, out_h, out_w);
-  COUNTR_LAUNCH_CHECK("countr_frame_resize_u8");
+  return countr_check_launch("countr_frame_resize_u8");
 }
 
 extern "C" int countr_crop_resize_f32(const float* img, int h, int w, const int* rects, int n, int oh, int ow, float* out, void* stream) {
@@ -149,5 +149,5 @@ extern "C" int countr_crop_resize_f32(const float* img, int h, int w, const int*
   const int64_t threads = (int64_t)n * 3 * oh * (vec ? ow / 4 : ow);
   if (vec) hipLaunchKernelGGL(crop_resize_kernel<true>, dim3(countr_blocks_for(threads, MAX_BLOCKS)), dim3(256), 0, STREAM(stream), img, a, out, n, h, w, oh, ow);
   else hipLaunchKernelGGL(crop_resize_kernel<false>, dim3(countr_blocks_for(threads, MAX_BLOCKS)), dim3(256), 0, STREAM(stream), img, a, out, n, h, w, oh, ow);
-  COUNTR_LAUNCH_CHECK("countr_crop_resize_f32");
+  return countr_check_launch("countr_crop_resize_f32");
 }

@@ -8,11 +8,7 @@
 //         compile-time variants staged through LDS into whole-row-segment stores.
 //   fp32: v_mfma_f32_16x16x4_f32 (exact f32 fma chain), register-staged padded tiles -- the parity mode.
 // Reference call sites: models_crossvit.py:62,65,84-92,115-127; models_mae_cross.py:47-100,138,152.
-#include "common.hpp"
-#include <type_traits>
-#include <utility>
-#include "../../include/countr_hip.h"
-#include <stdlib.h>
+#include "launch.hpp"
 
 // the kernel template lives in gemm_kernel.hpp; its instantiations in gemm_bf16_a.hip ((ROW, ROW), (ROW, COL), (COL, COL)),
 // gemm_bf16_b.hip ((COL, ROW), (IM2ROW, ROW), (COL, IM2COL)) and gemm_f32.hip (all six, parity mode).  1 = not one of mine.
@@ -146,8 +142,8 @@ __global__ void reduce_table_kernel(const long long* __restrict__ tab, int n) {
 
 extern "C" int countr_reduce_table(const long long* table, int n, int total_blocks, void* stream) {
   if (!table || n <= 0 || total_blocks <= 0) { countr_set_error("countr_reduce_table: bad args"); return -1; }
-  hipLaunchKernelGGL(reduce_table_kernel, dim3((unsigned)total_blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), table, n);
-  COUNTR_LAUNCH_CHECK("countr_reduce_table");
+  launch(reduce_table_kernel, (unsigned)total_blocks, 256, stream, table, n);
+  return countr_check_launch("countr_reduce_table");
 }
 
 int countr_lean_linear(const countr_gemm_args* a, hipStream_t s);   // linear.hip: 1 = does not qualify
@@ -297,18 +293,17 @@ extern "C" int countr_splitk_finish(const float* partial, void* out, const float
                                     void* stream) {
   if (!partial || !out || splitk < 1 || M <= 0 || N <= 0 || (N & 3)) { countr_set_error("countr_splitk_finish: bad args (N % 4 == 0)"); return -1; }
   const int64_t MN4 = (int64_t)M * N / 4;
-  const dim3 grid((unsigned)((MN4 + 255) / 256));
-  if (out_bf16) hipLaunchKernelGGL(splitk_finish_kernel<bf16_t>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), partial, (bf16_t*)out, bias, splitk, MN4, N / 4);
-  else hipLaunchKernelGGL(splitk_finish_kernel<float>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), partial, (float*)out, bias, splitk, MN4, N / 4);
-  COUNTR_LAUNCH_CHECK("countr_splitk_finish");
+  by_dtype(out_bf16 ? COUNTR_BF16 : COUNTR_F32, [&](auto t) {
+    using T = decltype(t);
+    launch(splitk_finish_kernel<T>, (unsigned)((MN4 + 255) / 256), 256, stream, partial, ptr<T>(out), bias, splitk, MN4, N / 4);
+  });
+  return countr_check_launch("countr_splitk_finish");
 }
 
 extern "C" int countr_splitk_reduce(const float* partial, float* out, int splitk, int M, int N, int perm_taps,
                                     int accumulate, const float* rowsum_partial, float* rowsum_out, void* stream) {
   if (!partial || !out || splitk < 1 || (rowsum_partial && !rowsum_out)) { countr_set_error("countr_splitk_reduce: bad args"); return -1; }
   const int64_t MN = (int64_t)M * N;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((MN + 255) / 256)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), partial, out, splitk, MN, N, perm_taps, accumulate, rowsum_partial,
-                     rowsum_out, M);
-  COUNTR_LAUNCH_CHECK("countr_splitk_reduce");
+  launch(splitk_reduce_kernel, (unsigned)((MN + 255) / 256), 256, stream, partial, out, splitk, MN, N, perm_taps, accumulate, rowsum_partial, rowsum_out, M);
+  return countr_check_launch("countr_splitk_reduce");
 }

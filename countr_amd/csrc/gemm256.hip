@@ -18,9 +18,7 @@
 //     on the read), W rows read in the permuted order that makes a lane's 16 accumulator registers 16 consecutive output columns.
 //   * epilogue: fp32 accumulators -> LDS (two passes of 64 rows per wave) -> whole 128-byte row segments; bias, LayerNorm fold, GELU on the
 //     read-back side.
-#include "common.hpp"
-#include "../../include/countr_hip.h"
-#include <stdlib.h>
+#include "launch.hpp"
 #include <type_traits>
 #include <utility>
 
@@ -455,10 +453,8 @@ int launch_big(const BigArgs& a0, hipStream_t s) {
     attr_set = true;
   }
   hipLaunchKernelGGL((g256_kernel<CONV, EPI, LN>), dim3(a.launch_tiles + a.npf), dim3(512), LDS_BYTES, s, a);
-  COUNTR_LAUNCH_CHECK("countr_gemm(256x256 8-phase)");
+  return countr_check_launch("countr_gemm(256x256 8-phase)");
 }
-
-int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
 }  // namespace
 

@@ -1047,7 +1047,7 @@ int launch_variant(const countr_gemm_args& a, hipStream_t s) {
     attr_set = true;
   }
   hipLaunchKernelGGL((gemm_kernel<T, MA, MB, STAGES, WM, WN, TMW, NLD>), grid, dim3(64 * (WM * WN + NLD)), lds_bytes, s, a, 0);
-  COUNTR_LAUNCH_CHECK("countr_gemm");
+  return countr_check_launch("countr_gemm");
 }
 
 // Tile-shape / stage selection (bf16).  Bigger workgroup tiles re-use each staged operand for more MFMAs (the kernel is

@@ -18,9 +18,7 @@
 // Launch forms: <NLD = 4> 4 compute + 4 loader waves, 3-stage LDS ring, one workgroup per CU (grids of <= 256 tiles);
 //               <NLD = 0> 4 waves that stage and multiply, 2 stages, two workgroups per CU (bigger grids).
 // Reference call sites: models_crossvit.py:62,65 (Mlp), :84,92 (Attention qkv / proj), :115-127 (CrossAttention), models_mae_cross.py:152.
-#include "common.hpp"
-#include "../../include/countr_hip.h"
-#include <stdlib.h>
+#include "launch.hpp"
 #include <type_traits>
 #include <utility>
 
@@ -579,14 +577,14 @@ int launch_lin(const LinArgs& a0, hipStream_t s) {
   a.launch_tiles = ((a.M + BMt - 1) / BMt - a.tile_m0) * a.tilesN;
   a.npf = countr_prefetch_blocks(a.launch_tiles, a.pf, a.pf_bytes);
   hipLaunchKernelGGL((lin_kernel<WMB, NLD, EPI, STAGES, CONV, WNB, LN, TM>), dim3(a.launch_tiles + a.npf), dim3(256 * WMB * WNB + 64 * NLD), lds, s, a);
-  COUNTR_LAUNCH_CHECK("countr_gemm(lean linear)");
+  return countr_check_launch("countr_gemm(lean linear)");
 }
 
 }  // namespace
 
 // Returns 1 when the launch does not qualify (the caller then uses gemm_kernel), otherwise the launch status (0 / < 0).
 int countr_lean_linear(const countr_gemm_args* a, hipStream_t s) {
-  { const char* e = getenv("COUNTR_LEAN"); if (e && atoi(e) == 0) return 1; }   // read per call: A/B inside one process (not on a replay path)
+  if (!env_int("COUNTR_LEAN", 1)) return 1;   // unset means on; read per call: A/B inside one process (not on a replay path)
   if (a->partial || a->nbatch > 1 || a->alpha != 1.0f || a->rowsum_partial) return 1;
   if (a->M < 1 || (a->N % 128) || (a->K % 64) || a->K < 128) return 1;      // any M: rows beyond it stage zeros and are not stored
   if ((a->lda % 8) || (a->ldb % 8) || (((uintptr_t)a->A | (uintptr_t)a->B | (uintptr_t)a->C | (uintptr_t)a->C2) & 15)) return 1;
@@ -677,8 +675,7 @@ int countr_lean_conv_rows(const countr_gemm_args* a, hipStream_t s, int row0);
 int countr_lean_conv(const countr_gemm_args* a, hipStream_t s) { return countr_lean_conv_rows(a, s, 0); }
 
 int countr_lean_conv_rows(const countr_gemm_args* a, hipStream_t s, int row0) {
-  { const char* e = getenv("COUNTR_LEAN"); if (e && atoi(e) == 0) return 1; }
-  { const char* e = getenv("COUNTR_LEAN_CONV"); if (e && atoi(e) == 0) return 1; }
+  if (!env_int("COUNTR_LEAN", 1) || !env_int("COUNTR_LEAN_CONV", 1)) return 1;
   if (row0 < 0 || (row0 % 128) || row0 >= a->M || (row0 > 0 && (a->N % 256))) return 1;
 #ifndef LIN_STAMP
   if (a->C2) return 1;

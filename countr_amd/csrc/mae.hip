@@ -1,7 +1,6 @@
 // MAE-pretraining specific kernels (reference models_mae_noct.py): row gather used for random masking / unshuffle and
 // their backward (:110-135, :163-170), and the all-patch pixel MSE with on-the-fly patchify (:84-96, :181-198).
-#include "common.hpp"
-#include "../../include/countr_hip.h"
+#include "launch.hpp"
 
 namespace {
 
@@ -123,24 +122,22 @@ extern "C" int countr_mae_indices(const long long* ids_shuffle, long long* ids_r
   if (!ids_shuffle || !ids_restore || !keep_pos || !keep_src || !restore_src || !mask || B < 1 || N < 1 || K < 1 || K > N || (K < N && !mask_src)) {
     countr_set_error("countr_mae_indices: bad args"); return -1;
   }
-  hipLaunchKernelGGL(mae_indices_kernel, dim3((B * N + 255) / 256), dim3(256), 0, STREAM(stream), ids_shuffle, ids_restore, keep_pos,
-                     keep_src, restore_src, mask_src, mask, B, N, K);
-  COUNTR_LAUNCH_CHECK("countr_mae_indices");
+  launch(mae_indices_kernel, (B * N + 255) / 256, 256, stream, ids_shuffle, ids_restore, keep_pos, keep_src, restore_src, mask_src, mask, B, N, K);
+  return countr_check_launch("countr_mae_indices");
 }
 
 extern "C" int countr_gather_rows(const void* src, const int* idx, void* dst, const float* default_row, const float* add, int add_mod,
                                   int rows, int cols, int src_dtype, int dst_dtype, void* stream) {
   if (!src || !dst || rows < 1 || cols < 4 || (cols & 3)) { countr_set_error("countr_gather_rows: null pointer or cols not a multiple of 4"); return -1; }
-  const int64_t total = (int64_t)rows * (cols / 4);
-  int nb = (int)((total + 255) / 256);
-  if (nb > 8192) nb = 8192;
-#define GR(TS, TD) hipLaunchKernelGGL((gather_rows_kernel<TS, TD>), dim3(nb), dim3(256), 0, STREAM(stream), (const TS*)src, idx, (TD*)dst, default_row, add, add_mod, rows, cols)
-  if (src_dtype == COUNTR_BF16 && dst_dtype == COUNTR_BF16) GR(bf16_t, bf16_t);
-  else if (src_dtype == COUNTR_BF16) GR(bf16_t, float);
-  else if (dst_dtype == COUNTR_BF16) GR(float, bf16_t);
-  else GR(float, float);
-#undef GR
-  COUNTR_LAUNCH_CHECK("countr_gather_rows");
+  const int nb = countr_blocks_for((int64_t)rows * (cols / 4), 8192);
+  by_dtype(src_dtype, [&](auto s) {
+    by_dtype(dst_dtype, [&](auto d) {
+      using TS = decltype(s);
+      using TD = decltype(d);
+      launch(gather_rows_kernel<TS, TD>, nb, 256, stream, ptr<TS>(src), idx, ptr<TD>(dst), default_row, add, add_mod, rows, cols);
+    });
+  });
+  return countr_check_launch("countr_gather_rows");
 }
 
 extern "C" int countr_patch_mse_workspace_floats(int B, int H, int W, int patch) { return B * (H / patch) * (W / patch); }
@@ -150,12 +147,12 @@ extern "C" int countr_patch_mse_amp(const float* pred, const float* imgs, void* 
     countr_set_error("countr_patch_mse: bad args (H, W multiples of patch; 3*patch^2 <= 1024)"); return -1;
   }
   const int rows = B * (H / patch) * (W / patch), F = 3 * patch * patch;
-  if (dpred_dtype == COUNTR_BF16)
-    hipLaunchKernelGGL(patch_mse_kernel<bf16_t>, dim3(rows), dim3(256), 0, STREAM(stream), pred, imgs, (bf16_t*)dpred, workspace, rows, H, W, patch, norm_pix, grad_scale, amp);
-  else
-    hipLaunchKernelGGL(patch_mse_kernel<float>, dim3(rows), dim3(256), 0, STREAM(stream), pred, imgs, (float*)dpred, workspace, rows, H, W, patch, norm_pix, grad_scale, amp);
-  hipLaunchKernelGGL(patch_mse_finish_kernel, dim3(1), dim3(256), 0, STREAM(stream), workspace, loss, rows, 1.f / ((float)F * (float)rows));
-  COUNTR_LAUNCH_CHECK("countr_patch_mse");
+  by_dtype(dpred_dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(patch_mse_kernel<T>, rows, 256, stream, pred, imgs, ptr<T>(dpred), workspace, rows, H, W, patch, norm_pix, grad_scale, amp);
+  });
+  launch(patch_mse_finish_kernel, 1, 256, stream, workspace, loss, rows, 1.f / ((float)F * (float)rows));
+  return countr_check_launch("countr_patch_mse");
 }
 extern "C" int countr_patch_mse(const float* pred, const float* imgs, void* dpred, float* loss, float* workspace, int B, int H, int W,
                                 int patch, int norm_pix, float grad_scale, int dpred_dtype, void* stream) {

@@ -119,5 +119,5 @@ extern "C" int countr_match_points(const countr_match_set* sets, int n, int* mat
   unsigned short* best = (unsigned short*)workspace;
   hipLaunchKernelGGL(match_init_kernel, dim3(INIT_BLOCKS, n), dim3(256), 0, STREAM(stream), a, best, match, match_d2);
   hipLaunchKernelGGL(match_rounds_kernel, dim3(n), dim3(ROUND_THREADS), 0, STREAM(stream), a, best, match, match_d2, counts);
-  COUNTR_LAUNCH_CHECK("countr_match_points");
+  return countr_check_launch("countr_match_points");
 }

@@ -130,5 +130,5 @@ extern "C" int countr_aug_mosaic(const countr_mosaic_image* imgs, int n, float* 
   }
   const int blocks = n * 3 * (OUT / 8) * (OUT / 4 / QW);
   hipLaunchKernelGGL(mosaic_kernel, dim3(blocks < 2048 ? blocks : 2048), dim3(256), 0, STREAM(stream), a, out, n);
-  COUNTR_LAUNCH_CHECK("countr_aug_mosaic");
+  return countr_check_launch("countr_aug_mosaic");
 }

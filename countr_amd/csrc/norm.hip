@@ -2,9 +2,8 @@
 //   LayerNorm fwd/bwd      : nn.LayerNorm(eps=1e-6)          models_mae_cross.py:146,182; models_crossvit.py:153-155
 //   GroupNorm(8)+ReLU      : decode_head*                     models_mae_cross.py:80-100   (NHWC maps)
 //   InstanceNorm+ReLU+pool : decoder_proj1-4                  models_mae_cross.py:47-71    (NHWC maps)
-#include "common.hpp"
-#include <stdlib.h>
-#include "../../include/countr_hip.h"
+#include "launch.hpp"
+#include <type_traits>
 
 namespace {
 
@@ -1017,10 +1016,9 @@ __global__ __launch_bounds__(256) void in_bwd_split_kernel(const T* __restrict__
 extern "C" int countr_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y, float* mean,
                                     float* rstd, int rows, int D, float eps, int out_bf16, void* stream) {
   if (!x || !gamma || !beta || !y || D % 4 || D > 2048 || rows <= 0) { countr_set_error("countr_layernorm_fwd: bad args (need D % 4 == 0, D <= 2048)"); return -1; }
-  dim3 grid((rows + 3) / 4), block(256);
-  if (out_bf16) hipLaunchKernelGGL(layernorm_fwd_kernel<bf16_t>, grid, block, 0, STREAM(stream), x, gamma, beta, (bf16_t*)y, mean, rstd, rows, D, eps);
-  else hipLaunchKernelGGL(layernorm_fwd_kernel<float>, grid, block, 0, STREAM(stream), x, gamma, beta, (float*)y, mean, rstd, rows, D, eps);
-  COUNTR_LAUNCH_CHECK("countr_layernorm_fwd");
+  by_dtype(out_bf16 ? COUNTR_BF16 : COUNTR_F32,
+           [&](auto t) { using T = decltype(t); launch(layernorm_fwd_kernel<T>, (rows + 3) / 4, 256, stream, x, gamma, beta, ptr<T>(y), mean, rstd, rows, D, eps); });
+  return countr_check_launch("countr_layernorm_fwd");
 }
 
 extern "C" int countr_layernorm_bwd_nblocks(void) { return 256; }
@@ -1031,37 +1029,39 @@ extern "C" int countr_layernorm_bwd(const void* dy, const float* x, const float*
   if (!dy || !x || !gamma || !mean || !rstd || !dx || !workspace || D % 4 || D > 2048) { countr_set_error("countr_layernorm_bwd: bad args"); return -1; }
   const int nb = countr_layernorm_bwd_nblocks();
   const size_t lds = (size_t)LNB_WAVES * 2 * D * sizeof(float);
-#define COUNTR_LNB_LAUNCH(TI, MV)                                                                                                          \
-  {                                                                                                                                        \
-    static bool attr_set = false;   /* D > 1024 needs more than the default 64 KiB of dynamic LDS */                                       \
-    if (!attr_set) {                                                                                                                       \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&layernorm_bwd_kernel<TI, MV>), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                LNB_WAVES * 2 * 256 * MV * 4);                                                                             \
-      attr_set = true;                                                                                                                     \
-    }                                                                                                                                      \
-    hipLaunchKernelGGL((layernorm_bwd_kernel<TI, MV>), dim3(nb), dim3(64 * LNB_WAVES), lds, STREAM(stream), (const TI*)dy, x, gamma, mean,  \
-                       rstd, dx, (bf16_t*)dx_bf16, workspace, rows, D, accumulate_dx);                                                     \
-  }
-#define COUNTR_LNB_BY_D(TI)                                                        \
-  if (D <= 512) COUNTR_LNB_LAUNCH(TI, 2) else if (D <= 768) COUNTR_LNB_LAUNCH(TI, 3) \
-  else if (D <= 1024) COUNTR_LNB_LAUNCH(TI, 4) else COUNTR_LNB_LAUNCH(TI, 8)
-  if (dy_bf16) { COUNTR_LNB_BY_D(bf16_t) } else { COUNTR_LNB_BY_D(float) }
-#undef COUNTR_LNB_BY_D
-#undef COUNTR_LNB_LAUNCH
+  by_dtype(dy_bf16 ? COUNTR_BF16 : COUNTR_F32, [&](auto t) {
+    using TI = decltype(t);
+    auto run = [&](auto maxv) {
+      constexpr int MV = decltype(maxv)::value;
+      // (a static of a generic lambda is one flag per instantiation: one per (TI, MV), as the attribute is one per kernel)
+      static bool attr_set = false;   // D > 1024 needs more than the default 64 KiB of dynamic LDS
+      if (!attr_set) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&layernorm_bwd_kernel<TI, MV>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  LNB_WAVES * 2 * 256 * MV * 4);
+        attr_set = true;
+      }
+      launch_lds(layernorm_bwd_kernel<TI, MV>, nb, 64 * LNB_WAVES, lds, stream, ptr<TI>(dy), x, gamma, mean, rstd, dx, ptr<bf16_t>(dx_bf16),
+                 workspace, rows, D, accumulate_dx);
+    };
+    if (D <= 512) run(std::integral_constant<int, 2>{});
+    else if (D <= 768) run(std::integral_constant<int, 3>{});
+    else if (D <= 1024) run(std::integral_constant<int, 4>{});
+    else run(std::integral_constant<int, 8>{});
+  });
   // workspace rows are {dgamma[D], dbeta[D]} per block; adjacent outputs (the flat gradient buffer) finish in one launch
   if (dgamma && dbeta == dgamma + D) {
-    hipLaunchKernelGGL(colsum_partials_kernel, dim3((2 * D + 15) / 16), dim3(256), 0, STREAM(stream), workspace, dgamma, nb, 2 * D, (int64_t)2 * D, accumulate_dgb);
-    COUNTR_LAUNCH_CHECK("countr_layernorm_bwd");
+    launch(colsum_partials_kernel, (2 * D + 15) / 16, 256, stream, workspace, dgamma, nb, 2 * D, (int64_t)2 * D, accumulate_dgb);
+    return countr_check_launch("countr_layernorm_bwd");
   }
-  if (dgamma) hipLaunchKernelGGL(colsum_partials_kernel, dim3((D + 15) / 16), dim3(256), 0, STREAM(stream), workspace, dgamma, nb, D, (int64_t)2 * D, accumulate_dgb);
-  if (dbeta) hipLaunchKernelGGL(colsum_partials_kernel, dim3((D + 15) / 16), dim3(256), 0, STREAM(stream), workspace + D, dbeta, nb, D, (int64_t)2 * D, accumulate_dgb);
-  COUNTR_LAUNCH_CHECK("countr_layernorm_bwd");
+  if (dgamma) launch(colsum_partials_kernel, (D + 15) / 16, 256, stream, workspace, dgamma, nb, D, (int64_t)2 * D, accumulate_dgb);
+  if (dbeta) launch(colsum_partials_kernel, (D + 15) / 16, 256, stream, workspace + D, dbeta, nb, D, (int64_t)2 * D, accumulate_dgb);
+  return countr_check_launch("countr_layernorm_bwd");
 }
 
 extern "C" int countr_colsum_partials(const float* partial, float* out, int nparts, int C, int accumulate, void* stream) {
   if (!partial || !out) { countr_set_error("countr_colsum_partials: null"); return -1; }
-  hipLaunchKernelGGL(colsum_partials_kernel, dim3((C + 15) / 16), dim3(256), 0, STREAM(stream), partial, out, nparts, C, (int64_t)C, accumulate);
-  COUNTR_LAUNCH_CHECK("countr_colsum_partials");
+  launch(colsum_partials_kernel, (C + 15) / 16, 256, stream, partial, out, nparts, C, (int64_t)C, accumulate);
+  return countr_check_launch("countr_colsum_partials");
 }
 
 // pixel splits of the GroupNorm statistics / backward reductions: enough blocks to hide the cold-miss latency of the small
@@ -1093,18 +1093,19 @@ static int groupnorm_relu_fwd(const void* x, const float* rows, const float* gam
   if (rows && (G != 8 || dtype != COUNTR_BF16 || ((uintptr_t)rows & 7))) { countr_set_error("countr_groupnorm_relu_fwd_rows: row partials are those of 8 groups of 32 channels in a 16-bit map"); return -1; }
   const int ns = gn_splits_fwd(HW);
   const int nblk = min((HW + 7) / 8, 512);
-  if (dtype == COUNTR_BF16) {
-    if (rows) hipLaunchKernelGGL(gn_stats_rows_kernel, dim3(ns, B), dim3(256), 0, STREAM(stream), rows, workspace, HW);
-    else if (G == 8) hipLaunchKernelGGL(gn_stats_tree_kernel<bf16_t>, dim3(ns, B), dim3(256), 0, STREAM(stream), (const bf16_t*)x, workspace, HW);
-    else hipLaunchKernelGGL(gn_stats_kernel<bf16_t>, dim3(ns, B), dim3(256), 0, STREAM(stream), (const bf16_t*)x, workspace, HW, G);
-    hipLaunchKernelGGL(gn_stats_finalize_kernel, dim3(B), dim3(64 * G), 0, STREAM(stream), workspace, stats, HW, G, ns, eps);
-    hipLaunchKernelGGL(gn_relu_fwd_kernel<bf16_t>, dim3(nblk, B), dim3(256), 0, STREAM(stream), (const bf16_t*)x, workspace, gamma, beta, (bf16_t*)y, w1, b1, out1, stats, HW, G, ns, eps);
-  } else {
-    hipLaunchKernelGGL(gn_stats_kernel<float>, dim3(ns, B), dim3(256), 0, STREAM(stream), (const float*)x, workspace, HW, G);
-    hipLaunchKernelGGL(gn_stats_finalize_kernel, dim3(B), dim3(64 * G), 0, STREAM(stream), workspace, stats, HW, G, ns, eps);
-    hipLaunchKernelGGL(gn_relu_fwd_kernel<float>, dim3(nblk, B), dim3(256), 0, STREAM(stream), (const float*)x, workspace, gamma, beta, (float*)y, w1, b1, out1, stats, HW, G, ns, eps);
-  }
-  COUNTR_LAUNCH_CHECK(who);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if constexpr (sizeof(T) == 2) {      // the 16-bit maps have two more statistics passes: from the row partials, and the tree of 8 groups
+      if (rows) launch(gn_stats_rows_kernel, dim3(ns, B), 256, stream, rows, workspace, HW);
+      else if (G == 8) launch(gn_stats_tree_kernel<T>, dim3(ns, B), 256, stream, ptr<T>(x), workspace, HW);
+      else launch(gn_stats_kernel<T>, dim3(ns, B), 256, stream, ptr<T>(x), workspace, HW, G);
+    } else {
+      launch(gn_stats_kernel<T>, dim3(ns, B), 256, stream, ptr<T>(x), workspace, HW, G);
+    }
+    launch(gn_stats_finalize_kernel, B, 64 * G, stream, workspace, stats, HW, G, ns, eps);
+    launch(gn_relu_fwd_kernel<T>, dim3(nblk, B), 256, stream, ptr<T>(x), workspace, gamma, beta, ptr<T>(y), w1, b1, out1, stats, HW, G, ns, eps);
+  });
+  return countr_check_launch(who);
 }
 
 extern "C" int countr_groupnorm_relu_fwd(const void* x, const float* gamma, const float* beta, void* y, const float* w1,
@@ -1132,33 +1133,34 @@ extern "C" int countr_groupnorm_relu_bwd(const void* x, const void* dy, const fl
   float* gmean = workspace + (int64_t)B * ns * 3 * GN_C + 64;  // [B][G][2] behind the partials and the d1 sums
   float* per_image = gmean + 16 * B;                           // [B][3][C] behind that (countr_groupnorm_bwd_image_sums_offset)
   if (G != 8) { countr_set_error("countr_groupnorm_relu_bwd: G must be 8"); return -1; }
-  if (dtype == COUNTR_BF16) {
-    // threads per block of the reduction pass: 512 (16 pixel slots) keeps more loads in flight per CU than 256 (96x96: 31.6 -> 20.8 us,
-    // 48x48 and 24x24: 17.4 -> 11.6 us); 1024 falls off a cliff (step +230 us: 128-VGPR budget)
-    const int nt = w1 ? 256 : 512;   // (the fused-head form -- 192x192, x only -- is better off with 256: 41.4 vs 44.4 us)
-    if (nt == 512) hipLaunchKernelGGL((gn_relu_bwd_reduce_kernel<bf16_t, 512>), dim3(ns, B), dim3(512), 0, STREAM(stream), (const bf16_t*)x, (const bf16_t*)dy, d1, w1, stats, gamma, beta, workspace, HW, G);
-    else if (d1 && w1) hipLaunchKernelGGL((gn_relu_bwd_reduce_kernel<bf16_t, 256, true>), dim3(ns, B), dim3(256), 0, STREAM(stream), (const bf16_t*)x, (const bf16_t*)dy, d1, w1, stats, gamma, beta, workspace, HW, G);
-    else hipLaunchKernelGGL((gn_relu_bwd_reduce_kernel<bf16_t, 256>), dim3(ns, B), dim3(256), 0, STREAM(stream), (const bf16_t*)x, (const bf16_t*)dy, d1, w1, stats, gamma, beta, workspace, HW, G);
-    hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(B), dim3(256), 0, STREAM(stream), workspace, gamma, gmean, per_image, HW, G, ns);
-    hipLaunchKernelGGL(gn_relu_bwd_apply_kernel<bf16_t>, dim3(nblk, B), dim3(256), 0, STREAM(stream), (const bf16_t*)x, (const bf16_t*)dy, d1, w1, stats, gamma, beta, gmean, (bf16_t*)dx, HW, G, ns);
-  } else {
-    hipLaunchKernelGGL((gn_relu_bwd_reduce_kernel<float, 256>), dim3(ns, B), dim3(256), 0, STREAM(stream), (const float*)x, (const float*)dy, d1, w1, stats, gamma, beta, workspace, HW, G);
-    hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(B), dim3(256), 0, STREAM(stream), workspace, gamma, gmean, per_image, HW, G, ns);
-    hipLaunchKernelGGL(gn_relu_bwd_apply_kernel<float>, dim3(nblk, B), dim3(256), 0, STREAM(stream), (const float*)x, (const float*)dy, d1, w1, stats, gamma, beta, gmean, (float*)dx, HW, G, ns);
-  }
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const dim3 grid(ns, B);
+    if constexpr (sizeof(T) == 2) {
+      // threads per block of the reduction pass: 512 (16 pixel slots) keeps more loads in flight per CU than 256 (96x96: 31.6 -> 20.8 us,
+      // 48x48 and 24x24: 17.4 -> 11.6 us); 1024 falls off a cliff (step +230 us: 128-VGPR budget)
+      const int nt = w1 ? 256 : 512;   // (the fused-head form -- 192x192, x only -- is better off with 256: 41.4 vs 44.4 us)
+      if (nt == 512) launch(gn_relu_bwd_reduce_kernel<T, 512>, grid, 512, stream, ptr<T>(x), ptr<T>(dy), d1, w1, stats, gamma, beta, workspace, HW, G);
+      else if (d1 && w1) launch(gn_relu_bwd_reduce_kernel<T, 256, true>, grid, 256, stream, ptr<T>(x), ptr<T>(dy), d1, w1, stats, gamma, beta, workspace, HW, G);
+      else launch(gn_relu_bwd_reduce_kernel<T, 256>, grid, 256, stream, ptr<T>(x), ptr<T>(dy), d1, w1, stats, gamma, beta, workspace, HW, G);
+    } else {
+      launch(gn_relu_bwd_reduce_kernel<T, 256>, grid, 256, stream, ptr<T>(x), ptr<T>(dy), d1, w1, stats, gamma, beta, workspace, HW, G);
+    }
+    launch(gn_bwd_finalize_kernel, B, 256, stream, workspace, gamma, gmean, per_image, HW, G, ns);
+    launch(gn_relu_bwd_apply_kernel<T>, dim3(nblk, B), 256, stream, ptr<T>(x), ptr<T>(dy), d1, w1, stats, gamma, beta, gmean, ptr<T>(dx), HW, G, ns);
+  });
   // parameter gradients: partial[p] = {sum g (dbeta) [C], sum g*xhat (dgamma) [C], sum d1*y (dw1) [C]}
   float* outs[3] = {dbeta, dgamma, dw1};
   for (int i = 0; i < 3; ++i) {
     if (!outs[i]) continue;
-    hipLaunchKernelGGL(colsum_partials_kernel, dim3(GN_C / 16), dim3(256), 0, STREAM(stream), per_image + i * GN_C, outs[i], B, GN_C,
-                       (int64_t)3 * GN_C, accumulate);
+    launch(colsum_partials_kernel, GN_C / 16, 256, stream, per_image + i * GN_C, outs[i], B, GN_C, (int64_t)3 * GN_C, accumulate);
   }
   if (db1 && d1) {  // the reduce/apply kernels are done with the first 64 floats of row 0's third plane only via dw1: use the tail
     float* part = workspace + (int64_t)B * ns * 3 * GN_C;  // 64 extra floats behind the partials
-    hipLaunchKernelGGL(sum_all_kernel, dim3(64), dim3(256), 0, STREAM(stream), d1, (int64_t)B * HW, part);
-    hipLaunchKernelGGL(colsum_partials_kernel, dim3(1), dim3(256), 0, STREAM(stream), part, db1, 64, 1, (int64_t)1, accumulate);
+    launch(sum_all_kernel, 64, 256, stream, d1, (int64_t)B * HW, part);
+    launch(colsum_partials_kernel, 1, 256, stream, part, db1, 64, 1, (int64_t)1, accumulate);
   }
-  COUNTR_LAUNCH_CHECK("countr_groupnorm_relu_bwd");
+  return countr_check_launch("countr_groupnorm_relu_bwd");
 }
 
 // bands of pooled rows for the split path (0 = one-kernel path): only for the big maps whose (C/64) x S blocks cannot fill the chip
@@ -1177,25 +1179,31 @@ extern "C" int countr_instnorm_relu_pool_fwd(const void* x, void* y, float* stat
   if (!x || !y || C % 64 || (H & 1) || (W & 1)) { countr_set_error("countr_instnorm_relu_pool_fwd: bad args (C % 64, even H/W)"); return -1; }
   if (x_f32 && dtype == COUNTR_BF16 && xhat_out == x) { countr_set_error("countr_instnorm_relu_pool_fwd: a bf16 x-hat cannot be stored in place of an fp32 map"); return -1; }
   const int ns = workspace ? in_splits(S, H, C, avgpool) : 0;
+  const bool mixed = dtype == COUNTR_BF16 && x_f32;      // an fp32 map into a 16-bit result: the one form whose input type is not the output's
   if (ns) {
-    dim3 grid(C / 64, S, ns), block(256);
-    if (dtype == COUNTR_BF16 && x_f32) {
-      hipLaunchKernelGGL(in_stats_split_kernel<float>, grid, block, 0, STREAM(stream), (const float*)x, workspace, H, W, C);
-      hipLaunchKernelGGL((in_apply_split_kernel<bf16_t, float>), grid, block, 0, STREAM(stream), (const float*)x, workspace, (bf16_t*)y, stats, H, W, C, eps, (bf16_t*)xhat_out);
-    } else if (dtype == COUNTR_BF16) {
-      hipLaunchKernelGGL(in_stats_split_kernel<bf16_t>, grid, block, 0, STREAM(stream), (const bf16_t*)x, workspace, H, W, C);
-      hipLaunchKernelGGL(in_apply_split_kernel<bf16_t>, grid, block, 0, STREAM(stream), (const bf16_t*)x, workspace, (bf16_t*)y, stats, H, W, C, eps, (bf16_t*)xhat_out);
+    const dim3 grid(C / 64, S, ns);
+    if (mixed) {
+      launch(in_stats_split_kernel<float>, grid, 256, stream, ptr<float>(x), workspace, H, W, C);
+      launch(in_apply_split_kernel<bf16_t, float>, grid, 256, stream, ptr<float>(x), workspace, ptr<bf16_t>(y), stats, H, W, C, eps, ptr<bf16_t>(xhat_out));
     } else {
-      hipLaunchKernelGGL(in_stats_split_kernel<float>, grid, block, 0, STREAM(stream), (const float*)x, workspace, H, W, C);
-      hipLaunchKernelGGL(in_apply_split_kernel<float>, grid, block, 0, STREAM(stream), (const float*)x, workspace, (float*)y, stats, H, W, C, eps, (float*)xhat_out);
+      by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        launch(in_stats_split_kernel<T>, grid, 256, stream, ptr<T>(x), workspace, H, W, C);
+        launch(in_apply_split_kernel<T>, grid, 256, stream, ptr<T>(x), workspace, ptr<T>(y), stats, H, W, C, eps, ptr<T>(xhat_out));
+      });
     }
-    COUNTR_LAUNCH_CHECK("countr_instnorm_relu_pool_fwd");
+    return countr_check_launch("countr_instnorm_relu_pool_fwd");
   }
-  dim3 grid(C / 64, S), block(256);
-  if (dtype == COUNTR_BF16 && x_f32) hipLaunchKernelGGL((in_relu_pool_fwd_kernel<bf16_t, 8, float>), grid, block, 0, STREAM(stream), (const float*)x, (bf16_t*)y, stats, H, W, C, avgpool, eps, (bf16_t*)xhat_out);
-  else if (dtype == COUNTR_BF16) hipLaunchKernelGGL((in_relu_pool_fwd_kernel<bf16_t, 8>), grid, block, 0, STREAM(stream), (const bf16_t*)x, (bf16_t*)y, stats, H, W, C, avgpool, eps, (bf16_t*)xhat_out);
-  else hipLaunchKernelGGL((in_relu_pool_fwd_kernel<float, 8>), grid, block, 0, STREAM(stream), (const float*)x, (float*)y, stats, H, W, C, avgpool, eps, (float*)xhat_out);
-  COUNTR_LAUNCH_CHECK("countr_instnorm_relu_pool_fwd");
+  const dim3 grid(C / 64, S);
+  if (mixed) {
+    launch(in_relu_pool_fwd_kernel<bf16_t, 8, float>, grid, 256, stream, ptr<float>(x), ptr<bf16_t>(y), stats, H, W, C, avgpool, eps, ptr<bf16_t>(xhat_out));
+    return countr_check_launch("countr_instnorm_relu_pool_fwd");
+  }
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(in_relu_pool_fwd_kernel<T, 8>, grid, 256, stream, ptr<T>(x), ptr<T>(y), stats, H, W, C, avgpool, eps, ptr<T>(xhat_out));
+  });
+  return countr_check_launch("countr_instnorm_relu_pool_fwd");
 }
 
 extern "C" int countr_instnorm_relu_pool_bwd(const void* x, const void* dyp, const float* stats, void* dx, int S, int H, int W,
@@ -1203,18 +1211,17 @@ extern "C" int countr_instnorm_relu_pool_bwd(const void* x, const void* dyp, con
   if (!x || !dyp || !stats || !dx || C % 64) { countr_set_error("countr_instnorm_relu_pool_bwd: bad args"); return -1; }
   const int ns = workspace ? in_splits(S, H, C, avgpool) : 0;
   if (ns) {
-    dim3 grid(C / 64, S, ns), block(256);
-    if (dtype == COUNTR_BF16) {
-      hipLaunchKernelGGL((in_bwd_split_kernel<bf16_t, false>), grid, block, 0, STREAM(stream), (const bf16_t*)x, (const bf16_t*)dyp, stats, workspace, (bf16_t*)dx, H, W, C, x_is_xhat);
-      hipLaunchKernelGGL((in_bwd_split_kernel<bf16_t, true>), grid, block, 0, STREAM(stream), (const bf16_t*)x, (const bf16_t*)dyp, stats, workspace, (bf16_t*)dx, H, W, C, x_is_xhat);
-    } else {
-      hipLaunchKernelGGL((in_bwd_split_kernel<float, false>), grid, block, 0, STREAM(stream), (const float*)x, (const float*)dyp, stats, workspace, (float*)dx, H, W, C, x_is_xhat);
-      hipLaunchKernelGGL((in_bwd_split_kernel<float, true>), grid, block, 0, STREAM(stream), (const float*)x, (const float*)dyp, stats, workspace, (float*)dx, H, W, C, x_is_xhat);
-    }
-    COUNTR_LAUNCH_CHECK("countr_instnorm_relu_pool_bwd");
+    by_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      const dim3 grid(C / 64, S, ns);
+      launch(in_bwd_split_kernel<T, false>, grid, 256, stream, ptr<T>(x), ptr<T>(dyp), stats, workspace, ptr<T>(dx), H, W, C, x_is_xhat);
+      launch(in_bwd_split_kernel<T, true>, grid, 256, stream, ptr<T>(x), ptr<T>(dyp), stats, workspace, ptr<T>(dx), H, W, C, x_is_xhat);
+    });
+    return countr_check_launch("countr_instnorm_relu_pool_bwd");
   }
-  dim3 grid(C / 64, S), block(256);
-  if (dtype == COUNTR_BF16) hipLaunchKernelGGL((in_relu_pool_bwd_kernel<bf16_t, 8>), grid, block, 0, STREAM(stream), (const bf16_t*)x, (const bf16_t*)dyp, stats, (bf16_t*)dx, H, W, C, avgpool, x_is_xhat);
-  else hipLaunchKernelGGL((in_relu_pool_bwd_kernel<float, 8>), grid, block, 0, STREAM(stream), (const float*)x, (const float*)dyp, stats, (float*)dx, H, W, C, avgpool, x_is_xhat);
-  COUNTR_LAUNCH_CHECK("countr_instnorm_relu_pool_bwd");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    launch(in_relu_pool_bwd_kernel<T, 8>, dim3(C / 64, S), 256, stream, ptr<T>(x), ptr<T>(dyp), stats, ptr<T>(dx), H, W, C, avgpool, x_is_xhat);
+  });
+  return countr_check_launch("countr_instnorm_relu_pool_bwd");
 }

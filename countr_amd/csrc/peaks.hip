@@ -254,5 +254,5 @@ extern "C" int countr_density_peaks(const countr_peak_map* maps, int n, int radi
   hipLaunchKernelGGL(peaks_detect_kernel, dim3((unsigned)tiles), dim3(256), 0, STREAM(stream), a, parts, masks, n, radius, threshold, rel_threshold);
   hipLaunchKernelGGL(peaks_write_kernel, dim3(WRITE_BLOCKS, n), dim3(256), 0, STREAM(stream), a, masks, totals, raw, radius, cap);
   hipLaunchKernelGGL(peaks_rank_kernel, dim3((cap + 255) / 256, n), dim3(256), 0, STREAM(stream), totals, raw, recs, cap);
-  COUNTR_LAUNCH_CHECK("countr_density_peaks");
+  return countr_check_launch("countr_density_peaks");
 }

@@ -239,7 +239,7 @@ extern "C" int countr_pretrain_aug_tables(const countr_pretrain_image* imgs, int
     }
   }
   hipLaunchKernelGGL(tables_kernel, dim3(countr_blocks_for(a.rows, MAX_BLOCKS)), dim3(256), 0, STREAM(stream), a, tables);
-  COUNTR_LAUNCH_CHECK("countr_pretrain_aug_tables");
+  return countr_check_launch("countr_pretrain_aug_tables");
 }
 
 extern "C" int countr_pretrain_aug(const countr_pretrain_image* imgs, int n, const int* tables, void* workspace, float* out, int out_rows,
@@ -308,5 +308,5 @@ extern "C" int countr_pretrain_aug(const countr_pretrain_image* imgs, int n, con
   hipLaunchKernelGGL(vpass_u8_kernel, dim3(countr_blocks_for(v1.total, MAX_BLOCKS)), dim3(256), 0, STREAM(stream), v1, tables);
   hipLaunchKernelGGL(hpass_kernel, dim3(max(1, min(MAX_BLOCKS, h2.items))), dim3(256), 0, STREAM(stream), h2, tables);
   hipLaunchKernelGGL(vpass_f32_kernel, dim3(countr_blocks_for((int64_t)n * OUT * (OUT / 4), MAX_BLOCKS)), dim3(256), 0, STREAM(stream), f, tables, out);
-  COUNTR_LAUNCH_CHECK(fn);
+  return countr_check_launch(fn);
 }

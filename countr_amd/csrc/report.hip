@@ -261,7 +261,7 @@ extern "C" int countr_report_panels(const countr_report_image* imgs, int n, int 
   const int blocks = countr_blocks_for(items, MAX_BLOCKS);
   const uint8_t* b8 = (const uint8_t*)blob;
   hipLaunchKernelGGL(panels_kernel, dim3(blocks), dim3(256), 0, STREAM(stream), a, b8, (const int*)(b8 ? b8 + rects_off : nullptr), (uint8_t*)out);
-  COUNTR_LAUNCH_CHECK("countr_report_panels");
+  return countr_check_launch("countr_report_panels");
 }
 
 extern "C" int countr_report_strip_shape(int S, int eh, int ew, int* shape) {
@@ -297,5 +297,5 @@ extern "C" int countr_report_quantize(const countr_report_strip* strips, int n, 
   }
   a.items = items;
   hipLaunchKernelGGL(strips_kernel, dim3(countr_blocks_for(items, MAX_BLOCKS)), dim3(256), 0, STREAM(stream), a, (uint8_t*)out);
-  COUNTR_LAUNCH_CHECK("countr_report_quantize");
+  return countr_check_launch("countr_report_quantize");
 }

@@ -100,7 +100,7 @@ extern "C" int countr_window_gather(const void* const* frames, const int* widths
   const int blocks = (int)min((int64_t)65535, (total + 255) / 256);
   if (vec) hipLaunchKernelGGL(window_gather_kernel<true>, dim3(blocks), dim3(256), 0, STREAM(stream), a, wins, nw, H);
   else hipLaunchKernelGGL(window_gather_kernel<false>, dim3(blocks), dim3(256), 0, STREAM(stream), a, wins, nw, H);
-  COUNTR_LAUNCH_CHECK("countr_window_gather");
+  return countr_check_launch("countr_window_gather");
 }
 
 extern "C" int countr_window_blend(const float* outs, int n, int nwin, const int* starts, int H, int W, float* dm, float* sums, float* workspace,
@@ -117,5 +117,5 @@ extern "C" int countr_window_blend(const float* outs, int n, int nwin, const int
   const int bpi = countr_window_blend_blocks(H, W);
   hipLaunchKernelGGL(window_blend_kernel, dim3(bpi, n), dim3(256), 0, STREAM(stream), outs, a, nwin, H, W, dm, sums ? workspace : nullptr, bpi);
   if (sums) hipLaunchKernelGGL(window_sum_kernel, dim3(n), dim3(64), 0, STREAM(stream), workspace, sums, bpi);
-  COUNTR_LAUNCH_CHECK("countr_window_blend");
+  return countr_check_launch("countr_window_blend");
 }
