@@ -4,7 +4,7 @@ build, the CPU tools) stays free of torch."""
 
 def __getattr__(name):
     if name in ("count_frames", "locate_frames", "count_regions", "count_classes", "ClassCounts", "FramePrep", "annotate_frames", "count_clip",
-                "count_flow"):
+                "count_flow", "annotate_clip"):
         from . import frames
         return getattr(frames, name)
     if name in ("flow_host", "FlowCounter", "FlowCounts", "blob_scene"):
@@ -16,6 +16,9 @@ def __getattr__(name):
     if name in ("Overlay", "overlay_host"):
         from . import overlay
         return getattr(overlay, name)
+    if name in ("draw_host", "Marks", "Painter", "Trails", "clip_marks", "track_color", "PALETTE"):
+        from . import draw
+        return getattr(draw, name)
     if name in ("tracks_host", "Tracker", "ClipCounts"):
         from . import tracks
         return getattr(tracks, name)

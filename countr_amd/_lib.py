@@ -6,7 +6,7 @@ import ctypes as C
 import os
 import re
 
-from .build import TAGS
+from .build import LATER_TAGS, TAGS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COUNTR_LIB", os.path.join(_HERE, "libcountr_hip.so"))
@@ -172,12 +172,15 @@ class Library:
 # tiles, 4:2:0 decoder surfaces to packed RGB, annotated frames, points joined into tracks, line counts from density flux, the camera's
 # motion from the flow field
 LIBRARIES = {tag: Library(tag) for tag in TAGS}
+# build.LATER_TAGS: the libraries that came after that table was closed, stated and bound by the same rule: marks drawn onto frames
+LATER_LIBRARIES = {tag: Library(tag) for tag in LATER_TAGS}
 # what the wrappers read: EXT_LIB_PATH, EXT_HEADER, EXT_CONSTS, EXT_STRUCTS, EXT_PROTOS, ext_lib(), ext_check(rc, what), ext_exported_symbols()
-# and the same for every other tag
-for _tag, _l in LIBRARIES.items():
+# and the same for every other tag, of either table
+for _tag, _l in list(LIBRARIES.items()) + list(LATER_LIBRARIES.items()):
     globals().update({_tag.upper() + "_LIB_PATH": _l.path, _tag.upper() + "_HEADER": _l.header, _tag.upper() + "_CONSTS": _l.consts,
                       _tag.upper() + "_STRUCTS": _l.structs, _tag.upper() + "_PROTOS": _l.protos, _tag + "_lib": _l.load,
                       _tag + "_check": _l.check, _tag + "_exported_symbols": _l.exported_symbols})
 RegionMap, Region = EXT_STRUCTS["countr_region_map"], EXT_STRUCTS["countr_region"]
 ClassSet, OverlayFrame = CLASSES_STRUCTS["countr_class_set"], OVERLAY_STRUCTS["countr_overlay_frame"]
 TracksStream, FlowMap = TRACKS_STRUCTS["countr_tracks_stream"], FLOW_STRUCTS["countr_flow_map"]
+DrawFrame = DRAW_STRUCTS["countr_draw_frame"]

@@ -1,4 +1,4 @@
-"""Build libcountr_hip.so (all HIP kernels + the C ABI) and the side libraries libcountr_hip_<tag>.so (SINGLE below) in-tree for gfx950.
+"""Build libcountr_hip.so (all HIP kernels + the C ABI) and the side libraries libcountr_hip_<tag>.so (SINGLE and LATER below) in-tree for gfx950.
 
 hipcc cross-compiles without a GPU, so this runs in the build container and on the GPU box.
 The .so is git-ignored but travels with the repo snapshot to the GPU box.
@@ -48,11 +48,16 @@ def _sources_of(tag):
 # tag -> (library, sources, its header)
 SINGLE = {tag: (os.path.join(HERE, "libcountr_hip_%s.so" % tag), _sources_of(tag),
                 os.path.join(HERE, "..", "include", "countr_hip_%s.h" % tag)) for tag in TAGS}
+# the table of eight is closed, as the ABI of countr_hip.h was before it.  Libraries added from here on join this second table, by the same
+# naming rule, built by the same loop, digest and flags.  A new library is a new tag at the end
+LATER_TAGS = ("draw",)
+LATER = {tag: (os.path.join(HERE, "libcountr_hip_%s.so" % tag), _sources_of(tag),
+               os.path.join(HERE, "..", "include", "countr_hip_%s.h" % tag)) for tag in LATER_TAGS}
 
 
 def build(force=False, verbose=True):
     """Compile every csrc/*.hip for gfx950 and link libcountr_hip.so + libcountr_hip_f16.so, and the sources of every side library
-    of SINGLE into that library.  An object is reused only if the record written when it was compiled (build/<variant>/<src>.o.sha256: content hash of the source, of every shared header and of the flags)
+    of SINGLE and of LATER into that library.  An object is reused only if the record written when it was compiled (build/<variant>/<src>.o.sha256: content hash of the source, of every shared header and of the flags)
     still matches -- content, not mtime, so a snapshot copy or a checkout cannot make a stale object look fresh.  COUNTR_BUILD_FORCE=1
     (or force=True / --force) recompiles everything.  Prints how many objects were compiled."""
     force = force or os.environ.get("COUNTR_BUILD_FORCE", "0") == "1"
@@ -61,12 +66,13 @@ def build(force=False, verbose=True):
     hdrs = shared + [os.path.join(HERE, "..", "include", "countr_hip.h")]
     procs, reused, total = [], 0, 0
     links = []
+    sides = dict(SINGLE, **LATER)
     jobs = int(os.environ.get("COUNTR_BUILD_JOBS", "0")) or max(2, (os.cpu_count() or 4))
-    for tag, lib, extra in VARIANTS + tuple((t, lib_, None) for t, (lib_, _s, _h) in SINGLE.items()):
+    for tag, lib, extra in VARIANTS + tuple((t, lib_, None) for t, (lib_, _s, _h) in sides.items()):
         bdir = os.path.join(HERE, "build", tag) if tag else os.path.join(HERE, "build")
         os.makedirs(bdir, exist_ok=True)
         objs, fresh = [], False
-        for src in sources() if extra is not None else SINGLE[tag][1]():
+        for src in sources() if extra is not None else sides[tag][1]():
             obj = os.path.join(bdir, os.path.basename(src) + ".o")
             objs.append(obj)
             total += 1
@@ -75,7 +81,7 @@ def build(force=False, verbose=True):
             else:
                 cmd = ([hipcc] + FLAGS + ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] + extra
                        + EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj])
-            want = _digest([src] + (hdrs if extra is not None else shared + [SINGLE[tag][2]])," ".join(cmd[1:-3]))
+            want = _digest([src] + (hdrs if extra is not None else shared + [sides[tag][2]])," ".join(cmd[1:-3]))
             rec = obj + ".sha256"
             if not force and os.path.exists(obj) and os.path.exists(rec) and open(rec).read().strip() == want:
                 reused += 1
@@ -104,7 +110,7 @@ def build(force=False, verbose=True):
             subprocess.check_call(cmd)
             open(lrec, "w").write(lwant + "\n")
     if verbose:
-        per_lib = "".join(" + %d of the %s library" % (len(srcs()), tag) for tag, (_l, srcs, _h) in SINGLE.items())
+        per_lib = "".join(" + %d of the %s library" % (len(srcs()), tag) for tag, (_l, srcs, _h) in sides.items())
         print("build_mode: %s -- %d of %d objects compiled (2 libraries x %d sources%s), %d reused after a "
               "content-hash check (source + headers + flags)"
               % ("full" if reused == 0 else "incremental", len(procs), total, len(sources()), per_lib, reused), flush=True)

@@ -16,19 +16,20 @@
 //   point_kernel      a block of 64 threads per point over the (2 r + 1)^2 box of its disc.
 //                     Each kind is a launch of its own behind the composition, so a later kind overwrites an earlier one; within a kind
 //                     every write carries the same bytes.
-//   yuv_kernel<fmt>   step 5 from the finished RGB: a thread per 16 columns x 2 rows = 8 chroma samples; `vec` as above with the yuv
-//                     pointers: 16-byte Y stores and 16-byte (NV12 / NV21) or two 8-byte (I420) chroma stores.
+//   yuv_kernel<fmt>   step 5 from the finished RGB (csrc/rgb420.hpp, shared with csrc_draw/draw.hip): a thread per 16 columns x 2 rows =
+//                     8 chroma samples; `vec` as above with the yuv pointers.
 #include <stdio.h>
 #include <string.h>
 #include "../csrc/common.hpp"
 #include "../csrc/host_api.hpp"
+#include "../csrc/rgb420.hpp"
 #include "../../include/countr_hip_overlay.h"
 
 namespace {
 
 constexpr int MAXF = COUNTR_OVERLAY_MAX_FRAMES;
-constexpr int PX = 16;                                            // columns of a thread
-constexpr int BX = 64, BY = 4;                                    // a block: 64 threads along a row x 4 row pairs
+static_assert(MAXF == 16 && COUNTR_OVERLAY_NV12 == RGB420_NV12 && COUNTR_OVERLAY_NV21 == RGB420_NV21 && COUNTR_OVERLAY_I420 == RGB420_I420,
+              "csrc/rgb420.hpp converts up to 16 frames and names the formats by the header's numbers");
 constexpr int STRIP = 8192;                                       // levels of the map a block of the composition stages in LDS
 constexpr int COORD = 1 << 20;                                    // a mark's coordinates lie in -COORD .. COORD (the Python layer refuses others)
 
@@ -36,7 +37,6 @@ struct OvArgs {
   const uint8_t* rgb[MAXF];
   const float* map[MAXF];
   uint8_t* out[MAXF];
-  uint8_t* yuv[MAXF];
   int n_points[MAXF], points_off[MAXF], n_edges[MAXF], edges_off[MAXF];
   int lh[MAXF], lw[MAXF], lx[MAXF], ly[MAXF], patch_off[MAXF];
   const uint8_t* pack;
@@ -45,7 +45,6 @@ struct OvArgs {
   uint32_t gain_max;                                              // bit j: frame j takes 255 / max(map)
   int vec;
   int radius, point_rgb, edge_rgb;
-  int yr, yg, yb, yoff, ur, ug, ub, vr, vg, vb;
 };
 
 __device__ __forceinline__ uint32_t div255(uint32_t v) { return (v * 0x8081u) >> 23; }      // exact for v < 65536
@@ -67,27 +66,6 @@ __global__ __launch_bounds__(256) void max_kernel(const OvArgs a) {
   __syncthreads();
   if (threadIdx.x == 0 && s_max) atomicMax(&a.maxbits[f], s_max);
 }
-
-// 16 pixels of a row from column x0 as 12 words; element-wise the column is clamped to W - 1
-__device__ __forceinline__ void load_px(const uint8_t* __restrict__ row, int x0, int W, bool vec, uint32_t (&o)[12]) {
-  if (vec) {
-    const uint4* p = reinterpret_cast<const uint4*>(row + 3 * x0);
-    const uint4 u = p[0], v = p[1], w = p[2];
-    o[0] = u.x; o[1] = u.y; o[2] = u.z; o[3] = u.w; o[4] = v.x; o[5] = v.y; o[6] = v.z; o[7] = v.w;
-    o[8] = w.x; o[9] = w.y; o[10] = w.z; o[11] = w.w;
-  } else {
-#pragma unroll
-    for (int q = 0; q < 12; ++q) o[q] = 0u;
-#pragma unroll
-    for (int k = 0; k < PX; ++k) {
-      const uint8_t* p = row + 3 * (int64_t)min(x0 + k, W - 1);
-#pragma unroll
-      for (int t = 0; t < 3; ++t) o[(3 * k + t) >> 2] |= (uint32_t)p[t] << (8 * ((3 * k + t) & 3));
-    }
-  }
-}
-
-__device__ __forceinline__ uint32_t byte_of(const uint32_t (&o)[12], int b) { return (o[b >> 2] >> (8 * (b & 3))) & 255u; }
 
 __device__ __forceinline__ void store_px(uint8_t* __restrict__ row, int x0, int W, bool vec, const uint32_t (&o)[12]) {
   if (vec) {
@@ -223,14 +201,6 @@ __global__ __launch_bounds__(256) void label_kernel(const OvArgs a) {
 
 __device__ __forceinline__ bool in_range(int v) { return v >= -COORD && v <= COORD; }
 
-// floor((2 a + n) / (2 n)), n > 0
-__device__ __forceinline__ int64_t rdiv(int64_t v, int64_t n) {
-  const int64_t num = 2 * v + n, den = 2 * n;
-  int64_t q = num / den;
-  if (num % den < 0) --q;
-  return q;
-}
-
 __global__ __launch_bounds__(256) void edge_kernel(const OvArgs a) {
   const int f = blockIdx.y, e = blockIdx.x;
   if (e >= a.n_edges[f]) return;
@@ -267,93 +237,6 @@ __global__ __launch_bounds__(64) void point_kernel(const OvArgs a) {
   }
 }
 
-template <int FMT>
-__global__ __launch_bounds__(BX * BY) void yuv_kernel(const OvArgs a) {
-  const int x0 = (blockIdx.x * BX + threadIdx.x) * PX;
-  const int j = blockIdx.y * BY + threadIdx.y;                    // the chroma row; luma rows 2 j and 2 j + 1
-  const int Hc = (a.H + 1) >> 1, Wc = (a.W + 1) >> 1;
-  if (x0 >= a.W || j >= Hc) return;
-  const int f = blockIdx.z;
-  const bool vec = a.vec != 0;
-  const uint8_t* __restrict__ src = a.out[f];
-  uint8_t* __restrict__ dst = a.yuv[f];
-  uint32_t o[2][12];
-  load_px(src + (int64_t)(2 * j) * a.W * 3, x0, a.W, vec, o[0]);
-  load_px(src + (int64_t)min(2 * j + 1, a.H - 1) * a.W * 3, x0, a.W, vec, o[1]);   // (an odd H: the last row again)
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const int y = 2 * j + r;
-    if (y >= a.H) break;
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int k = 0; k < PX; ++k) {
-      const int R = (int)byte_of(o[r], 3 * k), G = (int)byte_of(o[r], 3 * k + 1), B = (int)byte_of(o[r], 3 * k + 2);
-      const uint32_t Y = (uint32_t)(((a.yr * R + a.yg * G + a.yb * B + 128) >> 8) + a.yoff);
-      w[k >> 2] |= Y << (8 * (k & 3));
-    }
-    uint8_t* yrow = dst + (int64_t)y * a.W;
-    if (vec) {
-      *reinterpret_cast<uint4*>(yrow + x0) = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < PX; ++k)
-        if (x0 + k < a.W) yrow[x0 + k] = (uint8_t)((w[k >> 2] >> (8 * (k & 3))) & 255u);
-    }
-  }
-  uint32_t U[PX / 2], V[PX / 2];
-#pragma unroll
-  for (int i = 0; i < PX / 2; ++i) {
-    int s[3];
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-      s[t] = (int)((byte_of(o[0], 6 * i + t) + byte_of(o[0], 6 * i + 3 + t) + byte_of(o[1], 6 * i + t) + byte_of(o[1], 6 * i + 3 + t) + 2u) >> 2);
-    U[i] = clamp255(((a.ur * s[0] + a.ug * s[1] + a.ub * s[2] + 128) >> 8) + 128);
-    V[i] = clamp255(((a.vr * s[0] + a.vg * s[1] + a.vb * s[2] + 128) >> 8) + 128);
-  }
-  const int i0 = x0 >> 1;
-  uint8_t* c = dst + (int64_t)a.H * a.W;
-  if constexpr (FMT == COUNTR_OVERLAY_I420) {
-    uint8_t* urow = c + (int64_t)j * Wc;
-    uint8_t* vrow = urow + (int64_t)Hc * Wc;
-    if (vec) {
-      uint32_t wu[2] = {0u, 0u}, wv[2] = {0u, 0u};
-#pragma unroll
-      for (int i = 0; i < PX / 2; ++i) {
-        wu[i >> 2] |= U[i] << (8 * (i & 3));
-        wv[i >> 2] |= V[i] << (8 * (i & 3));
-      }
-      *reinterpret_cast<uint2*>(urow + i0) = make_uint2(wu[0], wu[1]);
-      *reinterpret_cast<uint2*>(vrow + i0) = make_uint2(wv[0], wv[1]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < PX / 2; ++i)
-        if (i0 + i < Wc) { urow[i0 + i] = (uint8_t)U[i]; vrow[i0 + i] = (uint8_t)V[i]; }
-    }
-  } else {
-    uint8_t* crow = c + (int64_t)j * 2 * Wc;
-    if (vec) {
-      uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int i = 0; i < PX / 2; ++i) {
-        const uint32_t lo = FMT == COUNTR_OVERLAY_NV12 ? U[i] : V[i], hi = FMT == COUNTR_OVERLAY_NV12 ? V[i] : U[i];
-        w[i >> 1] |= (lo | (hi << 8)) << (16 * (i & 1));
-      }
-      *reinterpret_cast<uint4*>(crow + 2 * i0) = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < PX / 2; ++i)
-        if (i0 + i < Wc) {
-          crow[2 * (i0 + i)] = (uint8_t)(FMT == COUNTR_OVERLAY_NV12 ? U[i] : V[i]);
-          crow[2 * (i0 + i) + 1] = (uint8_t)(FMT == COUNTR_OVERLAY_NV12 ? V[i] : U[i]);
-        }
-    }
-  }
-}
-
-// yr, yg, yb, yoff, ur, ug, ub, vr, vg, vb of [matrix][range] (the header's table)
-const int COEF[2][2][10] = {{{66, 129, 25, 16, -38, -74, 112, 112, -94, -18}, {77, 150, 29, 0, -43, -85, 128, 128, -107, -21}},
-                            {{47, 157, 16, 16, -26, -86, 112, 112, -102, -10}, {54, 184, 18, 0, -29, -99, 128, 128, -116, -12}}};
-
 // [off, off + bytes) inside the pack, behind its fixed part
 bool inside(int off, int64_t bytes, int pack_bytes) { return off >= COUNTR_OVERLAY_PACK_HEAD && (int64_t)off + bytes <= (int64_t)pack_bytes; }
 
@@ -382,7 +265,9 @@ extern "C" int countr_overlay_render(const countr_overlay_frame* frames, int n, 
   if (pack_bytes < COUNTR_OVERLAY_PACK_HEAD)
     return failf(-1, "countr_overlay_render: the packed upload has at least %d bytes, got %d", COUNTR_OVERLAY_PACK_HEAD, pack_bytes);
   OvArgs a;
+  Rgb420Args y;
   memset(&a, 0, sizeof(a));
+  memset(&y, 0, sizeof(y));
   uintptr_t bits = (uintptr_t)W;
   int max_points = 0, max_edges = 0, max_patch = 0;
   for (int j = 0; j < n; ++j) {
@@ -424,7 +309,8 @@ extern "C" int countr_overlay_render(const countr_overlay_frame* frames, int n, 
     a.rgb[j] = (const uint8_t*)fr.rgb;
     a.map[j] = (const float*)fr.map;
     a.out[j] = (uint8_t*)fr.out;
-    a.yuv[j] = (uint8_t*)fr.yuv;
+    y.src[j] = (const uint8_t*)fr.out;
+    y.dst[j] = (uint8_t*)fr.yuv;
     a.n_points[j] = fr.n_points; a.points_off[j] = fr.points_off;
     a.n_edges[j] = fr.n_edges; a.edges_off[j] = fr.edges_off;
     a.lh[j] = fr.lh; a.lw[j] = fr.lw; a.lx[j] = fr.lx; a.ly[j] = fr.ly; a.patch_off[j] = fr.patch_off;
@@ -437,8 +323,8 @@ extern "C" int countr_overlay_render(const countr_overlay_frame* frames, int n, 
   a.H = H; a.W = W; a.mh = mh; a.mw = mw;
   a.vec = (bits & 15) == 0;
   a.radius = point_radius; a.point_rgb = point_rgb & 0xffffff; a.edge_rgb = edge_rgb & 0xffffff;
-  const int* k = COEF[matrix][range];
-  a.yr = k[0]; a.yg = k[1]; a.yb = k[2]; a.yoff = k[3]; a.ur = k[4]; a.ug = k[5]; a.ub = k[6]; a.vr = k[7]; a.vg = k[8]; a.vb = k[9];
+  y.H = H; y.W = W; y.vec = a.vec;
+  set_coefficients(y, matrix, range);
   hipStream_t st = STREAM(stream);
   hipError_t e = hipSuccess;
   if (a.gain_max) {
@@ -448,14 +334,11 @@ extern "C" int countr_overlay_render(const countr_overlay_frame* frames, int n, 
     const unsigned blocks = (unsigned)(total / 1024 < 1 ? 1 : total / 1024 > 256 ? 256 : total / 1024);
     hipLaunchKernelGGL(max_kernel, dim3(blocks, (unsigned)n), dim3(256), 0, st, a);
   }
-  const int tx = (W + PX - 1) / PX, Hc = (H + 1) / 2;
-  const dim3 grid((unsigned)((tx + BX - 1) / BX), (unsigned)((Hc + BY - 1) / BY), (unsigned)n);      // <= 16 x 2048 x 16
+  const dim3 grid = rgb_grid(H, W, n);
   hipLaunchKernelGGL(compose_kernel, grid, dim3(BX, BY), 0, st, a);
   if (max_patch) hipLaunchKernelGGL(label_kernel, dim3((unsigned)((max_patch + 255) / 256), (unsigned)n), dim3(256), 0, st, a);
   if (max_edges) hipLaunchKernelGGL(edge_kernel, dim3((unsigned)max_edges, (unsigned)n), dim3(256), 0, st, a);
   if (max_points) hipLaunchKernelGGL(point_kernel, dim3((unsigned)max_points, (unsigned)n), dim3(64), 0, st, a);
-  if (format == COUNTR_OVERLAY_NV12) hipLaunchKernelGGL((yuv_kernel<COUNTR_OVERLAY_NV12>), grid, dim3(BX, BY), 0, st, a);
-  else if (format == COUNTR_OVERLAY_NV21) hipLaunchKernelGGL((yuv_kernel<COUNTR_OVERLAY_NV21>), grid, dim3(BX, BY), 0, st, a);
-  else if (format == COUNTR_OVERLAY_I420) hipLaunchKernelGGL((yuv_kernel<COUNTR_OVERLAY_I420>), grid, dim3(BX, BY), 0, st, a);
+  launch_rgb420(format, y, n, st);
   return launched("countr_overlay_render");
 }

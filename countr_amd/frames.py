@@ -550,10 +550,11 @@ def _is_shared(boxes):
     return isinstance(boxes, tuple) and len(boxes) == 2 and isinstance(boxes[0], (int, np.integer))
 
 
-def _clip_groups(who, device, frames, boxes, group):
-    """count_clip's and count_flow's walk over a clip: (items, sizes) of every consecutive group of `group` frames.  boxes: None, one
-    list per frame, or (k, boxes): the exemplar crops are then cut once, from frame k of the call, before the first group.  who: the
-    calling function's name, for the error texts."""
+def _clip_groups(who, device, frames, boxes, group, on_device=False):
+    """count_clip's and count_flow's walk over a clip: (items, sizes, frames) of every consecutive group of `group` frames.  boxes: None,
+    one list per frame, or (k, boxes): the exemplar crops are then cut once, from frame k of the call, before the first group.  who: the
+    calling function's name, for the error texts.  on_device: the group's frames go through FramePrep.device_frames first and are
+    yielded as those device tensors, so that what draws on them uploads nothing again."""
     if int(group) != group or group < 1:
         raise ValueError("%s: group is >= 1" % who)
     frames = list(frames)
@@ -565,11 +566,13 @@ def _clip_groups(who, device, frames, boxes, group):
         cut = cut_exemplars(device, frames[int(k)], bx)
     for g0 in range(0, len(frames), int(group)):
         part = frames[g0:g0 + int(group)]
+        if on_device:
+            part = frame_prep(device).device_frames(part)
         if cut is not None:
             items = shared_exemplar_items(device, part, cut)
         else:
             items = prepare_items(device, part, boxes[g0:g0 + int(group)] if boxes is not None else None)
-        yield items, _sizes(part)
+        yield items, _sizes(part), part
 
 
 @torch.no_grad()
@@ -596,21 +599,38 @@ def count_clip(model, frames, boxes=None, *, max_dist, lines=None, group=8, max_
     coordinate, rounded once: max_dist and the lines are then in pixels of the FIRST frame.  The returned points stay locate_frames'
     bytes, and each frame's tuple ends with C_t float64 (x, y).  counter=: a FlowCounter(lines=(), camera=...) to continue with
     tracker=; camera and its settings are then the counter's own."""
+    rows, clip = [], None
+    for part, clip in _track_groups("count_clip", model, frames, boxes, max_dist=max_dist, lines=lines, group=group, max_missed=max_missed,
+                                    min_hits=min_hits, beta=beta, tracker=tracker, radius=radius, threshold=threshold,
+                                    rel_threshold=rel_threshold, max_points=max_points, keep=keep, normalization=normalization,
+                                    max_s_cnt=max_s_cnt, max_batch=max_batch, camera=camera, search=search, interval=interval,
+                                    min_gain=min_gain, min_texture=min_texture, cam_tol=cam_tol, min_voters=min_voters, counter=counter):
+        if part is not None:
+            rows += [r[:6] + ((summary,) if summaries else ()) + where for r, summary, where, _crops, _frame in part]
+    return rows, clip
+
+
+def _track_groups(who, model, frames, boxes, *, max_dist, lines, group, max_missed, min_hits, beta, tracker, radius, threshold, rel_threshold,
+                  max_points, keep, normalization, max_s_cnt, max_batch, camera, search, interval, min_gain, min_texture, cam_tol, min_voters,
+                  counter, on_device=False):
+    """count_clip's walk, a group at a time, for count_clip and annotate_clip: yields ([((count, map, points, score, ids, events), summary,
+    (C_t,) or (), the nine crop maps or None, the frame), ...], ClipCounts so far) per group, and at the end (None, the clip's ClipCounts)
+    -- the tracker's own state when the clip had no frame.  on_device: _clip_groups' argument; `the frame` is then its device tensor."""
     from . import flow as flow_, tracks as tracks_
     device = next(model.parameters()).device
     if tracker is None:
         tracker = tracks_.Tracker(device, max_dist=max_dist, max_missed=max_missed, min_hits=min_hits, beta=beta, lines=lines if lines is not None else ())
     elif tracker.streams != 1 or lines is not None:
-        raise ValueError("count_clip: tracker= is a Tracker of one stream, and the lines are its own")
+        raise ValueError("%s: tracker= is a Tracker of one stream, and the lines are its own" % who)
     if counter is not None and (camera is not None or counter.camera is None or counter.lines.shape[0]):
-        raise ValueError("count_clip: counter= is a line-less FlowCounter with a camera, and the camera is its own")
+        raise ValueError("%s: counter= is a line-less FlowCounter with a camera, and the camera is its own" % who)
     if counter is None and camera is not None:
         counter = flow_.FlowCounter(device, lines=(), search=search, interval=interval, min_gain=min_gain, camera=camera,
                                     min_texture=min_texture, cam_tol=cam_tol, min_voters=min_voters)
-    out, last = [], None
-    for items, sizes in _clip_groups("count_clip", device, frames, boxes, group):
+    L, last = tracker.lines.shape[0], None
+    for items, sizes, part in _clip_groups(who, device, frames, boxes, group, on_device):
         res = locate_items(model, items, sizes, radius=radius, threshold=threshold, rel_threshold=rel_threshold, max_points=max_points,
-                           keep=keep, normalization=normalization, max_s_cnt=max_s_cnt, max_batch=max_batch)
+                           keep=keep, normalization=normalization, max_s_cnt=max_s_cnt, max_batch=max_batch, crops=True)
         points, where = [r[2] for r in res], [()] * len(res)
         if counter is not None:
             t0 = counter.frames
@@ -618,14 +638,16 @@ def count_clip(model, frames, boxes=None, *, max_dist, lines=None, group=8, max_
             path = counter.camera_path()
             where = [(path.position(t0 + k, counter.placement),) for k in range(len(res))]
             points = [(p.astype(np.float64) + c).astype(np.float32) for p, (c,) in zip(points, where)]
-        for r, c, (ids, events, summary) in zip(res, where, tracker.run(points)):
-            out.append(r[:4] + (ids, events) + ((summary,) if summaries else ()) + c)
+        out = []
+        for r, c, f, (ids, events, summary) in zip(res, where, part, tracker.run(points)):
+            out.append((r[:4] + (ids, events), summary, c, r[5], f))
             last = summary
-    L = tracker.lines.shape[0]
+        yield out, tracks_.clip_counts(last, L)
     if last is None:
         st = tracker.state()
-        return out, tracks_.ClipCounts(st["started"], st["confirmed"], st["dropped"], st["counts"][:L].astype(np.int64), st["id"].shape[0])
-    return out, tracks_.clip_counts(last, L)
+        yield None, tracks_.ClipCounts(st["started"], st["confirmed"], st["dropped"], st["counts"][:L].astype(np.int64), st["id"].shape[0])
+    else:
+        yield None, tracks_.clip_counts(last, L)
 
 
 @torch.no_grad()
@@ -660,7 +682,7 @@ def count_flow(model, frames, boxes=None, *, lines, search=4, interval=1, min_ga
     elif lines is not None or camera is not None:
         raise ValueError("count_flow: counter= is a FlowCounter, and the lines are its own" + (", and so is the camera" if lines is None else ""))
     out = []
-    for items, sizes in _clip_groups("count_flow", device, frames, boxes, group):
+    for items, sizes, _part in _clip_groups("count_flow", device, frames, boxes, group):
         res = count_items_crops(model, items, normalization, max_s_cnt, max_batch)
         t0 = counter.frames
         got = counter.run([it[0] for it in items], [None if cr is not None else dm for _c, dm, cr in res], sizes,
@@ -717,6 +739,66 @@ def annotate_frames(model, frames, boxes=None, *, out="rgb", gain=127.5, colorma
         point_radius=point_radius, regions=polygons, labels=[overlay_.count_label(r[0], *wh) if label else None for r, wh in zip(res, sizes)],
         out=out, matrix=[s[0] for s in spaces], range=[s[1] for s in spaces])
     return [(c, dm, pic, p, s) for (c, dm, _cr), pic, (p, s, _t) in zip(res, pictures, located)]
+
+
+@torch.no_grad()
+def annotate_clip(model, frames, boxes=None, *, max_dist, lines=None, line_names=None, out="rgb", heat=True, gain=127.5, colormap="red",
+                  trail=16, tags=True, tally=True, hud=True, scale=None, matrix=None, range=None, trails=None, group=8, max_missed=2,
+                  min_hits=3, beta=0.5, tracker=None, radius=4, threshold=0.0, rel_threshold=0.1, max_points=4096, keep="all",
+                  normalization=True, max_s_cnt=1, max_batch=32, summaries=False, camera=None, search=4, interval=1, min_gain=256,
+                  min_texture=128, cam_tol=8, min_voters=16, counter=None):
+    """count_clip that also shows what it found.  A GENERATOR over the clip's groups of `group` frames: each iteration yields
+    ([(count, density map, points, score, ids, events, annotated), ...] of the group's frames, ClipCounts so far); with summaries=True
+    each tuple gains the step's summary behind annotated, and with a camera it ends with C_t, as count_clip's.  count through events are
+    count_clip's bit for bit, and every other argument is count_clip's.
+    annotated is the frame's own pixels at the frame's own size: the density map as a colour overlay (heat, gain, colormap: the
+    Overlay's; a frame that took the 3 x 3 split is drawn without heat, as annotate_frames draws it), then what clip_marks draws --
+    every track's trail of the last `trail` positions (0: none) in the track's colour, the counting lines with their names
+    (line_names, default "0", "1", ...) and running tallies, a disc and the id per point, and count, live tracks and confirmed total at
+    the top left; scale: the marks' size, default by the frame's height (countr_amd/draw.py states the rule).  It is a uint8 device
+    tensor [H, W, 3], or for out = "nv12" / "nv21" / "i420" the packed 4:2:0 buffer YuvFrame.from_buffer reads, in `matrix` / `range`
+    (default: a YuvFrame's own, bt709 / limited for other frames).  THE TENSORS ARE BUFFERS of the device's Overlay and Painter: they are
+    valid until the next iteration, which overwrites them -- that is why this is a generator; copy what must outlive the step.
+    Every frame goes to the device once (FramePrep.device_frames).  Per group: count_clip's locate path and Tracker.run, then
+    Overlay.render and Painter.paint on the same stream, with no synchronisation beyond count_clip's one per group -- the marks are built
+    from what that download brought.  trails=: a draw.Trails to continue with tracker= (the live-stream case; `trail` is then its own).
+    zoom is not taken."""
+    from . import draw as draw_
+    device = next(model.parameters()).device
+    frames = list(frames)
+    spaces = [(matrix or (f.matrix if isinstance(f, yuv_.YuvFrame) else "bt709"), range or (f.range if isinstance(f, yuv_.YuvFrame) else "limited"))
+              for f in frames]
+    if trails is None and trail:
+        trails = draw_.Trails(trail)
+    done = 0
+    for part, clip in _track_groups("annotate_clip", model, frames, boxes, max_dist=max_dist, lines=lines, group=group, max_missed=max_missed,
+                                    min_hits=min_hits, beta=beta, tracker=tracker, radius=radius, threshold=threshold,
+                                    rel_threshold=rel_threshold, max_points=max_points, keep=keep, normalization=normalization,
+                                    max_s_cnt=max_s_cnt, max_batch=max_batch, camera=camera, search=search, interval=interval,
+                                    min_gain=min_gain, min_texture=min_texture, cam_tol=cam_tol, min_voters=min_voters, counter=counter,
+                                    on_device=True):
+        if part is None:
+            return
+        if tracker is None:          # the lines as the tracker holds them: what was counted is what is drawn
+            drawn = np.asarray(lines if lines is not None else (), np.float32).reshape(-1, 4)
+        else:
+            drawn = tracker.lines
+        names = list(line_names) if line_names is not None else ["%d" % k for k in np.arange(len(drawn))]
+        if len(names) != len(drawn):
+            raise ValueError("annotate_clip: one name per line")
+        pictures = overlay_.overlay_for(device).render(
+            [f for _r, _s, _c, _cr, f in part], [r[1] if (heat and cr is None) else None for r, _s, _c, cr, _f in part], gain=gain,
+            colormap=colormap, out="rgb")
+        marks = []
+        for r, summary, where, _cr, f in part:
+            pos = r[2].astype(np.float64) + (where[0] if where else 0.0)                   # scene pixels under a camera
+            marks.append(draw_.clip_marks(r[2], r[4], r[5], summary, names, drawn, r[0], where[0] if where else None,
+                                          size=(int(f.shape[1]), int(f.shape[0])), trails=trails.update(pos, r[4]) if trails is not None else None,
+                                          scale=scale, tags=tags, tally=tally, hud=hud))
+        sp = spaces[done:done + len(part)]
+        done += len(part)
+        painted = draw_.painter_for(device).paint(pictures, marks, out=out, matrix=[a for a, _b in sp], range=[b for _a, b in sp])
+        yield [r + (pic,) + ((summary,) if summaries else ()) + where for (r, summary, where, _cr, _f), pic in zip(part, painted)], clip
 
 
 def map_placement(W, H, new_w, new_h=NEW_H):

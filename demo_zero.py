@@ -38,6 +38,11 @@ two frames in pixels of the frame, --lines_json is {"name": [[ax, ay], [bx, by]]
 Each frame's line gains ` - tracks: <live> - crossed: {name: [forward, backward]}` (the crossings of that frame), points_<stem>_<i>.json gains
 "ids", viz_*.jpg gets the lines, and at the end {"clip": {"started", "confirmed", "lines": {name: [forward, backward]}}} is printed and
 written to tracks_<stem>.json.  The defaults of --track_missed and --track_hits are unmeasured.  Without --track nothing changes.
+With `--out_yuv` or `--device_viz`, --track goes through countr_amd.frames.annotate_clip instead: the written frames (and viz_*.jpg under
+--device_viz) carry every track's id and trail in its colour, the counting lines with their running tallies, and count, live tracks and
+confirmed total at the top left, drawn on the device (countr_amd/draw.py states the rule); `--trail N` (default 16, 0 = none) is the
+trail's length in positions, `--no_tags` leaves the ids out, `--mark_scale S` sets the marks' size.  The printed lines and JSON files
+are the same.
 `--flow --lines_json FILE [--flow_search R] [--flow_interval S] [--flow_band W]` (with --yuv, at --zoom 1, without --track) counts the
 crossings of the same lines from the flux of the density map instead (countr_amd.frames.count_flow, include/countr_hip_flow.h): no peaks
 and no tracks.  Each frame's line gains ` - flux: {name: [forward, backward]}` (that frame's share; null for the first S frames) and at
@@ -345,23 +350,49 @@ def run_track(args, model, device, clip):
     if args.camera:
         from countr_amd.flow import FlowCounter
         counter = FlowCounter(device, lines=(), search=args.flow_search, interval=args.flow_interval, camera=args.camera)
+    out_file, out_format, trails = None, "rgb", None
+    if args.out_yuv is not None:
+        out_path, out_format = parse_out_yuv(args.out_yuv, clip[0].format)
+        out_file = open(out_path, "wb")
+    drawn = out_file is not None or args.device_viz          # the annotated clip: ids, trails, lines and tallies composed on the device
+    if drawn and args.trail:
+        from countr_amd.draw import Trails
+        trails = Trails(args.trail)
     for g0 in range(0, len(clip), group):
         raw = clip[g0:g0 + group]
         t0 = time.perf_counter()
-        got, clip_counts = frames.count_clip(model, raw, max_dist=args.track_dist, group=group, tracker=tracker, normalization=False,
-                                             summaries=True, counter=counter, **peak)
+        pics = [None] * len(raw)
+        if drawn:
+            (got, clip_counts), = frames.annotate_clip(model, raw, max_dist=args.track_dist, group=group, tracker=tracker, normalization=False,
+                                                       summaries=True, counter=counter, line_names=names, out=out_format, trail=args.trail,
+                                                       trails=trails, tags=not args.no_tags, scale=args.mark_scale, **peak)
+            pics = [r[6].cpu().numpy() for r in got]
+            got = [r[:6] + r[7:] for r in got]
+        else:
+            got, clip_counts = frames.count_clip(model, raw, max_dist=args.track_dist, group=group, tracker=tracker, normalization=False,
+                                                 summaries=True, counter=counter, **peak)
         dt = (time.perf_counter() - t0) / len(raw)
         # the number of peaks found, for points_<stem>.json: the peak finder once more, no forward
         totals = [t for _p, _s, t in frames.locate_maps([(r[0], r[1]) for r in got], [(w, h)] * len(raw), **peak)]
         for k, (f, (pred_cnt, dm, pts, score, ids, events, summary, *where), total) in enumerate(zip(raw, got, totals)):
             name = "%s_%d" % (stem, g0 + k)
             write_points(args.output_path / ("points_%s.json" % name), pred_cnt, total, pts, score, ids)
-            if not args.no_viz:
+            if out_file is not None:
+                out_file.write(pics[k].tobytes())
+            if args.device_viz:
+                if not args.no_viz:
+                    pic = pics[k]
+                    if out_file is not None:
+                        pic = yuv.yuv_host(yuv.YuvFrame.from_buffer(pic, w, h, format=out_format, matrix=f.matrix, range=f.range))
+                    Image.fromarray(pic).save(args.output_path / ("viz_%s.jpg" % name))
+            elif not args.no_viz:
                 sample = prep.prepare([yuv.yuv_host(f)])[0][0]
                 save_visualisation(sample, dm.float(), pred_cnt, args.output_path / ("viz_%s.jpg" % name), w, h, points=pts, lines=lines)
             crossed = {n: [int(((events >> j) & 1).sum()), int(((events >> (16 + j)) & 1).sum())] for j, n in enumerate(names)}
             print("%s#%d: Count: %s - Time: %s - tracks: %d - crossed: %s%s" % (stem, g0 + k, pred_cnt, dt, int(summary[0]), json.dumps(crossed),
                                                                                cam_text(where)))
+    if out_file is not None:
+        out_file.close()
     doc = {"clip": {"started": clip_counts.started, "confirmed": clip_counts.confirmed,
                     "lines": {n: [int(v) for v in clip_counts.line_counts[j]] for j, n in enumerate(names)}}}
     add_camera(doc, counter)
@@ -423,6 +454,9 @@ def main():
     p.add_argument("--lines_json", type=Path, default=None, help='with --track: counting lines {"name": [[ax, ay], [bx, by]], ...}, up to 16')
     p.add_argument("--track_missed", type=int, default=2, help="a track survives this many frames without a detection (the default is unmeasured)")
     p.add_argument("--track_hits", type=int, default=3, help="detections that confirm a track (the default is unmeasured)")
+    p.add_argument("--trail", type=int, default=16, help="with --track and --out_yuv or --device_viz: positions of a track's drawn trail (0 = none)")
+    p.add_argument("--no_tags", action="store_true", help="with --track and --out_yuv or --device_viz: no id beside the points")
+    p.add_argument("--mark_scale", type=int, default=None, help="with --track and --out_yuv or --device_viz: the marks' size 1..8 (default by the height)")
     p.add_argument("--flow", action="store_true", help="with --yuv and --lines_json: line crossings from the flux of the density map")
     p.add_argument("--flow_search", type=int, default=4, help="with --flow: the motion search radius in map pixels (the default is unmeasured)")
     p.add_argument("--flow_interval", type=int, default=1, help="with --flow: match against the frame this many frames back (slow motion needs > 1)")
@@ -438,8 +472,10 @@ def main():
     if args.track:
         if not args.yuv or args.track_dist is None:
             p.error("--track is for --yuv and needs --track_dist")
-        if zoom != 1 or args.regions_json is not None or args.out_yuv is not None or args.device_viz:
-            p.error("--track is for --zoom 1, without --regions_json, --out_yuv and --device_viz")
+        if zoom != 1 or args.regions_json is not None:
+            p.error("--track is for --zoom 1, without --regions_json")
+        if args.trail < 0 or (args.mark_scale is not None and not 1 <= args.mark_scale <= 8):
+            p.error("--trail is >= 0 and --mark_scale is 1..8")
         args.points = True
     elif args.flow:
         if not args.yuv or args.lines_json is None or args.track_dist is not None:
