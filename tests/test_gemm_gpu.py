@@ -296,7 +296,8 @@ def test_wgrad_with_fused_bias_gradient(hip):
 
 def test_gemm_randomised_shapes_strides_and_options(hip):
     """Seeded sweep over operand modes, ragged and padded shapes (leading dimensions larger than the row), both dtypes, bias /
-    residual / GELU / output-type options, split-K and grid sizes on both sides of the kernel-selection thresholds (256 workgroups:
+    residual / GELU / output-type options (operand pads and the ldc pad of the output are NaN: the pads must not be read into a result
+    and must come back NaN), split-K and grid sizes on both sides of the kernel-selection thresholds (256 workgroups:
     wave-specialised vs plain; K a multiple of 64 or not: uniform-base vs per-lane addressing)."""
     import random
     rng = random.Random(1234)
@@ -313,8 +314,9 @@ def test_gemm_randomised_shapes_strides_and_options(hip):
         M, N = -(-M // chunk) * chunk, -(-N // chunk) * chunk
         pad = rng.choice([0, chunk, 5 * chunk])
         A, B = _mk((M, K), dt, 100 + it), _mk((N, K), dt, 200 + it)
-        As = torch.zeros((M, K + pad) if ma == 0 else (K, M + pad), device="cuda", dtype=dt)
-        Bs = torch.zeros((N, K + pad) if mb == 0 else (K, N + pad), device="cuda", dtype=dt)
+        # the pad columns hold NaN: a kernel that multiplies them (a lost K-tail or ragged-edge mask) cannot pass
+        As = torch.full((M, K + pad) if ma == 0 else (K, M + pad), float("nan"), device="cuda", dtype=dt)
+        Bs = torch.full((N, K + pad) if mb == 0 else (K, N + pad), float("nan"), device="cuda", dtype=dt)
         (As[:, :K] if ma == 0 else As[:, :M]).copy_(A if ma == 0 else A.t())
         (Bs[:, :K] if mb == 0 else Bs[:, :N]).copy_(B if mb == 0 else B.t())
         a = _lib.GemmArgs()
@@ -335,7 +337,7 @@ def test_gemm_randomised_shapes_strides_and_options(hip):
         else:
             obf = code == 1 and rng.random() < 0.5
             ldc = N + rng.choice([0, 8])
-            out = torch.zeros((M, ldc), device="cuda", dtype=torch.bfloat16 if obf else torch.float32)
+            out = torch.full((M, ldc), float("nan"), device="cuda", dtype=torch.bfloat16 if obf else torch.float32)
             a.C, a.ldc, a.out_bf16 = out.data_ptr(), ldc, int(obf)
             opt = rng.choice(["plain", "bias", "bias+gelu", "bias+resid", "resid"])
             if "bias" in opt:
@@ -351,6 +353,7 @@ def test_gemm_randomised_shapes_strides_and_options(hip):
                 a.resid, a.ldres, a.res_mod = res.data_ptr(), N, rmod
                 ref = ref + (res.double() if not rmod else res.double()[torch.arange(M, device="cuda") % rmod])
             _lib.check(hip.countr_gemm(C.byref(a), code, ma, mb, _stream()), "gemm")
+            assert torch.isnan(out[:, N:].float()).all(), (it, "ldc pad written")
             out = out[:, :N]
             tol = 2e-2 if obf else (3e-3 if ("gelu" in opt and code) else 2e-4)   # bf16 GELU uses the 1.5e-7-accurate fast erf
         torch.cuda.synchronize()
